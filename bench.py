@@ -4,14 +4,18 @@
     python bench.py --gpus 1 --steps 3 --warmup 1
     python bench.py --gpus N ...            (starts N ranks itself: a child `python -m torch.distributed.run`, before any GPU call)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+    python bench.py --full                   (the headline plus everything below: roofline, second transform mode, CPU baseline, side legs)
+    python bench.py --dump-outputs DIR       (also writes the last timed frame's result as DIR/<name>.npy, float64)
     python bench.py --all-configs            (the five BASELINE.json configurations, one JSON line each, into profiles/ with --out-dir)
     python bench.py --decode                 (the decoder on the same configuration: frames/s, stage split)
-    python bench.py --no-legs                (the headline only: no side legs - see below)
+    python bench.py --full --no-legs         (everything but the side legs - see below)
 
+A plain run sets up, warms up, times `--steps` frames and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`, `dtype`, `bpp_mean`,
+...).  Every other measurement and check below runs only with `--full`, after the timed region.
 The headline `value` is measured in STRICT-IDENTITY mode (round 5): the float -> integer step is the reference's own numpy float32 arithmetic
-(data_preprocess.py:42-70,171-214) on a prefetch thread, inside the timed region, and the run asserts that 0 points of the seed-0 frame differ
-from the reference's integers (`transform_parity`); the device-transform rate is the extra key `device_transform`.
-After the headline (outside its timed region, N = 1 only) the default run adds short legs, each a child process running this file
+(data_preprocess.py:42-70,171-214) on a prefetch thread, inside the timed region; `--full` asserts that 0 points of the seed-0 frame differ
+from the reference's integers (`transform_parity`) and adds the device-transform rate as the extra key `device_transform`.
+After the headline (outside its timed region, N = 1 only) `--full` adds short legs, each a child process running this file
 (5 warm-up + 16 timed frames; 32 for the batched L12 workload): the other four BASELINE.json workloads and the decoder under `configs`, and a `cli` leg - `.bin` files on disk
 through the drop-in `encode_mullevel.py` (file read, parse, host -> device copy and the written `.bin` / `.dat` inside) - with `cli_over_bench`;
 `decode_2_procs` / `decode_4_procs`: independent decoder processes sharing the GPU (a decode is a serial chain of short launches: streams scale by process).
@@ -23,7 +27,7 @@ on the host inside the timed region, as in a real encode.  Frames are independen
 (weak scaling), the only collective is the end-of-run all-reduce of the 5 summary scalars (RCCL).
 Prints ONE JSON line on rank 0.
 
-How the roofline numbers of the line are measured (round 4): `native.launch_profile` switches on the launch brackets of the C ABI
+How the roofline numbers of the `--full` line are measured (round 4): `native.launch_profile` switches on the launch brackets of the C ABI
 (include/scp_debug.h: scp_prof_*): inside libscp_hip.so every hot entry point records a hipEvent immediately before and
 immediately after its hipLaunchKernelGGL, on the stream the kernel is launched on - no Python, no allocation between the two
 records.  One untimed frame warms the measuring stream's allocator pool, three frames are measured, every launch keeps its MINIMUM
@@ -58,19 +62,23 @@ def parse():
     ap.add_argument("--steps", type=int, default=None, help="timed frames per rank (default 48; 3 with --decode)")
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--config", default="ehem-L16-m", choices=sorted(CONFIGS))
-    ap.add_argument("--cpu-baseline", default="sample", choices=["sample", "full", "none"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline: the live roofline, per-stage times, the second transform mode, the "
+                    "transform-parity check, the CPU baseline and the side legs (the options below marked 'with --full' tune these)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write the result of the last timed frame "
+                    "(rank 0) as DIR/<name>.npy in float64: the byte stream as byte values, bits, bpp, node / point counts, level sizes, ...")
+    ap.add_argument("--cpu-baseline", default="sample", choices=["sample", "full", "none"], help="with --full")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full")
     ap.add_argument("--depth", type=int, default=4, help="frames in flight (encode_async handles not yet finished); 4 measured 1.2 % above 3, 5 no better")
     ap.add_argument("--batch", type=int, default=None, help="frames per stage-G / packed-forward / CDF launch (FrameEncoder.encode_batch_async); "
                     "default: 8 for the level-12 EHEM configuration (a 115 k-node frame is 22 windows), 1 elsewhere")
     ap.add_argument("--host-transform", action="store_true", help="(default for the EHEM configurations since round 5) strict-identity mode as the "
                     "HEADLINE: the reference's numpy float32 transform + quantiser on a prefetch thread one to two frames ahead")
     ap.add_argument("--device-transform", action="store_true", help="headline with the device transform (rounds 1 - 4); the strict leg becomes the extra key")
-    ap.add_argument("--no-strict-leg", action="store_true", help="skip the second timed loop (the other transform mode)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the side legs (the other four workloads, the decoder, the CLI), which run as child processes "
-                    "after the headline, outside its timed region")
-    ap.add_argument("--leg-steps", type=int, default=16)
-    ap.add_argument("--leg-warmup", type=int, default=5)
+    ap.add_argument("--no-strict-leg", action="store_true", help="with --full: skip the second timed loop (the other transform mode)")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the side legs (the other four workloads, the decoder, the CLI), which run as "
+                    "child processes after the headline, outside its timed region")
+    ap.add_argument("--leg-steps", type=int, default=16, help="with --full")
+    ap.add_argument("--leg-warmup", type=int, default=5, help="with --full")
     ap.add_argument("--oa-batch", type=int, default=None, help="OctAttention: windows per forward (OctAttnFrameEncoder.max_batch)")
     ap.add_argument("--decode", action="store_true", help="time the decoder (FrameDecoder) on the configuration's frame instead of the encoder")
     ap.add_argument("--proc-barrier", default=None, metavar="DIR:N", help="with --decode: this process is one of N decoder processes sharing the GPU; after its warm-up it "
@@ -81,6 +89,8 @@ def parse():
     ap.add_argument("--out-dir", default=None, help="with --all-configs: also write <out-dir>/<tag>_bench_<config>.json")
     ap.add_argument("--tag", default="r4", help="file-name prefix used with --out-dir")
     a = ap.parse_args()
+    if a.dump_outputs and (a.decode or a.all_configs):
+        ap.error("--dump-outputs writes the encoder's result: not with --decode or --all-configs")
     if a.steps is None:
         a.steps = 3 if a.decode else 48      # (four frames are in flight: 24 timed frames left the fill / drain of the pipeline at 2 - 4 % of the figure, 14.7 - 15.2 against 15.3 - 15.4)
     return a
@@ -549,7 +559,7 @@ def cli_leg(n_warm, n_timed):
 def side_legs(args, out):
     """The other four BASELINE.json workloads, the decoder and the CLI, after the headline and outside its timed region (N = 1 only)."""
     torch.cuda.empty_cache()
-    common = ["--steps", str(args.leg_steps), "--warmup", str(args.leg_warmup), "--cpu-baseline", "none", "--no-legs", "--no-strict-leg"]
+    common = ["--steps", str(args.leg_steps), "--warmup", str(args.leg_warmup), "--full", "--cpu-baseline", "none", "--no-legs", "--no-strict-leg"]
 
     def brief(z):
         if "error" in z:
@@ -580,6 +590,21 @@ def side_legs(args, out):
         out["cli_over_bench"] = out["cli"]["fps"] / out["value"]
     out["legs_note"] = ("`configs` / `decode` / `cli`: child processes of this run, started after the headline's timed region; each is this file's own "
                         "timed loop (barrier + synchronize on both sides) on that workload")
+
+
+def dump_outputs(out_dir, res):
+    """`--dump-outputs`: the result dict the timed path hands its caller for the last timed frame (FrameEncoder.finish /
+    OctAttnFrameEncoder.finish), one float64 array per field; the byte stream as its byte values."""
+    arrays = dict(stream=np.frombuffer(bytes(res["bytes"]), np.uint8), bits=res["bits"], bpp=res["bpp"], n_nodes=res["n_nodes"],
+                  n_points=res["n_points"], n_levels=res["n_levels"], level_sizes=res["level_sizes"], bin_num=res["bin_num"],
+                  z_offset=res["z_offset"], pos_mm=res["pos_mm"])
+    if res.get("bin_nums") is not None:
+        arrays["bin_nums"] = res["bin_nums"]
+    if res.get("quant"):
+        arrays["quant"] = [[q["qs"], q["offset"]] for q in res["quant"]]         # [shell, (qs, offset), xyz]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(v, np.float64))
 
 
 def main():
@@ -702,7 +727,7 @@ def main():
     headline_strict = ehem and not args.device_transform
     dt_own, dt, cpu_ms, results = timed_loop(headline_strict)
     other = None
-    if ehem and world == 1 and not args.no_strict_leg:
+    if args.full and ehem and world == 1 and not args.no_strict_leg:
         s_own, s_dt, s_cpu, s_res = timed_loop(not headline_strict)
         other = dict(fps=args.steps / s_dt, ms_per_step=1e3 * s_dt / args.steps, host_cpu_ms_per_frame=s_cpu,
                      ratio_to_headline=(args.steps / s_dt) / (args.steps / dt), bpp_mean=float(np.mean([r["bpp"] for r in s_res])),
@@ -732,29 +757,7 @@ def main():
 
     if rank == 0:
         n_nodes = results[-1]["n_nodes"]
-        P = results[-1]["n_points"]
-        peak3 = BF16_MFMA_PEAK_TFLOPS / 3.0
-        bytes_G = 12 * P + 25 * n_nodes            # SURVEY.md §8d algorithmic bytes of stage G
-        bytes_C = n_nodes * (255 * 4 + 4)
         level_sizes = results[-1]["level_sizes"]
-        # ---- live kernel measurement on the caller's stream (single stream: a bracket never spans another lane's kernel)
-        recs = measure_kernels(lambda: enc.encode(frames[-1]))
-        per_tag = summarise(recs, knn_pairs(enc, level_sizes) if ehem else None)
-        # per-stage wall times of the same frame with a device sync after every stage: the faster of two runs
-        if ehem:
-            st = min((enc.encode(frames[-1], timing=True)["times"] for _ in range(2)), key=lambda t: t["total"])
-        else:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter(); enc.encode(frames[-1]); torch.cuda.synchronize()
-            st = {"total": time.perf_counter() - t0}
-        model_tags = [t for t in per_tag if t not in ("cdf", "geom")]
-        kernel_ms = sum(per_tag[t]["total_ms"] for t in model_tags)
-        ref_ms = 1e3 * (st["model"] if ehem else st["total"])
-        valid = kernel_ms <= 1.02 * ref_ms
-        dom_tag = max((t for t in per_tag if KERNEL_OF.get(t, ("", ""))[1] == "mfma"), key=lambda t: per_tag[t]["total_ms"])
-        dom = roofline_entry(dom_tag, per_tag[dom_tag])
-        traffic, frame_bytes, traffic_src = pmc_traffic(args.config)
-        fl_total, fl_att = frame_flops(cfg, level_sizes, n_nodes)
         ms_step = 1e3 * dt / args.steps
         if ehem:
             metric = "KITTI frames/sec encode (SCP-EHEM, level 16) + bpp match vs ref"
@@ -782,71 +785,98 @@ def main():
             "rccl_world": dist.get_world_size() if dist_on else 1, "dist_backend": backend if dist_on else None,
             "host_cpu_ms_per_frame": cpu_ms,
             "bpp_mean": float(summ[0] / summ[4]),
-            "stage_ms": {k: round(1e3 * v, 3) for k, v in st.items()},
-            # dominant kernel = the MFMA-bound kernel with the most time per frame.  `achieved` counts ALGORITHMIC flops (2*M*N*K of the fp32
-            # product it replaces); a split kernel spends three 16-bit MFMAs per product, so its own ceiling is a third of the dense 16-bit peak.
-            "roofline": {"bound": "mfma", "kernel": dom["kernel"] + ": " + dom["note"] + " (3x v_mfma_f32_32x32x16 per fp32-class product)",
-                         "achieved": dom["achieved"], "peak": peak3, "unit": "TFLOP/s", "frac": dom["frac"],
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "valid": bool(valid), "kernel_ms_sum": kernel_ms, "kernel_ms_bound": ref_ms,
-                         "validity_rule": "event-timed kernels of one frame (per-launch minimum over 3 frames) must sum to <= 1.02 x the synchronised wall "
-                                          "time of the same frame's model stage; false = do not use these fractions",
-                         "method": "hipEvents recorded inside libscp_hip.so around each launch (include/scp_debug.h), allocator-warm stream, per-launch minimum of 3 frames",
-                         "peak_note": "2500 TFLOP/s dense 16-bit MFMA / 3 products; the fp32 MFMA peak this replaces is 157.3.  With all 256 CUs multiplying the clock settles at 1.85 GHz (tools/src/mb_power.cpp): 1.95 PFLOP/s sustained, 650 per fp32-class product; this kernel runs at 1.91 GHz inside the frame (GRBM_GUI_ACTIVE / duration, profiles/r4k_kernel_clocks.md)",
-                         "launches_per_frame": dom["launches_per_frame"], "avg_launch_us": dom["avg_launch_us"], "flops_per_launch": dom["flops_per_launch"]},
-            # the whole frame against both roofs: algorithmic flop of what the reference's window loop computes (encode_mullevel.py:106-133;
-            # SURVEY.md 8d formulas on the frame's real window lengths) / the bench's own ms_per_step
-            "roofline_frame": {"flops": fl_total, "attention_flops": fl_att, "achieved_tflops": fl_total / (ms_step * 1e-3) / 1e12 / world,
-                               "peak_tflops": peak3, "frac_mfma": fl_total / (ms_step * 1e-3) / 1e12 / world / peak3,
-                               "hbm_bytes": frame_bytes, "achieved_gbs": None if frame_bytes is None else frame_bytes / (ms_step * 1e-3) / 1e9 / world,
-                               "frac_hbm": None if frame_bytes is None else frame_bytes / (ms_step * 1e-3) / 1e9 / world / HBM_PEAK_GBS,
-                               "note": "per GPU; flops priced against 2500 / 3 TFLOP/s as if every product were a three-MFMA split; hbm_bytes from " + (traffic_src or "no PMC pass for this configuration")},
-            "roofline_kernels": {KERNEL_OF.get(t, (t,))[0]: roofline_entry(t, per_tag[t]) for t in sorted(per_tag, key=lambda t: -per_tag[t]["total_ms"])},
-            "launches_bracketed_per_frame": len(recs),
         }
-        if ehem:
-            out["roofline_stages"] = {
-                "G": {"bound": "hbm", "achieved": bytes_G / st["geom"] / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                      "frac": bytes_G / st["geom"] / 1e9 / HBM_PEAK_GBS, "bytes": bytes_G, "note": "host wall time of the whole stage incl. its small D2H syncs"},
-                "C": {"bound": "hbm", "achieved": bytes_C / st["cdf"] / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                      "frac": bytes_C / st["cdf"] / 1e9 / HBM_PEAK_GBS, "bytes": bytes_C, "note": "includes the 4 B/node D2H copy"}}
-            if other is not None:
-                out["device_transform" if headline_strict else "strict_identity"] = other
-                out["strict_identity_fps"] = out["value"] if headline_strict else other["fps"]
-                out["device_transform_fps"] = other["fps"] if headline_strict else out["value"]
-            try:
-                out["transform_parity"] = differing_points(enc, cfg, dev)
-            except Exception as e:
-                out["transform_parity"] = {"error": str(e)}
-            tp = out["transform_parity"]
-            if headline_strict and tp is not None and "host_transform" in tp:
-                # asserted in-run: the headline's integers ARE the reference's (tests/golden/frame_ints.npz, written by running the reference's proc_pc)
-                out["strict_identity_verified"] = all(v == 0 for v in tp["host_transform"])
-                if not out["strict_identity_verified"]:
-                    raise SystemExit(f"strict-identity headline, but the host transform's integers differ from the reference's: {tp}")
-            elif headline_strict:
-                out["strict_identity_verified"] = None      # no reference integers for this workload's frames in tests/golden/
-        if not ehem:
-            try:
-                out["transform_parity"] = differing_points(enc, cfg, dev)     # OctAttention legs run the device transform: how many points it misses
-            except Exception as e:
-                out["transform_parity"] = {"error": str(e)}
         if rank_stats:
             fps = [r["fps"] for r in rank_stats]
             cpu = [r["host_cpu_ms_per_frame"] for r in rank_stats]
             out["ranks"] = {"fps_min": min(fps), "fps_max": max(fps), "host_cpu_ms_per_frame_min": min(cpu), "host_cpu_ms_per_frame_max": max(cpu),
                             "shared_frame_streams_identical": len({r["shared_frame_sha256"] for r in rank_stats}) == 1, "per_rank": rank_stats}
-        mode = "none" if args.no_cpu_baseline else args.cpu_baseline
-        if world == 1 and mode != "none":
-            try:
-                out["cpu_baseline"] = cpu_baseline(cfg, frames_host[-1], full=mode == "full", config=args.config)
-            except Exception as e:   # the baseline is a reported number, never a reason to lose the bench line
-                out["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
-        if world == 1 and not args.no_legs and args.config == "ehem-L16-m":
-            try:
-                side_legs(args, out)
-            except Exception as e:     # a leg is extra information, never a reason to lose the headline
-                out["legs_error"] = repr(e)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, results[-1])
+        if args.full:
+            P = results[-1]["n_points"]
+            peak3 = BF16_MFMA_PEAK_TFLOPS / 3.0
+            bytes_G = 12 * P + 25 * n_nodes            # SURVEY.md §8d algorithmic bytes of stage G
+            bytes_C = n_nodes * (255 * 4 + 4)
+            # ---- live kernel measurement on the caller's stream (single stream: a bracket never spans another lane's kernel)
+            recs = measure_kernels(lambda: enc.encode(frames[-1]))
+            per_tag = summarise(recs, knn_pairs(enc, level_sizes) if ehem else None)
+            # per-stage wall times of the same frame with a device sync after every stage: the faster of two runs
+            if ehem:
+                st = min((enc.encode(frames[-1], timing=True)["times"] for _ in range(2)), key=lambda t: t["total"])
+            else:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter(); enc.encode(frames[-1]); torch.cuda.synchronize()
+                st = {"total": time.perf_counter() - t0}
+            model_tags = [t for t in per_tag if t not in ("cdf", "geom")]
+            kernel_ms = sum(per_tag[t]["total_ms"] for t in model_tags)
+            ref_ms = 1e3 * (st["model"] if ehem else st["total"])
+            valid = kernel_ms <= 1.02 * ref_ms
+            dom_tag = max((t for t in per_tag if KERNEL_OF.get(t, ("", ""))[1] == "mfma"), key=lambda t: per_tag[t]["total_ms"])
+            dom = roofline_entry(dom_tag, per_tag[dom_tag])
+            traffic, frame_bytes, traffic_src = pmc_traffic(args.config)
+            fl_total, fl_att = frame_flops(cfg, level_sizes, n_nodes)
+            out.update({
+                "stage_ms": {k: round(1e3 * v, 3) for k, v in st.items()},
+                # dominant kernel = the MFMA-bound kernel with the most time per frame.  `achieved` counts ALGORITHMIC flops (2*M*N*K of the fp32
+                # product it replaces); a split kernel spends three 16-bit MFMAs per product, so its own ceiling is a third of the dense 16-bit peak.
+                "roofline": {"bound": "mfma", "kernel": dom["kernel"] + ": " + dom["note"] + " (3x v_mfma_f32_32x32x16 per fp32-class product)",
+                             "achieved": dom["achieved"], "peak": peak3, "unit": "TFLOP/s", "frac": dom["frac"],
+                             "traffic": traffic, "traffic_source": traffic_src,
+                             "valid": bool(valid), "kernel_ms_sum": kernel_ms, "kernel_ms_bound": ref_ms,
+                             "validity_rule": "event-timed kernels of one frame (per-launch minimum over 3 frames) must sum to <= 1.02 x the synchronised wall "
+                                              "time of the same frame's model stage; false = do not use these fractions",
+                             "method": "hipEvents recorded inside libscp_hip.so around each launch (include/scp_debug.h), allocator-warm stream, per-launch minimum of 3 frames",
+                             "peak_note": "2500 TFLOP/s dense 16-bit MFMA / 3 products; the fp32 MFMA peak this replaces is 157.3.  With all 256 CUs multiplying the clock settles at 1.85 GHz (tools/src/mb_power.cpp): 1.95 PFLOP/s sustained, 650 per fp32-class product; this kernel runs at 1.91 GHz inside the frame (GRBM_GUI_ACTIVE / duration, profiles/r4k_kernel_clocks.md)",
+                             "launches_per_frame": dom["launches_per_frame"], "avg_launch_us": dom["avg_launch_us"], "flops_per_launch": dom["flops_per_launch"]},
+                # the whole frame against both roofs: algorithmic flop of what the reference's window loop computes (encode_mullevel.py:106-133;
+                # SURVEY.md 8d formulas on the frame's real window lengths) / the bench's own ms_per_step
+                "roofline_frame": {"flops": fl_total, "attention_flops": fl_att, "achieved_tflops": fl_total / (ms_step * 1e-3) / 1e12 / world,
+                                   "peak_tflops": peak3, "frac_mfma": fl_total / (ms_step * 1e-3) / 1e12 / world / peak3,
+                                   "hbm_bytes": frame_bytes, "achieved_gbs": None if frame_bytes is None else frame_bytes / (ms_step * 1e-3) / 1e9 / world,
+                                   "frac_hbm": None if frame_bytes is None else frame_bytes / (ms_step * 1e-3) / 1e9 / world / HBM_PEAK_GBS,
+                                   "note": "per GPU; flops priced against 2500 / 3 TFLOP/s as if every product were a three-MFMA split; hbm_bytes from " + (traffic_src or "no PMC pass for this configuration")},
+                "roofline_kernels": {KERNEL_OF.get(t, (t,))[0]: roofline_entry(t, per_tag[t]) for t in sorted(per_tag, key=lambda t: -per_tag[t]["total_ms"])},
+                "launches_bracketed_per_frame": len(recs),
+            })
+            if ehem:
+                out["roofline_stages"] = {
+                    "G": {"bound": "hbm", "achieved": bytes_G / st["geom"] / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": bytes_G / st["geom"] / 1e9 / HBM_PEAK_GBS, "bytes": bytes_G, "note": "host wall time of the whole stage incl. its small D2H syncs"},
+                    "C": {"bound": "hbm", "achieved": bytes_C / st["cdf"] / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": bytes_C / st["cdf"] / 1e9 / HBM_PEAK_GBS, "bytes": bytes_C, "note": "includes the 4 B/node D2H copy"}}
+                if other is not None:
+                    out["device_transform" if headline_strict else "strict_identity"] = other
+                    out["strict_identity_fps"] = out["value"] if headline_strict else other["fps"]
+                    out["device_transform_fps"] = other["fps"] if headline_strict else out["value"]
+                try:
+                    out["transform_parity"] = differing_points(enc, cfg, dev)
+                except Exception as e:
+                    out["transform_parity"] = {"error": str(e)}
+                tp = out["transform_parity"]
+                if headline_strict and tp is not None and "host_transform" in tp:
+                    # asserted in-run: the headline's integers ARE the reference's (tests/golden/frame_ints.npz, written by running the reference's proc_pc)
+                    out["strict_identity_verified"] = all(v == 0 for v in tp["host_transform"])
+                    if not out["strict_identity_verified"]:
+                        raise SystemExit(f"strict-identity headline, but the host transform's integers differ from the reference's: {tp}")
+                elif headline_strict:
+                    out["strict_identity_verified"] = None      # no reference integers for this workload's frames in tests/golden/
+            if not ehem:
+                try:
+                    out["transform_parity"] = differing_points(enc, cfg, dev)     # OctAttention legs run the device transform: how many points it misses
+                except Exception as e:
+                    out["transform_parity"] = {"error": str(e)}
+            mode = "none" if args.no_cpu_baseline else args.cpu_baseline
+            if world == 1 and mode != "none":
+                try:
+                    out["cpu_baseline"] = cpu_baseline(cfg, frames_host[-1], full=mode == "full", config=args.config)
+                except Exception as e:   # the baseline is a reported number, never a reason to lose the bench line
+                    out["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
+            if world == 1 and not args.no_legs and args.config == "ehem-L16-m":
+                try:
+                    side_legs(args, out)
+                except Exception as e:     # a leg is extra information, never a reason to lose the headline
+                    out["legs_error"] = repr(e)
         print(json.dumps(out), flush=True)
     if dist_on:
         dist.destroy_process_group()

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,7 @@ def test_bench_gpus_2_launches_two_ranks_itself():
     """`python bench.py --gpus 2` (no torchrun around it) starts two ranks as a child launcher before touching the GPU; here both
     ranks share the box's one GPU (SCP_FORCE_DEVICE=0) and reduce over gloo.  The line says n_gpus 2, the whole-job rate counts both
     ranks' frames, and the frame every rank encodes with the shared seed gives byte-identical streams."""
-    out = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--config", "ehem-L12-s"],
+    out = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline", "--config", "ehem-L12-s"],
                {"SCP_FORCE_DEVICE": "0", "SCP_DIST_BACKEND": "gloo"})
     assert out["n_gpus"] == 2 and out["rccl_world"] == 2 and out["scaling"] == "weak"
     assert out["steps"] == 4 and abs(out["value"] - 2 * 4 / (out["ms_per_step"] * 4e-3)) < 1e-6 * out["value"]
@@ -39,7 +40,7 @@ def test_bench_gpus_2_launches_two_ranks_itself():
 
 
 def test_bench_single_rank_line_has_the_contract_fields():
-    out = _run(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--config", "ehem-L12-s"])
+    out = _run(["--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--config", "ehem-L12-s"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline"):
         assert k in out
@@ -70,17 +71,37 @@ def test_bench_single_rank_line_has_the_contract_fields():
     assert "configs" not in out                                                 # side legs belong to the headline configuration only
 
 
+def test_bench_plain_run_is_the_headline_only_and_dumps_the_last_frame(tmp_path):
+    """Without --full the run times --steps frames and prints the headline fields only; --dump-outputs writes the last timed frame's result
+    (float64), identical for two runs with the same arguments."""
+    args = ["--steps", "3", "--warmup", "1", "--config", "ehem-L12-s"]
+    a = _run(args + ["--dump-outputs", str(tmp_path / "a")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "bpp_mean", "config"):
+        assert k in a
+    assert a["steps"] == 3 and a["warmup"] == 1 and abs(a["value"] - 1e3 / a["ms_per_step"]) < 1e-9 * a["value"]
+    assert not {"roofline", "roofline_kernels", "stage_ms", "device_transform", "transform_parity", "cpu_baseline", "configs"} & set(a)
+    b = _run(args + ["--dump-outputs", str(tmp_path / "b")])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and {"stream.npy", "bits.npy", "bpp.npy", "n_nodes.npy"} <= set(names)
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float64 and np.array_equal(x, y), n
+    stream = np.load(tmp_path / "a" / "stream.npy")
+    assert stream.size > 0 and 8 * stream.size == np.load(tmp_path / "a" / "bits.npy") and stream.max() <= 255
+    assert np.load(tmp_path / "a" / "n_nodes.npy") == a["config"]["nodes_per_frame"]
+
+
 def test_bench_device_transform_headline_and_strict_leg():
-    out = _run(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--config", "ehem-L12-s", "--device-transform"])
+    out = _run(["--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--config", "ehem-L12-s", "--device-transform"])
     assert out["config"]["transform"] == "device" and out["strict_identity"]["fps"] == out["strict_identity_fps"] and out["device_transform_fps"] == out["value"]
     tp = out["transform_parity"]
     assert tp["host_transform"] == [0] and tp["device_transform"][0] > 0       # L12 --spher: the device transform misses 853 of the reference's points
 
 
 def test_bench_side_legs_fill_configs_decode_and_cli():
-    """The default run of the headline configuration adds the other four BASELINE.json workloads, the decoder and the drop-in CLI as child
+    """The `--full` run of the headline configuration adds the other four BASELINE.json workloads, the decoder and the drop-in CLI as child
     processes behind the headline: five `configs` entries, `decode`, `cli`, `cli_over_bench`."""
-    out = _run(["--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-strict-leg", "--leg-steps", "2", "--leg-warmup", "1"], timeout=2400)
+    out = _run(["--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-strict-leg", "--leg-steps", "2", "--leg-warmup", "1"], timeout=2400)
     assert out["strict_identity_verified"] is True and out["transform_parity"]["host_transform"] == [0, 0, 0]
     assert set(out["configs"]) == {"ehem-L16-m", "ehem-L12-s", "ehem-F17-m", "octattn-L12-spher", "octattn-L14-cylin"}, out.get("legs_error")
     for name, c in out["configs"].items():

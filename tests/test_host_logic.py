@@ -251,9 +251,7 @@ def test_packed_chunks_respect_the_padded_row_limit():
     assert chunk_windows(ws[:5], 1_000_000) == [(0, 5)]
 
 
-def test_frame_flop_formula_matches_the_survey():
-    """bench.py prices a frame with SURVEY.md 8d's formulas: 310.2 GFLOP per full EHEM window (40.0 of them attention), 27.9 per
-    OctAttention window (11.3 attention)."""
+def _bench_module():
     import importlib.util
     import sys
     spec = importlib.util.spec_from_file_location("scp_bench", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
@@ -263,9 +261,35 @@ def test_frame_flop_formula_matches_the_survey():
         spec.loader.exec_module(b)
     finally:
         sys.argv = argv
+    return b
+
+
+def test_frame_flop_formula_matches_the_survey():
+    """bench.py prices a frame with SURVEY.md 8d's formulas: 310.2 GFLOP per full EHEM window (40.0 of them attention), 27.9 per
+    OctAttention window (11.3 attention)."""
+    b = _bench_module()
     assert abs(b.ehem_window_flops(8192) / 1e9 - 310.2) < 0.1 and abs(b.ehem_window_flops(8192, True) / 1e9 - 40.0) < 0.05
     assert abs(b.octattn_window_flops(1024) / 1e9 - 27.9) < 0.1 and abs(b.octattn_window_flops(1024, True) / 1e9 - 11.3) < 0.05
     assert b.ehem_window_flops(1) == b.ehem_window_flops(2) and b.ehem_window_flops(600) < b.ehem_window_flops(1024)
+
+
+def test_bench_dump_outputs_writes_every_result_field_as_float64(tmp_path):
+    """bench.py --dump-outputs: the fields of the result dict FrameEncoder.finish hands its caller, one float64 array each, the byte
+    stream as its byte values; the OctAttention result (no per-shell fields) writes the fields it has."""
+    b = _bench_module()
+    stream = bytes([0, 7, 255, 128, 3])
+    res = dict(bytes=stream, bits=40, bpp=40 / 3, n_nodes=9, n_points=3, n_levels=2, level_sizes=[1, 8], bin_num=2.5, z_offset=-1.0,
+               pos_mm=np.array([[1.0, 2.0], [3.0, 4.0]]), bin_nums=[2.5, 3.5], quant=[dict(qs=[1, 2, 3], offset=[4, 5, 6]), dict(qs=[7, 8, 9], offset=[0, 0, 1])],
+               times=dict(total=0.1))
+    b.dump_outputs(str(tmp_path / "ehem"), res)
+    got = {f[:-4]: np.load(tmp_path / "ehem" / f) for f in os.listdir(tmp_path / "ehem")}
+    assert set(got) == {"stream", "bits", "bpp", "n_nodes", "n_points", "n_levels", "level_sizes", "bin_num", "z_offset", "pos_mm", "bin_nums", "quant"}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["stream"].tolist() == list(stream) and got["bits"] == 40 and got["bpp"] == 40 / 3 and got["level_sizes"].tolist() == [1, 8]
+    assert got["quant"].shape == (2, 2, 3) and got["quant"][1, 0].tolist() == [7, 8, 9] and got["pos_mm"].shape == (2, 2)
+    oa = {k: v for k, v in res.items() if k not in ("bin_nums", "quant")}
+    b.dump_outputs(str(tmp_path / "oa"), oa)
+    assert sorted(os.listdir(tmp_path / "oa")) == sorted(f"{k}.npy" for k in got if k not in ("bin_nums", "quant"))
 
 
 @pytest.mark.parametrize("lengths", [[1], [1, 6, 20, 56, 208, 1372, 5605, 8192, 4938, 7, 2, 513], [8192, 8192], [3, 3, 3], [129, 257, 1025]])

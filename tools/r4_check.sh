@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:?run under gpurun (or export GRAFT_REPO_ROOT=the repository root)}; T=$1; O=$R/gpurun_out/$T; mkdir -p $O
 cd $R
 timeout 1200 python3 -m pytest tests -q -m gpu > $O/${T}_gpu_tests.txt 2>&1; tail -15 $O/${T}_gpu_tests.txt
-timeout 600 python3 bench.py > $O/${T}_bench.log 2>&1; grep '^{' $O/${T}_bench.log | tail -1 > $O/${T}_bench.json; cut -c1-400 $O/${T}_bench.json; tail -5 $O/${T}_bench.log | grep -v '^{' | cut -c1-300
+timeout 600 python3 bench.py --full > $O/${T}_bench.log 2>&1; grep '^{' $O/${T}_bench.log | tail -1 > $O/${T}_bench.json; cut -c1-400 $O/${T}_bench.json; tail -5 $O/${T}_bench.log | grep -v '^{' | cut -c1-300
 timeout 300 python3 bench.py --decode > $O/${T}_decode.log 2>&1; grep '^{' $O/${T}_decode.log | tail -1 > $O/${T}_bench_decode.json; cut -c1-600 $O/${T}_bench_decode.json
 bash tools/prof_frame.sh $T
 cp $R/gpurun_out/prof_$T/*/*_kernel_stats.csv $O/${T}_frame_kernel_stats.csv 2>/dev/null

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:?}" || exit 1
 T=${1:-r5chk}; O=gpurun_out/$T; mkdir -p $O
 python scp_amd/build.py > $O/build.log 2>&1 || { tail -20 $O/build.log; exit 1; }
 timeout 2400 python -m pytest tests -m gpu -x -q > $O/gpu_tests.txt 2>&1; echo "pytest rc=$?"; tail -4 $O/gpu_tests.txt
-t0=$(date +%s); timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$? wall $(( $(date +%s) - t0 )) s"; tail -2 $O/bench.err
+t0=$(date +%s); timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$? wall $(( $(date +%s) - t0 )) s"; tail -2 $O/bench.err
 python - <<PY
 import json
 try:

@@ -5,7 +5,7 @@ T=$1; K=$2; CFGS=$3; O=gpurun_out/$T; mkdir -p $O
 python scp_amd/build.py > $O/build.log 2>&1 || { tail -20 $O/build.log; exit 1; }
 if [ -n "$K" ]; then timeout 2400 python -m pytest tests -m gpu -q -k "$K" > $O/pytest.txt 2>&1; echo "pytest rc=$?"; grep -E "^(FAILED|ERROR)|passed|failed" $O/pytest.txt | tail -12 | cut -c1-250; fi
 for c in $CFGS; do
-  timeout 900 python bench.py --config $c --no-legs --cpu-baseline none > $O/bench_$c.json 2> $O/bench_$c.err
+  timeout 900 python bench.py --config $c --full --no-legs --cpu-baseline none > $O/bench_$c.json 2> $O/bench_$c.err
   python - <<PY
 import json
 try:

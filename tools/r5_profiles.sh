@@ -29,8 +29,8 @@ for w in $W; do
       done ;;
     bench)
       cd $R
-      timeout 1800 python3 bench.py > $O/${T}_bench.log 2>&1; grep '^{' $O/${T}_bench.log | tail -1 > $O/${T}_bench.json; cut -c1-200 $O/${T}_bench.json
-      timeout 1500 python3 bench.py --all-configs --no-cpu-baseline --out-dir $O --tag $T > $O/${T}_all_configs.log 2>&1; cut -c1-160 $O/${T}_all_configs.log
+      timeout 1800 python3 bench.py --full > $O/${T}_bench.log 2>&1; grep '^{' $O/${T}_bench.log | tail -1 > $O/${T}_bench.json; cut -c1-200 $O/${T}_bench.json
+      timeout 1500 python3 bench.py --all-configs --full --no-cpu-baseline --out-dir $O --tag $T > $O/${T}_all_configs.log 2>&1; cut -c1-160 $O/${T}_all_configs.log
       timeout 300 python3 bench.py --decode > $O/${T}_decode.log 2>&1; grep '^{' $O/${T}_decode.log | tail -1 > $O/${T}_bench_decode.json
       cd /tmp ;;
   esac

@@ -10,7 +10,7 @@ if [ "$K" = all ]; then
 elif [ "$K" != none ]; then
   timeout 2400 python -m pytest tests -m gpu -x -q -k "$K" > $O/gpu_tests.txt 2>&1; echo "pytest rc=$?"; tail -15 $O/gpu_tests.txt
 fi
-t0=$(date +%s); timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $O/bench.json 2> $O/bench.err; echo "bench rc=$? wall $(( $(date +%s) - t0 )) s"; tail -2 $O/bench.err
+t0=$(date +%s); timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --full "$@" > $O/bench.json 2> $O/bench.err; echo "bench rc=$? wall $(( $(date +%s) - t0 )) s"; tail -2 $O/bench.err
 python - <<PY
 import json
 try:

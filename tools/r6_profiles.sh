@@ -6,8 +6,8 @@ python scp_amd/build.py > /dev/null 2>&1
 bash tools/r5_profiles.sh r6 ehem octattn
 O=$GRAFT_REPO_ROOT/gpurun_out/r6
 cd $GRAFT_REPO_ROOT
-timeout 900 python3 bench.py --steps 6 --warmup 2 --no-legs --no-strict-leg --cpu-baseline full > $O/r6_bench_cpu_full.log 2>&1; grep '^{' $O/r6_bench_cpu_full.log | tail -1 > $O/r6_bench_cpu_full.json
-timeout 600 python3 bench.py --steps 6 --warmup 2 --no-legs --no-strict-leg > $O/r6_bench_cpu_sampled.log 2>&1; grep '^{' $O/r6_bench_cpu_sampled.log | tail -1 > $O/r6_bench_cpu_sampled.json
+timeout 900 python3 bench.py --steps 6 --warmup 2 --full --no-legs --no-strict-leg --cpu-baseline full > $O/r6_bench_cpu_full.log 2>&1; grep '^{' $O/r6_bench_cpu_full.log | tail -1 > $O/r6_bench_cpu_full.json
+timeout 600 python3 bench.py --steps 6 --warmup 2 --full --no-legs --no-strict-leg > $O/r6_bench_cpu_sampled.log 2>&1; grep '^{' $O/r6_bench_cpu_sampled.log | tail -1 > $O/r6_bench_cpu_sampled.json
 python3 - <<PY
 import json
 for n in ("full", "sampled"):
