@@ -43,7 +43,7 @@ extern "C" {
  *   220  GELU (round 5, numeric profile ehem/5): max(y, 0) - |y| exp(-beta y^2) / P4(|y|) instead of the degree-12 erf polynomial, in every
  *        kernel that applies it; scp_swin_post_attn expects fc1 scaled by scp_gelu_prescale() and fc2 by its inverse.
  *        (additive, no new version: scp_decode_expand, scp_linear_split_f16_max, scp_row_scale_from_max, scp_octattn_attention_f16x3_vmax;
- *        round 6: scp_linear_split_hier2, scp_mlp3_rows - existing entry points keep their bits, the EHEM model's numeric profile moved to ehem/6
+ *        round 6: scp_linear_split_hier2, scp_mlp3_rows; scp_octattn_attention_rowinv, scp_decode_expand_octattn - existing entry points keep their bits, the EHEM model's numeric profile moved to ehem/6
  *        because models/packed.py now calls the two new ones.) */
 #define SCP_ABI_VERSION 220
 SCP_API int scp_version(void);
@@ -359,6 +359,21 @@ SCP_API int scp_octattn_attention_f16x3(const float *q_u, const float *k, const 
 SCP_API int scp_octattn_attention_f16x3_vmax(const float *q_u, const float *k, const float *k_u, const float *v, const float *v_u,
                                              int64_t ldkv, int32_t B, int32_t c, int32_t H, int32_t hd, float *out, float *out_u, void *workspace,
                                              int64_t ws_bytes, const uint32_t *vmax_bits, void *stream);
+/* The decodable profile's attention (octattn/1d, csrc/octattn_rowinv.hip): the same mathematics in fp32 with every output row ONE fixed
+ * arithmetic sequence over rows 0..t of its own window (key tiles of 32 in ascending order from key 0, no launch-wide V scale), so a row's
+ * bits do not depend on the batch, on other windows or on the query range launched.  Rows [q0, q1) of B windows; k, v: the known
+ * stream's keys / values (window stride kw, row stride kr, floats; a decoder's per-layer cache); q_u, k_u, v_u, out, out_u: row r at
+ * index r - qoff (strides qw / qr, uw / ur, ow / orr).  out or out_u may be NULL (that stream is skipped; with out NULL row t of k, v
+ * is not read).  Head width hd <= 152. */
+SCP_API int scp_octattn_attention_rowinv(const float *q_u, int64_t qw, int64_t qr, const float *k, const float *v, int64_t kw, int64_t kr,
+                                         const float *k_u, const float *v_u, int64_t uw, int64_t ur, float *out, float *out_u, int64_t ow,
+                                         int64_t orr, int32_t B, int32_t q0, int32_t q1, int32_t qoff, int32_t H, int32_t hd, void *stream);
+/* The children of one decoded octree level in OctAttention's context layout (the decoder's sibling of scp_decode_expand):
+ * sym / cum as there; ctx uint8 [n][12] = (occ, level, octant) x (ggp, gp, p, self) of the parents (own occupancy not read), apos int32
+ * [n][4][3] the four rows' integer origins (0 for pad rows), L = the parents' level, shift = depth - L.  Child c of parent i: ctx =
+ * (ctx_i[3:9], (sym_i, ctx_i[10], ctx_i[11]), (255, L + 1, digit + 1)), apos = (apos_i[1:4], origin), pos = apos / 2^depth as float. */
+SCP_API int scp_decode_expand_octattn(const int64_t *sym, const int64_t *cum, const uint8_t *ctx, const int32_t *apos, int64_t n, int32_t L,
+                                      int32_t shift, int32_t depth, uint8_t *cctx, int32_t *capos, float *cpos, uint8_t *occ8, void *stream);
 /* OctAttention's input stage in one launch (oct_attention.py:48-66): embeddings of the four ancestors + Linear(3 -> d_pos) of their
  * positions, concatenated to D = 4 (d_occ + d_lvl + d_oct + d_pos) <= 768 channels, scaled by sqrt(D), plus the position table pe [c][D];
  * both streams (1 = "unknown": occ_enc[255] for the node's own occupancy).  ctx uint8 [n][12] = (occ, level, octant) x 4, pos fp32

@@ -72,6 +72,9 @@ def get_args(argv=None, mullevel=False):
     p.add_argument("--random_weights", type=int, default=None)
     p.add_argument("--out_dir", type=str, default=None)
     p.add_argument("--metrics", action="store_true", help="chamfer distance + D1 PSNR per frame (computed on the device)")
+    p.add_argument("--decodable", action="store_true",
+                   help="OctAttention only: code under the decodable numeric profile (octattn/1d) so that decode.py can rebuild the stream; "
+                        "EHEM streams are decodable already")
     p.add_argument("--host_transform", action="store_true",
                    help="strict identity with the reference from the frame on: the coordinate transform + quantiser run in numpy float32 on the "
                         "host exactly as data_preprocess.py:42-70 does (the device transform is more accurate, hence not bit-identical); "
@@ -122,6 +125,13 @@ def refuse_unsupported(args, name, mullevel):
         raise native.ScpError("--type obj is Cartesian and single-level in the reference (proc_pc defaults); drop --spher/--cylin/mullevel")
     if args.sequential and name != "OctAttention":
         raise native.ScpError("--sequential is an OctAttention mode (encode.py:38-41)")
+    decodable = getattr(args, "decodable", False)
+    if decodable and name != "OctAttention":
+        raise native.ScpError("--decodable is an OctAttention option: EHEM streams are decodable already")
+    if decodable and mullevel:
+        raise native.ScpError("--decodable: multi-level OctAttention streams (encode_mullevel.py) have no decoder; use encode.py")
+    if decodable and args.sequential:
+        raise native.ScpError("--decodable with --sequential: each node's window slides, so a decoder has no cache to keep")
 
 
 def spawn_ranks(n, argv0, argv):
@@ -203,7 +213,7 @@ def main(argv=None, mullevel=False):
         mul = mullevel and args.spher and not obj       # encode_dataset_mullevel.py:76: the three-shell form exists for --spher
         enc = OctAttnFrameEncoder(model, args.type, args.lidar_level, spher=args.spher and not obj, cylin=args.cylin and not obj, device=dev,
                                   mullevel=mul, level_wise=args.level_wise and mullevel, named=mullevel,
-                                  host_transform=True if args.host_transform else None)
+                                  host_transform=True if args.host_transform else None, decodable=args.decodable)
     else:
         enc = FrameEncoder(model, args.type, args.lidar_level, spher=args.spher, cylin=args.cylin, mullevel=mullevel, device=dev,
                            host_transform=True if args.host_transform else None)
@@ -234,6 +244,8 @@ def main(argv=None, mullevel=False):
         if name != "OctAttention":
             torch.save(torch.Tensor(res["pos_mm"].astype(np.float32)), outfile + ".dat")     # encode.py:150
             write_sidecar(outfile, enc, res, name)
+        elif args.decodable:
+            write_sidecar(outfile, enc, res, name)                                            # what decode.py reads besides the stream
         print("outputfile                  :", outfile)
         print("time(s)                     :", elapsed)
         print("pt num                      :", res["n_points"])
@@ -328,6 +340,83 @@ def get_decode_args(argv=None):
     return p.parse_args(argv)
 
 
+def get_decode_octattn_args(argv=None):
+    """decode.py's flags (the reference's decode.py:157-172) plus the repository's additions."""
+    p = argparse.ArgumentParser()
+    p.add_argument("--ckpt_path", type=str, default="", help="example: outputs/obj/2023-04-28/10-43-45/ckpt/epoch=7-step=64088.ckpt")
+    p.add_argument("--test_files", nargs="*", default=["data/obj/mpeg/8iVLSF_910bit/boxer_viewdep_vox9.ply"])
+    p.add_argument("--sequential_enc", action="store_true")
+    p.add_argument("--level_wise", action="store_true")
+    # additions
+    p.add_argument("--random_weights", type=int, default=None)
+    p.add_argument("--out_dir", type=str, default=None)
+    p.add_argument("--lidar_level", type=int, default=None, help="checked against the side-info file")
+    p.add_argument("--type", type=str, default=None, choices=[None, "obj", "kitti", "ford"])
+    p.add_argument("--preproc_path", type=str, default="")
+    return p.parse_args(argv)
+
+
+def decode_octattn_main(argv=None):
+    """Drop-in for the reference's decode.py (decodeOct): for every original file, its `<stem>.bin` (`find_stream`) written by
+    `encode.py --decodable` is decoded (scp_amd/decoder.py: OctAttnFrameDecoder), checked against the record file `<stem>.npy` when it
+    exists, and written as `<stem>.ply`.  The stream's side-info file carries the window length, level-wise flag, depth and profile;
+    streams of the default profile, --sequential and multi-level streams are refused with the reason."""
+    from .decoder import decode_octattn_file, read_sidecar
+    args = get_decode_octattn_args(argv)
+    if not torch.cuda.is_available():
+        raise native.ScpError("decode needs an MI355X: the SCP hot path has no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    native.lib()
+    from .models import OctAttention
+    cfg = load_cfg(args.ckpt_path, "OctAttention")
+    if cfg.model.class_name != "OctAttention":
+        raise native.ScpError("decode.py decodes OctAttention streams; EHEM streams: decode_ehem.py / decode_ehem_mullevel.py")
+    if args.random_weights is not None or not args.ckpt_path:
+        from .weights import fill_weights
+        model = fill_weights(OctAttention(cfg), args.random_weights or 0)
+    else:
+        model = OctAttention.load_from_checkpoint(args.ckpt_path, cfg=cfg)
+    model = model.to(dev).eval()
+    if args.out_dir:
+        out_root = args.out_dir.rstrip("/") + "/"
+    else:
+        root = args.ckpt_path.split("ckpt")[0] if args.ckpt_path else "./"
+        out_root = root + "test_output" + (args.ckpt_path.split("ckpt")[1][:-1] if args.ckpt_path else "") + "/"
+    files = expand_files(args.test_files)
+    elapsed, results = 0.0, []
+    for i, ori in enumerate(files):
+        print(f"{i}/{len(files)}")
+        name, stem = find_stream(out_root, ori)
+        binfile = out_root + name
+        side = read_sidecar(binfile)
+        if side is not None:     # the flags describe the stream; the side-info file is what it was coded with
+            if args.sequential_enc != bool(side.get("sequential", False)) or args.level_wise != bool(side.get("level_wise", False)):
+                print("note: --sequential_enc / --level_wise differ from the stream's side-info file; the side-info file wins")
+            if args.lidar_level is not None and args.lidar_level != side.get("lidar_level"):
+                raise native.ScpError(f"{binfile}: coded at lidar level {side.get('lidar_level')}, --lidar_level {args.lidar_level} given")
+            if args.type is not None and args.type != side.get("type"):
+                raise native.ScpError(f"{binfile}: coded as --type {side.get('type')}, --type {args.type} given")
+        t0 = time.time()
+        out = decode_octattn_file(binfile, model, dev)
+        torch.cuda.synchronize()
+        t = time.time() - t0
+        elapsed += t
+        npy = (args.preproc_path.rstrip("/") + "/" + Path(ori).stem) if args.preproc_path else str(ori).rsplit(".")[0]
+        if os.path.exists(npy + ".npy"):                       # the reference asserts every node against it (decode.py:99)
+            want = np.load(npy + ".npy")[:, -1, 0]
+            got = out["codes"][0].cpu().numpy().astype(np.int64)
+            assert np.array_equal(got[:len(want)], want) and len(got) == len(want), f"decoded occupancy differs from {npy}.npy"
+            print("checked against", npy + ".npy")
+        print("decode succee,time:", t)
+        print("oct len:", int(out["codes"][0].numel()))
+        ply = out_root + stem + ".ply"
+        pointCloud.write_ply_data(ply, out["points"].cpu().numpy())
+        print(ply)
+        results.append((ply, out))
+    print(elapsed / max(len(files), 1))
+    return results
+
+
 def find_stream(out_root, ori):
     """The stream the encode CLIs wrote for the original file `ori`: `<stem>[_spher|_cylin]_<levels>_<bin_num>_<z_offset>.bin` with
     stem = `<sequence dir><frame>` for KITTI EHEM runs (encode.py:140-144 via the dataset's file name) or the plain file stem.  The
@@ -363,7 +452,7 @@ def decode_main(argv=None, mullevel=False):
     from .models import EHEM
     cfg = load_cfg(args.ckpt_path, "EHEM")
     if cfg.model.class_name != "EHEM":
-        raise native.ScpError("decode_ehem*.py decode EHEM streams (the reference has no OctAttention decoder for these files)")
+        raise native.ScpError("decode_ehem*.py decode EHEM streams; OctAttention streams written with --decodable: decode.py")
     if args.random_weights is not None or not args.ckpt_path:
         from .weights import fill_weights
         model = fill_weights(EHEM(cfg), args.random_weights or 0)

@@ -262,3 +262,54 @@ extern "C" SCP_API int scp_decode_expand(const int64_t *sym, const int64_t *cum,
     LAUNCH_CHECK();
     return SCP_OK;
 }
+
+// Decoder, OctAttention layout (encode_dataset.py:32-55, ctx_octattn_kernel of csrc/geom.hip): the children of one decoded level with
+// their context rows (occ, level, octant) x (ggp, gp, p, self) and the four rows' positions, in ONE launch.  The parent's row moves up by
+// one slot with its own occupancy filled in; pad rows (255, 0, 0) at origin 0 move up unchanged.  pos = origin / 2^depth in double,
+// rounded to float once: the encoder's values bit for bit.
+__global__ __launch_bounds__(256) void decode_expand_octattn_kernel(const int64_t *__restrict__ sym, const int64_t *__restrict__ cum,
+                                                                    const uint8_t *__restrict__ ctx, const int32_t *__restrict__ apos, int64_t n, int L,
+                                                                    int shift, double scale, uint8_t *__restrict__ cctx, int32_t *__restrict__ capos,
+                                                                    float *__restrict__ cpos, uint8_t *__restrict__ occ8) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t s = sym[i];
+    const unsigned occ = (unsigned)((s + 1) & 0xff);
+    occ8[i] = (uint8_t)occ;
+    if (!occ) return;
+    int64_t c = cum[i] - __popc(occ);
+    uint8_t cx[9];
+    int32_t ap[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) { cx[j] = ctx[12 * i + 3 + j]; ap[j] = apos[12 * i + 3 + j]; }
+    cx[6] = (uint8_t)s;
+    const int px = ap[6], py = ap[7], pz = ap[8];
+    for (int d = 0; d < 8; ++d) {
+        if (!((occ >> d) & 1)) continue;
+        const int o[3] = {px + (((d >> 2) & 1) << shift), py + (((d >> 1) & 1) << shift), pz + ((d & 1) << shift)};
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            cctx[12 * c + j] = cx[j];
+            capos[12 * c + j] = ap[j];
+            cpos[12 * c + j] = (float)((double)ap[j] / scale);
+        }
+        cctx[12 * c + 9] = 255; cctx[12 * c + 10] = (uint8_t)(L + 1); cctx[12 * c + 11] = (uint8_t)(d + 1);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            capos[12 * c + 9 + j] = o[j];
+            cpos[12 * c + 9 + j] = (float)((double)o[j] / scale);
+        }
+        ++c;
+    }
+}
+
+extern "C" SCP_API int scp_decode_expand_octattn(const int64_t *sym, const int64_t *cum, const uint8_t *ctx, const int32_t *apos, int64_t n, int32_t L,
+                                                 int32_t shift, int32_t depth, uint8_t *cctx, int32_t *capos, float *cpos, uint8_t *occ8, void *stream) {
+    if (!sym || !cum || !ctx || !apos || !cctx || !capos || !cpos || !occ8 || n <= 0 || L < 1 || L > 254 || shift < 0 || shift > 30 || depth < 1 ||
+        depth > 30 || shift >= depth)
+        return SCP_EINVAL;
+    hipLaunchKernelGGL(decode_expand_octattn_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, sym, cum, ctx, apos, n, (int)L,
+                       (int)shift, (double)(1ll << depth), cctx, capos, cpos, occ8);
+    LAUNCH_CHECK();
+    return SCP_OK;
+}

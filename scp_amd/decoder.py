@@ -44,7 +44,13 @@ def write_sidecar(outfile, enc, res, model_name):
     side = dict(model=model_name, type=enc.data_type, lidar_level=int(enc.lidar_level), mullevel=bool(enc.mullevel),
                 spher=bool(enc.spher), cylin=bool(enc.cylin), n_points=int(res["n_points"]), n_nodes=int(res["n_nodes"]),
                 bin_nums=[float(b) for b in res.get("bin_nums", [res["bin_num"]])],
-                z_offset=float(res["z_offset"]), quant=res.get("quant"), profile=native.numeric_profile(model_name, getattr(enc, "profile", None)))
+                z_offset=float(res["z_offset"]), quant=res.get("quant"),
+                profile=native.numeric_profile(model_name, getattr(enc, "profile", None), decodable=getattr(enc, "decodable", False)))
+    if model_name == "OctAttention":
+        # additive fields (OctAttnFrameDecoder): the window length, whether every level is its own chunk, the one-window-per-node mode,
+        # and the octree depth the positions are normalised by
+        side.update(context_size=int(enc.context_size), level_wise=bool(enc.level_wise), sequential=bool(res.get("sequential", False)),
+                    depth=int(res["depth"]) if "depth" in res else None)
     with open(outfile + SIDECAR, "w") as f:
         json.dump(side, f)
     return side
@@ -75,6 +81,146 @@ def dequantise_leaves(leaves, qs, bin_num, z_offset, spher, cylin, data_type=KIT
         o = -200.0 if data_type == KITTI else -float(2 ** 17)
         q, off = [qs, qs, qs], [o, o, o]
     return metrics.dequantize(leaves, q, off, spher=spher, cylin=cylin)
+
+
+def octattn_window_of(r, cs):
+    """OctAttention's window rule (encoder._chunk_rows): node r of a chunk (front-padded with cs - 1 rows) is predicted at position
+    (r + cs - 1) % cs of window (r + cs - 1) // cs.  -> (window, position)."""
+    return divmod(r + cs - 1, cs)
+
+
+def octattn_chunks(level_sizes, level_wise):
+    """The chunk lengths of a frame: one chunk of every node, or (level_wise) one per octree level."""
+    return [int(n) for n in level_sizes] if level_wise else [int(sum(level_sizes))]
+
+
+def _refuse_octattn(binfile, side):
+    """The OctAttention streams OctAttnFrameDecoder cannot decode, refused with the reason."""
+    if side is None or "profile" not in side:
+        raise native.ScpError(f"{binfile}: no side-info file ({SIDECAR}): the default OctAttention profile cannot be decoded bit for bit (its "
+                              "attention scales V by a maximum over the whole launch) - re-encode with --decodable")
+    if side.get("model") != "OctAttention":
+        raise native.ScpError(f"{binfile}: an {side.get('model')} stream, not OctAttention")
+    if not str(side["profile"]).startswith("octattn/1d:"):
+        raise native.ScpError(f"{binfile}: coded under the default OctAttention profile {side['profile']!r}, which cannot be decoded bit for bit "
+                              "(its attention scales V by a maximum over the whole launch) - re-encode with --decodable")
+    if side.get("mullevel"):
+        raise native.ScpError(f"{binfile}: multi-level OctAttention streams (three shells) are not decodable")
+    if side.get("sequential"):
+        raise native.ScpError(f"{binfile}: a --sequential stream: each node's window slides, so the decoder has no cache to keep")
+    want = native.numeric_profile("OctAttention", None, decodable=True)
+    if side["profile"] != want:
+        raise native.ScpError(f"{binfile}: coded under numeric profile {side['profile']!r}, this process runs {want!r}: the integer CDFs would "
+                              "differ and the range decoder would desynchronise")
+    for k in ("context_size", "level_wise", "depth", "n_nodes"):
+        if side.get(k) is None:
+            raise native.ScpError(f"{binfile}: side-info file without `{k}`")
+
+
+def decode_octattn_file(binfile, model, device=None):
+    """An OctAttention stream written with `--decodable` -> dict(codes [n_nodes] uint8 occupancy in BFS order, leaves int64 [U, 3],
+    points [U, 3] float64 Cartesian).  Everything the decoder needs beyond the stream comes from the `.scp.json` side-info file."""
+    side = read_sidecar(binfile)
+    _refuse_octattn(binfile, side)
+    if side["context_size"] != model.cfg.model.context_size:
+        raise native.ScpError(f"{binfile}: coded with context size {side['context_size']}, the model has {model.cfg.model.context_size}")
+    with open(binfile, "rb") as f:
+        stream = f.read()
+    dec = OctAttnFrameDecoder(model, side["depth"], level_wise=side["level_wise"], device=device)
+    codes, leaves = dec.decode(stream, side["n_nodes"])
+    spher, cylin = side["spher"], side["cylin"]
+    data_type, quant = side["type"], side.get("quant")
+    if data_type == "obj" and quant:
+        # the steps and offset the integers were made with: encode.py's --type obj rule (qs 1, the frame's per-axis minimum), or the
+        # encoder's own quantiser
+        from . import metrics
+        pts = metrics.dequantize(leaves, quant[0]["qs"], quant[0]["offset"], spher=spher, cylin=cylin)
+    else:
+        # KITTI / Ford: the reference decoder's rule with the side-info's (un-truncated) z offset; obj without `quant`: the
+        # encoder's fixed rule (qs 2^(18 - L), offset -2^17: OctAttnFrameEncoder.cart_offset)
+        qs = shell_qs(data_type, side["lidar_level"], False)[0]
+        pts = dequantise_leaves(leaves, qs, side["bin_nums"][0], side["z_offset"], spher, cylin, data_type)
+    return dict(codes=[codes], leaves=[leaves], points=pts, spher=spher, cylin=cylin, stats=dec.stats)
+
+
+class OctAttnFrameDecoder:
+    """The inverse of OctAttnFrameEncoder(decodable=True).  The octree is regenerated breadth first; a level's children, their context
+    rows (occ, level, octant) x (ggp, gp, p, self) and positions come from one launch (native.decode_expand_octattn) once the level is
+    decoded.  Node by node (the window rule of `octattn_window_of`; with `level_wise` every level is its own chunk): the unknown pass of
+    OctAttnStepper gives the logits row, the encoder's CDF kernel its integer CDF, one pinned copy brings it to the host range decoder,
+    and the known pass with the decoded symbol extends the window's cache."""
+
+    def __init__(self, model, depth, level_wise=False, device=None):
+        self.model = model
+        self.depth = int(depth)
+        self.level_wise = bool(level_wise)
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.context_size = model.cfg.model.context_size
+        self.stats = None             # set to {} to collect wall seconds per stage (a device synchronisation per stamp)
+        self._pin = torch.empty(256, dtype=torch.int16, pin_memory=True)
+
+    def _stamp(self, key, t0):
+        if self.stats is None:
+            return t0
+        import time
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        self.stats[key] = self.stats.get(key, 0.0) + (t - t0)
+        return t
+
+    def decode(self, stream, n_nodes):
+        """-> (occupancy codes uint8 [n_nodes] in BFS order, leaf integer coordinates int64 [U, 3])."""
+        from . import ops
+        from .models.oct_attention import OctAttnStepper
+        import time
+        dev, cs = self.device, self.context_size
+        dec = native.AcDecoder(stream)
+        prev = self.model.decodable
+        self.model.decodable = True
+        try:
+            with ops.frozen_weights():
+                st = OctAttnStepper(self.model)
+                ctx = torch.tensor([[255, 0, 0] * 3 + [255, 1, 1]], dtype=torch.uint8, device=dev)     # the root: level 1, octant 1
+                apos = torch.zeros((1, 4, 3), dtype=torch.int32, device=dev)
+                pos = torch.zeros((1, 4, 3), dtype=torch.float32, device=dev)
+                codes, done, r = [], 0, 0
+                stream_ = torch.cuda.current_stream(dev)
+                for L in range(1, self.depth + 1):
+                    n = ctx.shape[0]
+                    if done + n > n_nodes:
+                        raise native.ScpError(f"the octree has more than the side-info's {n_nodes} nodes: stream and side-info disagree")
+                    if L == 1 or self.level_wise:
+                        r = 0
+                    syms = np.empty(n, np.int64)
+                    t = time.perf_counter() if self.stats is not None else 0.0
+                    if self.stats is not None:
+                        torch.cuda.synchronize()
+                    for i in range(n):
+                        w, p = octattn_window_of(r, cs)
+                        if r == 0 or p == 0:
+                            st.reset(pad=(w == 0))
+                        crow, prow = ctx[i:i + 1], pos[i:i + 1]
+                        logits = st.unknown(crow, prow)
+                        t = self._stamp("model_step", t)
+                        self._pin.copy_(native.softmax_cdf(logits, want_lohi=False, want_cdf=True)["cdf"][0], non_blocking=True)
+                        stream_.synchronize()
+                        t = self._stamp("cdf_d2h", t)
+                        s = dec.next(self._pin.numpy())
+                        t = self._stamp("range_decoder", t)
+                        syms[i] = s
+                        crow[0, 9] = s
+                        st.known(crow, prow)
+                        t = self._stamp("model_step", t)
+                        r += 1
+                    done += n
+                    occ8, ctx, apos, pos = native.decode_expand_octattn(torch.from_numpy(syms).to(dev), ctx, apos, L, self.depth)
+                    t = self._stamp("expansion", t)
+                    codes.append(occ8)
+                if done != n_nodes:
+                    raise native.ScpError(f"decoded {done} nodes, the side-info says {n_nodes}")
+        finally:
+            self.model.decodable = prev
+        return torch.cat(codes), apos[:, 3].long()
 
 
 def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False, device=None, profile=None):

@@ -593,8 +593,13 @@ class OctAttnFrameEncoder:
     (`probabilities[:-1023]`) and coded as one stream.  File name `<base>[_spher]_<chunks>_<bin_num>_0.bin`."""
 
     def __init__(self, model, data_type=KITTI, lidar_level=12, spher=True, cylin=False, max_batch=128, device=None, mullevel=False,
-                 level_wise=False, named=False, host_transform=None):
+                 level_wise=False, named=False, host_transform=None, decodable=False):
         self.model = model
+        # decodable=True: the octattn/1d numeric profile (models/oct_attention.py) - every PMF row a function of its own window's rows
+        # 0..t, so OctAttnFrameDecoder can reproduce it node by node; the default (octattn/1) keeps the round-6 bits
+        self.decodable = bool(decodable)
+        if self.decodable and mullevel:
+            raise native.ScpError("--decodable: multi-level OctAttention streams (three shells) have no decoder; encode with encode.py")
         self.host_transform = (os.environ.get("SCP_XFORM", "") == "numpy") if host_transform is None else bool(host_transform)   # see FrameEncoder
         self.data_type = data_type
         self.lidar_level = lidar_level
@@ -611,6 +616,7 @@ class OctAttnFrameEncoder:
         self.context_size = model.cfg.model.context_size
         self.geom = native.Geom()
         self.cart_offset = -200.0 if data_type == KITTI else -float(2 ** 17)
+        self._infos = []                      # the last quantiser call's per-shell info (quant_info)
 
     def shells(self):
         L = self.lidar_level
@@ -621,13 +627,23 @@ class OctAttnFrameEncoder:
             from .data_preproc.data_preprocess import host_quantize_shells
             xyz = np.ascontiguousarray(xyz_dev.cpu().numpy(), np.float32)
             out = host_quantize_shells(xyz, self.mode, [level_qs(self.data_type, lv) for _, lv in self.shells()], 0.0 if self.mullevel else self.cart_offset)
+            self._infos = [i for _, i in out]
             return [torch.from_numpy(q).to(self.device) for q, _ in out], out[0][1].bin_num
-        qs, bin_num = [], None
+        qs, infos = [], []
         for path, lv in self.shells():
             q, qi, _ = native.quantize(xyz_dev, self.mode, level_qs(self.data_type, lv), 0.0 if self.mullevel else self.cart_offset)
             qs.append(q)
-            bin_num = qi.bin_num if bin_num is None else bin_num
-        return qs, bin_num
+            infos.append(qi)
+        self._infos = infos
+        return qs, infos[0].bin_num
+
+    def quant_info(self):
+        """Per shell the (qs[3], offset[3]) the last `quantize` / `build_from_xyz` made its integers with - the cylindrical z offset
+        (the frame's z minimum) included: what a decoder needs to de-quantise (encode_ints(..., quant=))."""
+        return _quant_of(self._infos)
+
+    def profile_string(self):
+        return native.numeric_profile("OctAttention", None, decodable=self.decodable)
 
     def encode(self, xyz, timing=False, sequential=False):
         t0 = time.perf_counter()
@@ -636,9 +652,9 @@ class OctAttnFrameEncoder:
         xyz_dev = xyz.to(self.device)
         if not self.host_transform:
             bin_num = self.build_from_xyz(xyz_dev)
-            return self.encode_ints(None, bin_num, xyz_dev.shape[0], t0, sequential=sequential, front=self._front(None))
+            return self.encode_ints(None, bin_num, xyz_dev.shape[0], t0, sequential=sequential, front=self._front(None), quant=self.quant_info())
         qs, bin_num = self.quantize(xyz_dev)
-        return self.encode_ints(qs, bin_num, xyz_dev.shape[0], t0, sequential=sequential)
+        return self.encode_ints(qs, bin_num, xyz_dev.shape[0], t0, sequential=sequential, quant=self.quant_info())
 
     def _sequential_rows(self, seq_ctx, seq_pos, N, table):
         """`--sequential` (encode.py:38-41,55-56): a window starts at EVERY row of the padded sequence and only the prediction
@@ -660,6 +676,7 @@ class OctAttnFrameEncoder:
         """Device transform: stage G1 + G2 in one launch sequence (scp_geom_build_xyz) -> bin_num of the first shell."""
         infos = self.geom.build_xyz([xyz_dev], self.mode, [level_qs(self.data_type, lv) for _, lv in self.shells()],
                                     0.0 if self.mullevel else self.cart_offset, [(path, self.mullevel) for path, _ in self.shells()])
+        self._infos = infos
         return infos[0].bin_num
 
     def _front(self, qs):
@@ -703,7 +720,8 @@ class OctAttnFrameEncoder:
         """Default mode: consecutive windows of context_size over every padded chunk; all windows of the frame (whatever chunk they belong to)
         share batched forwards.  Round 6: a chunk's shorter TAIL window rides in the same forwards, padded behind its last row to a full window
         - the model is causal (attention_model.py:58-95: row i attends to rows <= i; everything else is per row), so the rows in front of the
-        padding come out as in a forward of the short window alone, and the frame saves that forward's ~45 launches on one window (1 ms of a
+        padding come out as in a forward of the short window alone (bit for bit under the decodable profile; under the default one the
+        attention's launch-wide V scale makes them agree to rounding only), and the frame saves that forward's ~45 launches on one window (1 ms of a
         15 ms L12 frame)."""
         cs = self.context_size
         full_c, full_p, dst = [], [], []       # windows + (table row of the window's first real node, leading pad rows, real rows in the window)
@@ -751,25 +769,35 @@ class OctAttnFrameEncoder:
                 table[r0:r0 + rows] = out[i * cs + skip:i * cs + skip + rows]
                 i = j
 
-    def encode_ints(self, q, bin_num, n_points, t0=None, sequential=False, defer=False, front=None):
-        """q: integer cloud (numpy / tensor int32 [P,3]) or the list of per-shell clouds of the multi-level form."""
+    def encode_ints(self, q, bin_num, n_points, t0=None, sequential=False, defer=False, front=None, quant=None):
+        """q: integer cloud (numpy / tensor int32 [P,3]) or the list of per-shell clouds of the multi-level form.  quant: per shell
+        dict(qs, offset) the integers were made with (`quant_info()`), kept in the result - `z_offset` is its cylindrical z offset - for
+        the side-info file; None: unknown (z offset 0)."""
         t0 = t0 or time.perf_counter()
         if front is None:
             qs = q if isinstance(q, (list, tuple)) else [q]
             qs = [(torch.from_numpy(np.ascontiguousarray(x, np.int32)) if isinstance(x, np.ndarray) else x).to(self.device) for x in qs]
             front = self._front(qs)
         chunks, sym, N = front
+        if sequential and self.decodable:
+            raise native.ScpError("--decodable with --sequential: each node's window slides, so a decoder has no cache to keep")
         table = torch.empty((N, 255), dtype=torch.float32, device=self.device)
-        if sequential:
-            row = 0
-            for seq_ctx, seq_pos, n in chunks:
-                self._sequential_rows(seq_ctx, seq_pos, n, table[row:row + n])
-                row += n
-        else:
-            self._chunk_rows(chunks, table)
+        prev = self.model.decodable
+        self.model.decodable = self.decodable
+        try:
+            if sequential:
+                row = 0
+                for seq_ctx, seq_pos, n in chunks:
+                    self._sequential_rows(seq_ctx, seq_pos, n, table[row:row + n])
+                    row += n
+            else:
+                self._chunk_rows(chunks, table)
+        finally:
+            self.model.decodable = prev
         lohi = native.softmax_cdf(table, sym)["lohi"]
-        meta = dict(n_nodes=N, n_points=n_points, bin_num=bin_num, z_offset=0.0, n_levels=len(chunks), pos_mm=np.zeros((0, 2)),
-                    level_sizes=[c[2] for c in chunks])
+        z_off = float(quant[0]["offset"][2]) if (quant and self.cylin) else 0.0
+        meta = dict(n_nodes=N, n_points=n_points, bin_num=bin_num, z_offset=z_off, quant=quant, n_levels=len(chunks), pos_mm=np.zeros((0, 2)),
+                    level_sizes=[c[2] for c in chunks], depth=int(self.geom.info[0].depth), sequential=bool(sequential))
         if defer:
             return lohi, meta, (table, sym, chunks)
         stream = native.ac_encode_lohi(lohi.cpu().numpy())
@@ -814,7 +842,7 @@ class OctAttnFrameEncoder:
             ready.record()
         main.wait_event(ready)
         with torch.cuda.stream(main):
-            lohi, meta, keep = self.encode_ints(q, bin_num, xyz_dev.shape[0], t0, defer=True, front=front)
+            lohi, meta, keep = self.encode_ints(q, bin_num, xyz_dev.shape[0], t0, defer=True, front=front, quant=self.quant_info())
             done = torch.cuda.Event()
             done.record()
             if native.CACHE_FILLS != fills0:

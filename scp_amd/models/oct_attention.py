@@ -77,7 +77,7 @@ class _Transformer(nn.Module):
 
 
 class OctAttention(nn.Module):
-    def __init__(self, cfg):
+    def __init__(self, cfg, decodable=False):
         super().__init__()
         self.cfg = cfg
         m = cfg.model
@@ -94,6 +94,10 @@ class OctAttention(nn.Module):
         self.decoder1 = nn.Linear(self.embed_dimension, m.token_num)
         mask = (torch.triu(torch.ones(m.context_size, m.context_size)) == 1).transpose(0, 1)
         self.register_buffer("mask", mask.float().masked_fill(mask == 0, float("-inf")).masked_fill(mask == 1, 0.0))
+        # the numeric profile (native.numeric_profile): False = octattn/1 (the f16x3 attention with a launch-wide V scale, the default
+        # encoder's bits); True = octattn/1d, the decodable profile: each logits row depends on its own window's rows 0..t only
+        # (csrc/octattn_rowinv.hip), so OctAttnFrameDecoder can rebuild it one node at a time (OctAttnStepper)
+        self.decodable = bool(decodable)
         self.eval()
 
     @classmethod
@@ -126,8 +130,20 @@ class OctAttention(nn.Module):
         E = torch.stack((torch.cat(parts, 3).reshape(B, c, D), torch.cat(parts_u, 3).reshape(B, c, D))) * math.sqrt(D)
         return E + self.transformer_encoder.position_enc.pe[:c]
 
+    def profile_string(self):
+        return native.numeric_profile("OctAttention", None, decodable=self.decodable)
+
+    def _check_decodable(self, c=None):
+        D = self.embed_dimension
+        if not PLANES or D > _KV_OFF or D % 4 or D // self.heads > 152 or not self.abs_pos_embed_dim or \
+                (c is not None and c > self.transformer_encoder.position_enc.pe.shape[0]):
+            raise native.ScpError("the decodable OctAttention profile needs the planes path, embedding width <= 640 (a multiple of 4), head "
+                                  "width <= 152, the position embedding and windows within the position table")
+
     @torch.no_grad()
-    def forward(self, data, pos=None):
+    def forward(self, data, pos=None, capture_kv=None):
+        """capture_kv (decodable profile only): a list that receives every layer's known-stream key | value projection [B, c, 1280]
+        (key in columns [0, D), value in [640, 640 + D)) - the rows a decoder's cache holds (OctAttnStepper.prefill)."""
         if not data.is_cuda:
             raise native.ScpError("OctAttention runs on the MI355X only (no CPU fallback)")
         B, c = data.shape[:2]
@@ -137,6 +153,13 @@ class OctAttention(nn.Module):
         n = B * c
         pa = None                                      # planes of E, when the kernel that produced E wrote them
         pe_tab = self.transformer_encoder.position_enc.pe
+        dec = self.decodable
+        if dec:
+            self._check_decodable(c)
+            if pos is None:
+                raise native.ScpError("the decodable OctAttention profile needs positions")
+        elif capture_kv is not None:
+            raise native.ScpError("capture_kv: decodable profile only")
         if planes and D <= 768 and D % 4 == 0 and pos is not None and c <= pe_tab.shape[0]:
             # the whole input stage in ONE kernel (csrc/octattn_embed.hip): three embedding lookups x four ancestors, the position
             # Linear, concatenation, sqrt(D) scale, position table - both streams - and the f16x3 operand of the first dense layers
@@ -176,7 +199,13 @@ class OctAttention(nn.Module):
                 # known stream for the attention kernel's V planes, the row maxima of linear1's output for linear2 - no pass over either tensor
                 mxw = torch.zeros(2 * n + 1, dtype=torch.int32, device=E.device)
                 vmax, h1max = mxw[2 * n:], mxw[:2 * n]
-                kv = native.linear_split_f16(pa, _ops._split16(wkv), bkv, cfg=1, col_max=(vmax, _KV_OFF, _KV_OFF + D, n)).reshape(2, B, c, wkv.shape[0])
+                if dec:                                # no V scale at all: the row-invariant attention reads v in fp32
+                    vmax = None
+                    kv = native.linear_split_f16(pa, _ops._split16(wkv), bkv, cfg=1).reshape(2, B, c, wkv.shape[0])
+                    if capture_kv is not None:
+                        capture_kv.append(kv[0])
+                else:
+                    kv = native.linear_split_f16(pa, _ops._split16(wkv), bkv, cfg=1, col_max=(vmax, _KV_OFF, _KV_OFF + D, n)).reshape(2, B, c, wkv.shape[0])
                 key, val = kv[..., :D], kv[..., _KV_OFF:_KV_OFF + D]
             else:
                 vmax = h1max = None
@@ -184,7 +213,10 @@ class OctAttention(nn.Module):
                 val = lin(pa, E, a.mlp_value.weight, a.mlp_value.bias, scales=rs).reshape(2, B, c, D)
             q_u = lin(pa, E[1], a.mlp_query.weight, a.mlp_query.bias, rows=(n, 2 * n), scales=rsq).reshape(B, c, D)
             att = torch.empty_like(E)
-            native.octattn_attention(q_u, key[0], key[1], val[0], val[1], self.heads, out=att[0], out_u=att[1], vmax=vmax)
+            if dec:
+                native.octattn_attention_rowinv(q_u, key[0], val[0], self.heads, k_u=key[1], v_u=val[1], out=att[0], out_u=att[1])
+            else:
+                native.octattn_attention(q_u, key[0], key[1], val[0], val[1], self.heads, out=att[0], out_u=att[1], vmax=vmax)
             # norm(x + residual) in one pass; with `planes` the same pass writes the f16x3 operand of the layer that reads the result
             E, p1 = native.layernorm_add(att, E, lyr.norm1.weight, lyr.norm1.bias, 1e-5, planes=True) if planes else \
                 (native.layernorm_add(att, E, lyr.norm1.weight, lyr.norm1.bias, 1e-5), None)
@@ -198,3 +230,114 @@ class OctAttention(nn.Module):
             d0 = native.linear_split_f16(pa.rows(n, 2 * n), _ops._split16(self.decoder0.weight), self.decoder0.bias, native.ACT_RELU)
             return linear(d0, self.decoder1.weight, self.decoder1.bias).reshape(B, c, -1)
         return linear(linear(emu, self.decoder0.weight, self.decoder0.bias, act="relu"), self.decoder1.weight, self.decoder1.bias)
+
+
+def _pad_rows(n, device):
+    """The front padding of a chunk (encoder._front): context rows (255, 0, 0) x 4, positions 0."""
+    ctx = torch.zeros((n, 12), dtype=torch.uint8, device=device)
+    ctx[:, 0::3] = 255
+    return ctx, torch.zeros((n, 4, 3), dtype=torch.float32, device=device)
+
+
+class OctAttnStepper:
+    """Incremental evaluation of ONE window under the decodable profile (the decoder's hot path): per layer a cache of the known stream's
+    key | value rows < t and the unknown stream's query of row t.  For the window's row t:
+      unknown(ctx, pos) -> logits [1, 255]: the unknown stream (own occupancy unknown) through the three layers and the two decoder layers;
+                           its attention reads the cached rows < t plus its own k_u, v_u;
+      known(ctx, pos)   -> the known stream of row t (own occupancy decoded) through the layers: its key | value rows go into the cache,
+                           its attention is q_u[t] (cached by `unknown`) against the cached rows <= t.  t advances by one.
+    Every launch is the batched forward's kernel on one row and each of them is row-invariant, so each logits row is bit-identical to the
+    same row of OctAttention.forward under the decodable profile (tests/test_gpu_octattn_decode.py)."""
+
+    def __init__(self, model):
+        model._check_decodable()
+        if not model.decodable:
+            raise native.ScpError("OctAttnStepper: the model runs the default (non-decodable) profile; set model.decodable = True")
+        self.m = model
+        p = next(model.parameters())
+        self.device = p.device
+        self.cs = model.cfg.model.context_size
+        self.D = model.embed_dimension
+        nl = len(model.transformer_encoder.layers)
+        self.kv = torch.zeros((nl, self.cs, 2 * _KV_OFF), dtype=torch.float32, device=self.device)
+        self.q = torch.zeros((nl, 1, self.D), dtype=torch.float32, device=self.device)
+        self.h1max = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self.t = 0
+
+    def reset(self, pad):
+        """Start a window: pad=True - the first window of a chunk, whose rows 0 .. cs - 2 are the front padding (their cache rows are the
+        same for every chunk: computed once per model by a batched forward, then copied); pad=False - an empty window."""
+        if pad and self.cs > 1:
+            kv_pad = self.prefill_pad()
+            self.kv[:, :self.cs - 1].copy_(kv_pad)
+            self.t = self.cs - 1
+        else:
+            self.t = 0
+
+    def prefill_pad(self):
+        m = self.m
+
+        def build():
+            ctx, pos = _pad_rows(self.cs - 1, self.device)
+            cap = []
+            m(ctx.reshape(1, -1, 4, 3), pos.reshape(1, -1, 4, 3), capture_kv=cap)
+            return torch.stack([k[0] for k in cap])
+        return _ops.derived(m, "decodable_pad_kv", list(m.parameters()) + list(m.buffers()), build)
+
+    def _embed(self, ctx, pos):
+        m, t = self.m, self.t
+        ap = m.abs_pos_enc
+        cap = 10 if m.cfg.train.type == "obj" else 12
+        pe = m.transformer_encoder.position_enc.pe[t:t + 1]
+        return native.octattn_embed(ctx, pos, 1, m.occ_enc.weight, m.level_enc.weight, m.octant_enc.weight, ap.weight, ap.bias, pe, cap,
+                                    m.cfg.model.max_octree_level)
+
+    def _kv(self, lyr):
+        a = lyr.attn
+        return _ops.derived(a, "kv_cat", [a.mlp_key.weight, a.mlp_key.bias, a.mlp_value.weight, a.mlp_value.bias], lambda: _kv_cat(a, self.D))
+
+    def _ffn(self, lyr, att, E):
+        """norm1(att + E) -> linear1 / ReLU -> linear2 + residual -> norm2: the batched forward's launches on one row."""
+        E, p1 = native.layernorm_add(att, E, lyr.norm1.weight, lyr.norm1.bias, 1e-5, planes=True)
+        self.h1max.zero_()
+        h1 = native.linear_split_f16(p1, _ops._split16(lyr.linear1.weight), lyr.linear1.bias, native.ACT_RELU, None, row_max=self.h1max)
+        y2 = linear(h1, lyr.linear2.weight, lyr.linear2.bias, residual=E, scales=native.RowScales.from_max(self.h1max))
+        return native.layernorm_add(y2, None, lyr.norm2.weight, lyr.norm2.bias, 1e-5, planes=True)
+
+    @torch.no_grad()
+    def unknown(self, ctx, pos):
+        """ctx uint8 [1, 12], pos float32 [1, 4, 3] of the window's row t (own occupancy: any value) -> logits float32 [1, 255]."""
+        if self.t >= self.cs:
+            raise native.ScpError("OctAttnStepper: the window is full (reset it)")
+        m, D, t = self.m, self.D, self.t
+        E2, pa2 = self._embed(ctx, pos)
+        E, pa = E2[1], pa2.rows(1, 2)
+        for l, lyr in enumerate(m.transformer_encoder.layers):
+            a = lyr.attn
+            wkv, bkv = self._kv(lyr)
+            kvu = native.linear_split_f16(pa, _ops._split16(wkv), bkv, cfg=1)
+            native.linear_split_f16(pa, _ops._split16(a.mlp_query.weight), a.mlp_query.bias, native.ACT_NONE, None, out=self.q[l])
+            att = torch.empty((1, D), dtype=torch.float32, device=self.device)
+            native.octattn_attention_rowinv(self.q[l], self.kv[l, :, :D], self.kv[l, :, _KV_OFF:_KV_OFF + D], m.heads, k_u=kvu[:, :D],
+                                            v_u=kvu[:, _KV_OFF:_KV_OFF + D], out_u=att, q0=t, q1=t + 1, qoff=t)
+            E, pa = self._ffn(lyr, att, E)
+        d0 = native.linear_split_f16(pa, _ops._split16(m.decoder0.weight), m.decoder0.bias, native.ACT_RELU)
+        return linear(d0, m.decoder1.weight, m.decoder1.bias)
+
+    @torch.no_grad()
+    def known(self, ctx, pos):
+        """The same row with its own occupancy decoded (ctx[0, 9]): its key | value rows join the cache; t advances."""
+        m, D, t = self.m, self.D, self.t
+        E2, pa2 = self._embed(ctx, pos)
+        E, pa = E2[0], pa2.rows(0, 1)
+        layers = m.transformer_encoder.layers
+        for l, lyr in enumerate(layers):
+            wkv, bkv = self._kv(lyr)
+            native.linear_split_f16(pa, _ops._split16(wkv), bkv, cfg=1, out=self.kv[l, t:t + 1])
+            if l == len(layers) - 1:                   # the last layer's known stream feeds nothing
+                break
+            att = torch.empty((1, D), dtype=torch.float32, device=self.device)
+            native.octattn_attention_rowinv(self.q[l], self.kv[l, :, :D], self.kv[l, :, _KV_OFF:_KV_OFF + D], m.heads, out=att, q0=t, q1=t + 1,
+                                            qoff=t)
+            E, pa = self._ffn(lyr, att, E)
+        self.t = t + 1

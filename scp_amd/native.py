@@ -120,6 +120,9 @@ def lib():
         "scp_octattn_f16x3_ws_bytes": (C.c_int64, [i32, i32, i32]),
         "scp_octattn_embed": (C.c_int, [_vp, _vp, i64, i32, _vp, i32, _vp, i32, i32, _vp, i32, _vp, _vp, i32, _vp, i32, _vp, _vp, _vp, i64, _vp, _vp, _vp]),
         "scp_octattn_attention_f16x3": (C.c_int, [_vp, _vp, _vp, _vp, _vp, i64, i32, i32, i32, i32, _vp, _vp, _vp, i64, _vp]),
+        "scp_octattn_attention_rowinv": (C.c_int, [_vp, i64, i64, _vp, _vp, i64, i64, _vp, _vp, i64, i64, _vp, _vp, i64, i64, i32, i32, i32, i32, i32,
+                                                   i32, _vp]),
+        "scp_decode_expand_octattn": (C.c_int, [_vp, _vp, _vp, _vp, i64, i32, i32, i32, _vp, _vp, _vp, _vp, _vp]),
         "scp_split_weight_bf16": (C.c_int, [_vp, i32, i32, i32, i32, _vp, _vp, _vp]),
         "scp_linear_bf16x3": (C.c_int, [_vp, i64, _vp, _vp, i32, _vp, _vp, i64, _vp, i64, i32, i32, i32, i32, _vp]),
         "scp_split_weight_f16": (C.c_int, [_vp, i32, i32, i32, i32, _vp, _vp, _vp, _vp]),
@@ -653,7 +656,7 @@ def attention_bf16x3():
     return (_MODES["attn"] == "bf16x3") if p is None else p.attention_bf16x3
 
 
-def numeric_profile(model_name, profile="current"):
+def numeric_profile(model_name, profile="current", decodable=False):
     """The arithmetic variants that decide the logits' last bits - hence the integer CDFs a decoder must reproduce - as a string.  The
     encoder writes it into its side-info file and the decoder refuses a stream coded under another profile.  `profile`: a
     NumericProfile, None (process default) or "current" (this thread's).  The remaining fields are constants since round 4 (the
@@ -662,6 +665,10 @@ def numeric_profile(model_name, profile="current"):
     from . import ops
     from .models import packed
     if model_name == "OctAttention":
+        if decodable:
+            # octattn/1d: the decodable profile (models/oct_attention.py, decodable=True) - every logits row a function of its own window's
+            # rows 0..t only: the row-invariant fp32 attention (csrc/octattn_rowinv.hip), no launch-global V scale
+            return f"octattn/1d:gemm={ops.MODE},attn=rowinv32"
         return f"octattn/1:gemm={ops.MODE},attn={OCTATTN_MODE}"
     if profile == "current":
         profile = current_profile()
@@ -1394,6 +1401,69 @@ def octattn_attention(q_u, k, k_u, v, v_u, heads, out=None, out_u=None, vmax=Non
                                      _dev(out), _dev(out_u), _stream())
     _check(rc, "scp_octattn_attention")
     return out, out_u
+
+
+def _win_strides(t):
+    """(window stride, row stride) in floats of a [B, c, X] or [c, X] float32 device tensor with unit channel stride."""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.stride(-1) == 1):
+        raise ScpError("octattn_attention_rowinv: float32 device tensors with unit channel stride expected")
+    return (t.stride(0) if t.dim() == 3 else 0), t.stride(-2)
+
+
+def octattn_attention_rowinv(q_u, k, v, heads, k_u=None, v_u=None, out=None, out_u=None, q0=0, q1=None, qoff=0):
+    """The decodable profile's dual-stream causal attention (csrc/octattn_rowinv.hip): query rows [q0, q1) of every window, each row
+    bit-identical whatever range or batch it is launched with.  k, v [B, >= q1, D] (or [>= q1, D]): the known stream's keys / values of
+    rows 0 .. q1 - 1 (a column slice of the key | value projection, or a decoder's cache); q_u, k_u, v_u, out, out_u: row r at index
+    r - qoff.  out / out_u: written in place when given (one of them may be None: that stream is skipped)."""
+    D = q_u.shape[-1]
+    B = q_u.shape[0] if q_u.dim() == 3 else 1
+    q1 = (q_u.shape[-2] + qoff) if q1 is None else q1
+    if out is None and out_u is None:
+        raise ScpError("octattn_attention_rowinv: nothing to compute (out and out_u are None)")
+    if q1 > k.shape[-2] or q1 - qoff > q_u.shape[-2]:
+        raise ScpError("octattn_attention_rowinv: query range beyond the key rows")
+    for t in (out, out_u, k_u, v_u):
+        if t is not None and t.shape[-2] < q1 - qoff:
+            raise ScpError("octattn_attention_rowinv: operand shorter than the query range")
+    qw, qr = _win_strides(q_u)
+    kw, kr = _win_strides(k)
+    if _win_strides(v) != (kw, kr):
+        raise ScpError("octattn_attention_rowinv: k and v must share their strides")
+    uw = ur = 0
+    if out_u is not None:
+        uw, ur = _win_strides(k_u)
+        if _win_strides(v_u) != (uw, ur):
+            raise ScpError("octattn_attention_rowinv: k_u and v_u must share their strides")
+    ow, orr = _win_strides(out if out is not None else out_u)
+    if out is not None and out_u is not None and _win_strides(out_u) != (ow, orr):
+        raise ScpError("octattn_attention_rowinv: out and out_u must share their strides")
+    ptr = lambda t: None if t is None else t.data_ptr()        # strided views: the strides above describe them
+    rc = lib().scp_octattn_attention_rowinv(q_u.data_ptr(), qw, qr, k.data_ptr(), v.data_ptr(), kw, kr, ptr(k_u), ptr(v_u), uw, ur, ptr(out),
+                                            ptr(out_u), ow, orr, B, int(q0), int(q1), int(qoff), int(heads), D // heads, _stream())
+    _check(rc, "scp_octattn_attention_rowinv")
+    return out, out_u
+
+
+def decode_expand_octattn(sym, ctx, apos, L, depth):
+    """Decoder, OctAttention layout: children of one decoded level + their model inputs, one launch (csrc/plan.hip:
+    scp_decode_expand_octattn).  sym int64 [n] (-1 = no children), ctx uint8 [n,12], apos int32 [n,4,3] (the parents' context rows and
+    their four integer origins) -> (occ8 uint8 [n], cctx uint8 [m,12], capos int32 [m,4,3], cpos float32 [m,4,3]); one host sync (m)."""
+    dev, n = sym.device, sym.shape[0]
+    tab = _POPC.get(dev)
+    if tab is None:
+        tab = _POPC[dev] = torch.tensor([bin(v).count("1") for v in range(256)], dtype=torch.int64, device=dev)
+    cum = torch.cumsum(tab[sym + 1], 0)
+    m = int(cum[-1])
+    occ8 = torch.empty(n, dtype=torch.uint8, device=dev)
+    cctx = torch.empty((m, 12), dtype=torch.uint8, device=dev)
+    capos = torch.empty((m, 4, 3), dtype=torch.int32, device=dev)
+    cpos = torch.empty((m, 4, 3), dtype=torch.float32, device=dev)
+    if m == 0:
+        return (sym + 1).clamp_(min=0).to(torch.uint8), cctx, capos, cpos
+    _check(lib().scp_decode_expand_octattn(_dev(sym, torch.int64), cum.data_ptr(), _dev(ctx, torch.uint8), _dev(apos, torch.int32), n, int(L),
+                                           int(depth - L), int(depth), cctx.data_ptr(), capos.data_ptr(), cpos.data_ptr(), occ8.data_ptr(), _stream()),
+           "scp_decode_expand_octattn")
+    return occ8, cctx, capos, cpos
 
 
 def octattn_embed(ctx, pos, c, occ_enc, level_enc, octant_enc, pos_w, pos_b, pe, level_cap, max_level):
