@@ -145,32 +145,39 @@ def test_decodable_logits_vs_reference(dmodel, dev, name):
     assert e <= 1e-3
 
 
-def test_step_equals_batched_forward(dmodel, dev):
-    """Teacher-forced steps over a chunk's pad-prefix window and two full windows: every logits row and every integer CDF row equals
-    the batched decodable forward's."""
-    from scp_amd import native
+def _teacher_forced(m, dev, st=None, n=None, poison=False):
+    """Teacher-forced steps over a chunk's pad-prefix window and two full windows (the first n of its 1 + 2 cs rows) -> (the stepper's
+    logits rows, the batched decodable forward's).  poison: after every reset the cache rows >= t are NaN (rows the window has not
+    written yet: after reset(pad=False) they still hold the previous window's values)."""
     from scp_amd.decoder import octattn_window_of
     from scp_amd.models.oct_attention import OctAttnStepper, _pad_rows
-    cs = dmodel.cfg.model.context_size
+    cs = m.cfg.model.context_size
     d, p = _windows(dev, 3)
-    n = 1 + 2 * cs
-    ctx = torch.cat((d[0, -1:], d[1], d[2])).reshape(n, 12).to(torch.uint8)
+    N = 1 + 2 * cs
+    ctx = torch.cat((d[0, -1:], d[1], d[2])).reshape(N, 12).to(torch.uint8)
     pos = torch.cat((p[0, -1:], p[1], p[2]))
     pc, pp = _pad_rows(cs - 1, dev)
     seq_c, seq_p = torch.cat((pc, ctx)), torch.cat((pp, pos))
-    ref = dmodel(seq_c.reshape(3, cs, 4, 3), seq_p.reshape(3, cs, 4, 3)).reshape(-1, 255)[cs - 1:]
-    st = OctAttnStepper(dmodel)
+    ref = m(seq_c.reshape(3, cs, 4, 3), seq_p.reshape(3, cs, 4, 3)).reshape(-1, 255)[cs - 1:]
+    st = OctAttnStepper(m) if st is None else st
     rows = []
-    for r in range(n):
+    for r in range(N if n is None else n):
         w, t = octattn_window_of(r, cs)
         if r == 0 or t == 0:
             st.reset(pad=(w == 0))
+            if poison:
+                st.kv[:, st.t:] = float("nan")
         assert st.t == t
         unk = ctx[r:r + 1].clone()
         unk[0, 9] = 255
         rows.append(st.unknown(unk, pos[r:r + 1]))
         st.known(ctx[r:r + 1], pos[r:r + 1])
     got = torch.cat(rows)
+    return got, ref[:got.shape[0]]
+
+
+def _assert_rows_equal(got, ref):
+    from scp_amd import native
     bad = (got != ref).any(1).nonzero().flatten()[:10].tolist()
     assert torch.equal(got, ref), f"rows differing: {bad}"
     c1 = native.softmax_cdf(got, want_lohi=False, want_cdf=True)["cdf"]
@@ -178,11 +185,59 @@ def test_step_equals_batched_forward(dmodel, dev):
     assert torch.equal(c1, c2)
 
 
+def test_step_equals_batched_forward(dmodel, dev):
+    """Teacher-forced steps over a chunk's pad-prefix window and two full windows: every logits row and every integer CDF row equals
+    the batched decodable forward's."""
+    _assert_rows_equal(*_teacher_forced(dmodel, dev))
+
+
+def test_step_reads_no_cache_row_at_or_after_t(dmodel, dev):
+    """The same steps with NaN in every cache row >= t after each reset: the unknown pass reads rows < t only, the known pass row t only
+    once it has written it - every logits row keeps its bits."""
+    got, ref = _teacher_forced(dmodel, dev, poison=True)
+    assert bool(torch.isfinite(got).all())
+    _assert_rows_equal(got, ref)
+
+
+def test_stepper_follows_weight_updates(dev):
+    """The stepper's derived weights (the pad rows' K / V cache, the fused key | value weight: ops.derived) follow an in-place refill of
+    the parameters, in the same stepper and in a new one.  A model of its own: the module-scoped one stays untouched."""
+    from scp_amd import ops
+    from scp_amd.models import OctAttention
+    from scp_amd.models.oct_attention import OctAttnStepper, _kv_cat, _pad_rows
+    from scp_amd.weights import fill_weights
+    m = fill_weights(OctAttention(octattn_cfg(), decodable=True), 0).to(dev)
+    n = 1 + 64                                        # the pad window's row and the next window's first 64 rows
+    st = OctAttnStepper(m)
+    got0, ref0 = _teacher_forced(m, dev, st, n)
+    _assert_rows_equal(got0, ref0)
+    lyr = m.transformer_encoder.layers[0]
+    pad0, kv0 = st.prefill_pad(), st._kv(lyr)
+    fill_weights(m, 1)
+    got1, ref1 = _teacher_forced(m, dev, st, n)
+    assert not torch.equal(ref1, ref0)
+    _assert_rows_equal(got1, ref1)
+    _assert_rows_equal(*_teacher_forced(m, dev, OctAttnStepper(m), n))
+    pad1, kv1 = st.prefill_pad(), st._kv(lyr)
+    cap = []
+    pc, pp = _pad_rows(m.cfg.model.context_size - 1, dev)
+    m(pc.reshape(1, -1, 4, 3), pp.reshape(1, -1, 4, 3), capture_kv=cap)
+    assert not torch.equal(pad1, pad0) and torch.equal(pad1, torch.stack([k[0] for k in cap]))
+    w, b = _kv_cat(lyr.attn, m.embed_dimension)
+    assert not torch.equal(kv1[0], kv0[0]) and torch.equal(kv1[0], w) and torch.equal(kv1[1], b)
+    fill_weights(m, 2)
+    with ops.frozen_weights():                        # the decoder's frame scope validates each derived weight at its first use
+        got2, ref2 = _teacher_forced(m, dev, st, n)
+    _assert_rows_equal(got2, ref2)
+    assert not torch.equal(ref2, ref1)
+
+
 def _round_trip(model, dev, tmp_path, xyz, level, spher=False, cylin=False, level_wise=False, stem="f", ints=None, data_type="kitti"):
     """Encode decodable, write stream + side-info, decode.  ints = (integers [P, 3], bin_num, quant) given from outside, else the encoder
-    quantises.  Checks: decoded codes = the encoder's symbols, leaves = the encoder's distinct integers, and every ORIGINAL point lies
-    within its quantisation cell's error bound of the decoded point of its leaf (an independent check of the de-quantisation: offsets,
-    steps, the cylindrical z offset)."""
+    quantises.  Checks: every logits row the decoder computes = the encoder's row (and so every integer CDF row), decoded codes = the
+    encoder's symbols, leaves = the encoder's distinct integers, and every ORIGINAL point lies within its quantisation cell's error bound
+    of the decoded point of its leaf (an independent check of the de-quantisation: offsets, steps, the cylindrical z offset)."""
+    from scp_amd import native
     from scp_amd.decoder import decode_octattn_file, write_sidecar
     from scp_amd.encoder import OctAttnFrameEncoder
     enc = OctAttnFrameEncoder(model, data_type, level, spher=spher, cylin=cylin, level_wise=level_wise, device=dev, decodable=True)
@@ -198,7 +253,32 @@ def _round_trip(model, dev, tmp_path, xyz, level, spher=False, cylin=False, leve
         f.write(res["bytes"])
     side = write_sidecar(out, enc, res, "OctAttention")
     assert side["profile"].startswith("octattn/1d:") and side["context_size"] == 1024 and side["level_wise"] == level_wise
-    got = decode_octattn_file(out, model, dev)
+    # every logits row the decoder computes, recorded on the device (no host sync per node) by a wrapper of OctAttnStepper.unknown for
+    # the length of the decode: the range decoder reads only the CDF entries around each symbol, so decoded symbols alone do not show
+    # that the decoder's CDF rows are the encoder's
+    from scp_amd.models.oct_attention import OctAttnStepper
+    table = res["_debug"]["table"]
+    rows = torch.empty_like(table)
+    seen = [0]
+    unknown = OctAttnStepper.unknown
+
+    def record(self, ctx, pos):
+        logits = unknown(self, ctx, pos)
+        if seen[0] < rows.shape[0]:
+            rows[seen[0]].copy_(logits[0])
+        seen[0] += 1
+        return logits
+
+    OctAttnStepper.unknown = record
+    try:
+        got = decode_octattn_file(out, model, dev)
+    finally:
+        OctAttnStepper.unknown = unknown
+    assert seen[0] == table.shape[0] == res["n_nodes"]
+    bad = (rows != table).any(1).nonzero().flatten()[:10].tolist()
+    assert torch.equal(rows, table), f"decoder logits rows differing from the encoder's: {bad}"
+    cdf = lambda t: native.softmax_cdf(t, want_lohi=False, want_cdf=True)["cdf"]
+    assert torch.equal(cdf(rows), cdf(table))
     sym = res["_debug"]["sym_coded"].cpu().numpy().astype(np.int64)
     assert np.array_equal(got["codes"][0].cpu().numpy().astype(np.int64) - 1, sym)
     q = qs[0].cpu().numpy().astype(np.int64)
