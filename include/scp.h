@@ -43,7 +43,7 @@ extern "C" {
  *   220  GELU (round 5, numeric profile ehem/5): max(y, 0) - |y| exp(-beta y^2) / P4(|y|) instead of the degree-12 erf polynomial, in every
  *        kernel that applies it; scp_swin_post_attn expects fc1 scaled by scp_gelu_prescale() and fc2 by its inverse.
  *        (additive, no new version: scp_decode_expand, scp_linear_split_f16_max, scp_row_scale_from_max, scp_octattn_attention_f16x3_vmax;
- *        round 6: scp_linear_split_hier2, scp_mlp3_rows; scp_octattn_attention_rowinv, scp_decode_expand_octattn - existing entry points keep their bits, the EHEM model's numeric profile moved to ehem/6
+ *        round 6: scp_linear_split_hier2, scp_mlp3_rows; scp_octattn_attention_rowinv, scp_decode_expand_octattn, scp_octattn_attention_rowinv_step - existing entry points keep their bits, the EHEM model's numeric profile moved to ehem/6
  *        because models/packed.py now calls the two new ones.) */
 #define SCP_ABI_VERSION 220
 SCP_API int scp_version(void);
@@ -368,6 +368,16 @@ SCP_API int scp_octattn_attention_f16x3_vmax(const float *q_u, const float *k, c
 SCP_API int scp_octattn_attention_rowinv(const float *q_u, int64_t qw, int64_t qr, const float *k, const float *v, int64_t kw, int64_t kr,
                                          const float *k_u, const float *v_u, int64_t uw, int64_t ur, float *out, float *out_u, int64_t ow,
                                          int64_t orr, int32_t B, int32_t q0, int32_t q1, int32_t qoff, int32_t H, int32_t hd, void *stream);
+/* The same attention for ONE query row per stream (the lockstep decoder's step, csrc/octattn_rowinv.hip): launch row s is the node a
+ * stream is decoding; it sits at row t[slot[s]] of the window cached in slot slot[s] of k / v (`slots` windows of `rows` <= 1024 rows,
+ * slot stride kw, row stride kr, floats).  t int32 [slots] and slot int32 [S] are DEVICE arrays: no stream's position is a launch
+ * argument.  q_u, k_u, v_u, out, out_u: row s at s * qr / ur / orr.  Row s is bit-identical to scp_octattn_attention_rowinv with
+ * q0 = t, q1 = t + 1 on that slot's cache; cache rows >= t (> t when out is wanted) and slots not listed are not read; a row whose
+ * slot or t is out of range is not written.  out or out_u may be NULL. */
+SCP_API int scp_octattn_attention_rowinv_step(const float *q_u, int64_t qr, const float *k, const float *v, int64_t kw, int64_t kr,
+                                              int32_t slots, int32_t rows, const float *k_u, const float *v_u, int64_t ur, float *out,
+                                              float *out_u, int64_t orr, const int32_t *t, const int32_t *slot, int32_t S, int32_t H,
+                                              int32_t hd, void *stream);
 /* The children of one decoded octree level in OctAttention's context layout (the decoder's sibling of scp_decode_expand):
  * sym / cum as there; ctx uint8 [n][12] = (occ, level, octant) x (ggp, gp, p, self) of the parents (own occupancy not read), apos int32
  * [n][4][3] the four rows' integer origins (0 for pad rows), L = the parents' level, shift = depth - L.  Child c of parent i: ctx =

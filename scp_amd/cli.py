@@ -353,15 +353,26 @@ def get_decode_octattn_args(argv=None):
     p.add_argument("--lidar_level", type=int, default=None, help="checked against the side-info file")
     p.add_argument("--type", type=str, default=None, choices=[None, "obj", "kitti", "ford"])
     p.add_argument("--preproc_path", type=str, default="")
+    p.add_argument("--streams", type=_streams_arg, default=1,
+                   help="decode this many files at a time in lockstep, one model step serving one node of each (1 .. 64; default 1: one "
+                        "file after the other).  With more than one, the time printed per file is the total over the number of files")
     return p.parse_args(argv)
+
+
+def _streams_arg(v):
+    n = int(v)
+    if not 1 <= n <= 64:
+        raise argparse.ArgumentTypeError(f"--streams {v}: 1 .. 64 expected")
+    return n
 
 
 def decode_octattn_main(argv=None):
     """Drop-in for the reference's decode.py (decodeOct): for every original file, its `<stem>.bin` (`find_stream`) written by
     `encode.py --decodable` is decoded (scp_amd/decoder.py: OctAttnFrameDecoder), checked against the record file `<stem>.npy` when it
     exists, and written as `<stem>.ply`.  The stream's side-info file carries the window length, level-wise flag, depth and profile;
-    streams of the default profile, --sequential and multi-level streams are refused with the reason."""
-    from .decoder import decode_octattn_file, read_sidecar
+    streams of the default profile, --sequential and multi-level streams are refused with the reason.  `--streams S` (S > 1) decodes
+    the files S at a time in lockstep (decoder.decode_octattn_files): the same checks, files and printed lines per file."""
+    from .decoder import decode_octattn_file, decode_octattn_files, read_sidecar
     args = get_decode_octattn_args(argv)
     if not torch.cuda.is_available():
         raise native.ScpError("decode needs an MI355X: the SCP hot path has no CPU fallback")
@@ -384,8 +395,8 @@ def decode_octattn_main(argv=None):
         out_root = root + "test_output" + (args.ckpt_path.split("ckpt")[1][:-1] if args.ckpt_path else "") + "/"
     files = expand_files(args.test_files)
     elapsed, results = 0.0, []
-    for i, ori in enumerate(files):
-        print(f"{i}/{len(files)}")
+
+    def locate(ori):
         name, stem = find_stream(out_root, ori)
         binfile = out_root + name
         side = read_sidecar(binfile)
@@ -396,11 +407,9 @@ def decode_octattn_main(argv=None):
                 raise native.ScpError(f"{binfile}: coded at lidar level {side.get('lidar_level')}, --lidar_level {args.lidar_level} given")
             if args.type is not None and args.type != side.get("type"):
                 raise native.ScpError(f"{binfile}: coded as --type {side.get('type')}, --type {args.type} given")
-        t0 = time.time()
-        out = decode_octattn_file(binfile, model, dev)
-        torch.cuda.synchronize()
-        t = time.time() - t0
-        elapsed += t
+        return binfile, stem
+
+    def report(ori, stem, out, t):
         npy = (args.preproc_path.rstrip("/") + "/" + Path(ori).stem) if args.preproc_path else str(ori).rsplit(".")[0]
         if os.path.exists(npy + ".npy"):                       # the reference asserts every node against it (decode.py:99)
             want = np.load(npy + ".npy")[:, -1, 0]
@@ -413,6 +422,27 @@ def decode_octattn_main(argv=None):
         pointCloud.write_ply_data(ply, out["points"].cpu().numpy())
         print(ply)
         results.append((ply, out))
+
+    if args.streams > 1:
+        # every stream is located and its side-info checked first; then the files are decoded `streams` at a time in lockstep
+        found = [locate(ori) for ori in files]
+        t0 = time.time()
+        outs = decode_octattn_files([b for b, _ in found], model, streams=args.streams, device=dev)
+        torch.cuda.synchronize()
+        elapsed = time.time() - t0
+        for i, (ori, (_, stem), out) in enumerate(zip(files, found, outs)):
+            print(f"{i}/{len(files)}")
+            report(ori, stem, out, elapsed / len(files))
+    else:
+        for i, ori in enumerate(files):
+            print(f"{i}/{len(files)}")
+            binfile, stem = locate(ori)
+            t0 = time.time()
+            out = decode_octattn_file(binfile, model, dev)
+            torch.cuda.synchronize()
+            t = time.time() - t0
+            elapsed += t
+            report(ori, stem, out, t)
     print(elapsed / max(len(files), 1))
     return results
 

@@ -204,3 +204,163 @@ extern "C" SCP_API int scp_octattn_attention_rowinv(const float *q_u, int64_t qw
     LAUNCH_CHECK();
     return SCP_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ one query row per stream
+// The decoder's lockstep step: launch row s is the current node of one stream; it sits at row t[slot[s]] of the window whose known
+// stream's keys / values are cache slot slot[s].  Both arrays live on the device, so nothing about a stream's position is a launch
+// argument.  Row s comes out bit-identical to octattn_rowinv_kernel launched with q0 = t, q1 = t + 1 on that cache - the same
+// arithmetic sequence (header comment), laid out for ONE query row instead of 32:
+//   1. scores: every key j < t is an independent fp32 FMA chain over the head's channels, one key per thread, K staged through LDS
+//      in tiles of RS_KT rows (coalesced row reads, conflict-free column reads); the two diagonal scores ride along on idle waves;
+//   2. the (M, alpha) recurrence over the <= 32 flash tiles of 32 keys: tile maxima in parallel, the chain on one thread;
+//      p_j = exp(s_j - M_tile) by all threads; tile sums in parallel, the L chain by register shuffles inside the idle fourth wave;
+//   3. PV: one chain per channel (thread d) over the keys, alpha applied at each tile boundary, the next tile's V rows in flight
+//      while the current one is folded in;
+//   4. the diagonal term closes the state (m2 / a2 / p2) exactly as above.
+// Workgroup = one (stream, head); 256 threads.  Cache rows >= t (> t when `out` is wanted) and slots not listed are never read.
+#define RS_KT 128                 // keys per LDS tile of the score pass (128 x 153 floats = 76.5 KB)
+#define RS_MAXT 1024              // cache rows limit: the scores of one (stream, head) stay in LDS
+#define RS_SI(k) ((k) + ((k) >> 5))   // score k's LDS index: flash tile starts land on different banks
+static_assert(RI_MAXHD <= 192, "the fourth wave must stay free of PV work");
+
+struct RowInvStepArgs {
+    const float *q, *k, *v, *ku, *vu;
+    float *out, *out_u;
+    const int32_t *t, *slot;
+    int64_t qr, kw, kr, ur, orr;               // row strides of q, k_u = v_u, out = out_u; slot / row stride of the cache (floats)
+    int32_t slots, rows, H, hd;
+    float scale;
+};
+
+__global__ __launch_bounds__(256) void octattn_rowinv_step_kernel(const RowInvStepArgs a) {
+    __shared__ float sK[RS_KT * RI_LDQ];
+    __shared__ float sQ[RI_MAXHD], sD[2][RI_MAXHD];
+    __shared__ float sS[RS_MAXT + RS_MAXT / 32];
+    __shared__ float sMt[32], sMn[32], sAlpha[32], sDiag[2], sML[2];
+    const int tid = threadIdx.x, hd = a.hd, h = blockIdx.x, s = blockIdx.y;
+    const int sl = a.slot[s];
+    if (sl < 0 || sl >= a.slots) return;          // (uniform over the workgroup) a slot the cache does not have: the row is left alone
+    const int t = a.t[sl];
+    if (t < 0 || t >= a.rows) return;
+    const float *kb = a.k + (int64_t)sl * a.kw + (int64_t)h * hd;
+    const float *vb = a.v + (int64_t)sl * a.kw + (int64_t)h * hd;
+    const int wv = tid >> 6, ln = tid & 63;
+
+    for (int d = tid; d < hd; d += 256) {
+        sQ[d] = a.q[(int64_t)s * a.qr + (int64_t)h * hd + d];
+        sD[0][d] = a.out ? kb[(int64_t)t * a.kr + d] : 0.f;
+        sD[1][d] = a.out_u ? a.ku[(int64_t)s * a.ur + (int64_t)h * hd + d] : 0.f;
+    }
+    __syncthreads();
+    if (tid == 128 || tid == 192) {               // the diagonal scores, on the waves the score pass leaves idle
+        const int which = tid == 192;
+        float sc = 0.f;
+        for (int d = 0; d < hd; ++d) sc = fmaf(sQ[d], sD[which][d], sc);
+        sDiag[which] = sc * a.scale;
+    }
+    // 1. scores of the keys below t
+    for (int k0 = 0; k0 < t; k0 += RS_KT) {
+        const int nkt = min(RS_KT, t - k0);
+        __syncthreads();                          // the previous tile is consumed
+#pragma unroll 4
+        for (int j = wv; j < nkt; j += 4) {
+            const float *kr = kb + (int64_t)(k0 + j) * a.kr;
+            for (int d = ln; d < hd; d += 64) sK[j * RI_LDQ + d] = kr[d];
+        }
+        __syncthreads();
+        if (tid < nkt) {
+            float sc = 0.f;
+            for (int d = 0; d < hd; ++d) sc = fmaf(sQ[d], sK[tid * RI_LDQ + d], sc);
+            sS[RS_SI(k0 + tid)] = sc * a.scale;
+        }
+    }
+    __syncthreads();
+    // 2. flash state over tiles of RI_KT keys
+    const int ntile = (t + RI_KT - 1) / RI_KT;
+    if (tid < ntile) {
+        const int k0 = tid * RI_KT, nk = min(RI_KT, t - k0);
+        float mt = sS[RS_SI(k0)];
+        for (int j = 1; j < nk; ++j) mt = fmaxf(mt, sS[RS_SI(k0 + j)]);
+        sMt[tid] = mt;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float M = -INFINITY;
+        for (int i = 0; i < ntile; ++i) {
+            const float mn = fmaxf(M, sMt[i]);
+            sAlpha[i] = __expf(M - mn);
+            sMn[i] = mn;
+            M = mn;
+        }
+        sML[0] = M;
+    }
+    __syncthreads();
+    for (int k = tid; k < t; k += 256) sS[RS_SI(k)] = __expf(sS[RS_SI(k)] - sMn[k >> 5]);
+    __syncthreads();
+    float acc = 0.f;
+    if (wv == 3) {                                // L' = L alpha + sum_j p_j: lane i sums tile i, the chain runs on shuffled values
+        float ps = 0.f, al = 0.f;
+        if (ln < ntile) {
+            const int k0 = ln * RI_KT, nk = min(RI_KT, t - k0);
+            for (int j = 0; j < nk; ++j) ps += sS[RS_SI(k0 + j)];
+            al = sAlpha[ln];
+        }
+        float L = 0.f;
+        for (int i = 0; i < ntile; ++i) L = L * __shfl(al, i) + __shfl(ps, i);
+        if (ln == 0) sML[1] = L;
+    } else if (tid < hd) {
+        // 3. PV: channel tid of the head
+        float vn[RI_KT];
+#pragma unroll
+        for (int j = 0; j < RI_KT; ++j) vn[j] = j < t ? vb[(int64_t)j * a.kr + tid] : 0.f;
+        for (int i = 0; i < ntile; ++i) {
+            const int k0 = i * RI_KT, nk = min(RI_KT, t - k0);
+            float vx[RI_KT];
+#pragma unroll
+            for (int j = 0; j < RI_KT; ++j) vx[j] = vn[j];
+#pragma unroll
+            for (int j = 0; j < RI_KT; ++j) vn[j] = k0 + RI_KT + j < t ? vb[(int64_t)(k0 + RI_KT + j) * a.kr + tid] : 0.f;
+            acc *= sAlpha[i];
+#pragma unroll
+            for (int j = 0; j < RI_KT; ++j)
+                if (j < nk) acc = fmaf(sS[RS_SI(k0 + j)], vx[j], acc);
+        }
+    }
+    __syncthreads();
+    // 4. the diagonal term
+    if (tid < hd) {
+        const float M = sML[0], L = sML[1];
+        for (int which = 0; which < 2; ++which) {
+            float *ob = which == 0 ? a.out : a.out_u;
+            if (!ob) continue;
+            const float sd = sDiag[which];
+            const float m2 = fmaxf(M, sd);
+            const float a2 = __expf(M - m2), p2 = __expf(sd - m2);
+            const float L2 = L * a2 + p2;
+            const float vr = which == 0 ? vb[(int64_t)t * a.kr + tid] : a.vu[(int64_t)s * a.ur + (int64_t)h * hd + tid];
+            ob[(int64_t)s * a.orr + (int64_t)h * hd + tid] = (acc * a2 + p2 * vr) / L2;
+        }
+    }
+}
+
+// S launch rows, one query row each.  q_u, k_u, v_u, out, out_u: row s at s * (their row stride).  k / v: the known stream's cache,
+// `slots` windows of `rows` rows (slot stride kw, row stride kr); launch row s reads rows 0 .. t[slot[s]] - 1 of slot slot[s] (and
+// row t itself when `out` is wanted).  t int32 [slots] and slot int32 [S] are DEVICE arrays.  A row whose slot lies outside
+// [0, slots) or whose t lies outside [0, rows) is not written.
+extern "C" SCP_API int scp_octattn_attention_rowinv_step(const float *q_u, int64_t qr, const float *k, const float *v, int64_t kw, int64_t kr,
+                                                         int32_t slots, int32_t rows, const float *k_u, const float *v_u, int64_t ur, float *out,
+                                                         float *out_u, int64_t orr, const int32_t *t, const int32_t *slot, int32_t S, int32_t H,
+                                                         int32_t hd, void *stream) {
+    if (!q_u || !k || !v || !t || !slot || (!out && !out_u) || (out_u && (!k_u || !v_u)) || S <= 0 || H <= 0 || hd <= 0 || hd > RI_MAXHD ||
+        slots <= 0 || rows <= 0 || rows > RS_MAXT || qr < (int64_t)H * hd || kr < (int64_t)H * hd || kw < 0 || (slots > 1 && kw < (int64_t)rows * kr) ||
+        (out_u && ur < (int64_t)H * hd) || orr < (int64_t)H * hd)
+        return SCP_EINVAL;
+    RowInvStepArgs a;
+    a.q = q_u; a.k = k; a.v = v; a.ku = k_u; a.vu = v_u; a.out = out; a.out_u = out_u; a.t = t; a.slot = slot;
+    a.qr = qr; a.kw = kw; a.kr = kr; a.ur = ur; a.orr = orr;
+    a.slots = slots; a.rows = rows; a.H = H; a.hd = hd;
+    a.scale = 1.0f / sqrtf((float)hd);
+    hipLaunchKernelGGL(octattn_rowinv_step_kernel, dim3((unsigned)H, (unsigned)S), dim3(256), 0, (hipStream_t)stream, a);
+    LAUNCH_CHECK();
+    return SCP_OK;
+}

@@ -128,6 +128,11 @@ def decode_octattn_file(binfile, model, device=None):
         stream = f.read()
     dec = OctAttnFrameDecoder(model, side["depth"], level_wise=side["level_wise"], device=device)
     codes, leaves = dec.decode(stream, side["n_nodes"])
+    return _octattn_result(side, codes, leaves, dec.stats)
+
+
+def _octattn_result(side, codes, leaves, stats):
+    """Decoded codes and leaf integers -> the dict decode_octattn_file returns (the leaves de-quantised by the side-info's rule)."""
     spher, cylin = side["spher"], side["cylin"]
     data_type, quant = side["type"], side.get("quant")
     if data_type == "obj" and quant:
@@ -140,7 +145,7 @@ def decode_octattn_file(binfile, model, device=None):
         # encoder's fixed rule (qs 2^(18 - L), offset -2^17: OctAttnFrameEncoder.cart_offset)
         qs = shell_qs(data_type, side["lidar_level"], False)[0]
         pts = dequantise_leaves(leaves, qs, side["bin_nums"][0], side["z_offset"], spher, cylin, data_type)
-    return dict(codes=[codes], leaves=[leaves], points=pts, spher=spher, cylin=cylin, stats=dec.stats)
+    return dict(codes=[codes], leaves=[leaves], points=pts, spher=spher, cylin=cylin, stats=stats)
 
 
 class OctAttnFrameDecoder:
@@ -221,6 +226,209 @@ class OctAttnFrameDecoder:
         finally:
             self.model.decodable = prev
         return torch.cat(codes), apos[:, 3].long()
+
+
+def decode_octattn_files(binfiles, model, streams=1, device=None):
+    """Several OctAttention streams written with `--decodable`, decoded `streams` at a time in lockstep (OctAttnBatchDecoder): one model
+    step serves one node of every stream in flight.  -> the dicts decode_octattn_file returns, in the order of `binfiles`, each with
+    the bits the one-stream decoder gives.  The streams share the model; they may differ in depth, coordinate system, data type, lidar
+    level and `level_wise`.  Every side-info file is read and checked before anything is decoded."""
+    if streams < 1:
+        raise native.ScpError("decode_octattn_files: streams >= 1 expected")
+    binfiles = [str(b) for b in binfiles]
+    sides = []
+    for binfile in binfiles:
+        side = read_sidecar(binfile)
+        _refuse_octattn(binfile, side)
+        if side["context_size"] != model.cfg.model.context_size:
+            raise native.ScpError(f"{binfile}: coded with context size {side['context_size']}, the model has {model.cfg.model.context_size}")
+        sides.append(side)
+    if not binfiles:
+        return []
+    jobs = []
+    for binfile, side in zip(binfiles, sides):
+        with open(binfile, "rb") as f:
+            jobs.append(dict(name=binfile, stream=f.read(), n_nodes=side["n_nodes"], depth=side["depth"], level_wise=side["level_wise"]))
+    dec = OctAttnBatchDecoder(model, min(int(streams), len(jobs)), device=device)
+    return [_octattn_result(side, codes, leaves, dec.stats) for side, (codes, leaves) in zip(sides, dec.decode(jobs))]
+
+
+class OctAttnLockstep:
+    """The host bookkeeping of the lockstep decoder, free of any device state (tests drive it with made-up level sizes).  `slots`
+    slots each hold one file's position: level L, node i of the level's n, row r of the chunk (`level_wise`: a chunk per level).
+    A step visits one node of every active slot; its window and position follow `octattn_window_of` exactly as in
+    OctAttnFrameDecoder.decode.  Idle slots take the pending files in file order (`refill`, lowest idle slot first)."""
+
+    def __init__(self, n_files, slots, context_size, level_wise):
+        self.cs = int(context_size)
+        self.level_wise = [bool(x) for x in level_wise]
+        assert len(self.level_wise) == n_files and slots >= 1
+        self.pending = list(range(n_files))[::-1]
+        self.file = [None] * slots
+        self.L = [0] * slots
+        self.n = [0] * slots
+        self.i = [0] * slots
+        self.r = [0] * slots
+
+    def refill(self):
+        """-> [(slot, file)] newly started: level 1, the root node alone."""
+        new = []
+        for s in range(len(self.file)):
+            if self.file[s] is None and self.pending:
+                self.file[s] = self.pending.pop()
+                self.L[s], self.n[s], self.i[s], self.r[s] = 1, 1, 0, 0
+                new.append((s, self.file[s]))
+        return new
+
+    def active(self):
+        return tuple(s for s, f in enumerate(self.file) if f is not None)
+
+    def step(self):
+        """One node of every active slot (no slot may sit at the end of its level) -> [(slot, file, node index in its level, window,
+        position, reset, pad)]: reset = the slot's window starts here, pad = with the chunk's front padding."""
+        rows = []
+        for s, f in enumerate(self.file):
+            if f is None:
+                continue
+            assert self.i[s] < self.n[s]
+            w, p = octattn_window_of(self.r[s], self.cs)
+            reset = self.r[s] == 0 or p == 0
+            rows.append((s, f, self.i[s], w, p, reset, reset and w == 0))
+            self.i[s] += 1
+            self.r[s] += 1
+        return rows
+
+    def level_ends(self):
+        """The slots whose level is decoded: each needs next_level() or finish() before the next step."""
+        return [s for s, f in enumerate(self.file) if f is not None and self.i[s] == self.n[s]]
+
+    def next_level(self, slot, n):
+        self.L[slot] += 1
+        self.n[slot], self.i[slot] = int(n), 0
+        if self.level_wise[self.file[slot]]:
+            self.r[slot] = 0
+
+    def finish(self, slot):
+        self.file[slot] = None
+
+
+class OctAttnBatchDecoder:
+    """OctAttnFrameDecoder for several streams at once.  Slot s of an OctAttnBatchStepper holds the window of one stream; in one step
+    every active slot decodes exactly one node: one `unknown` over the active slots, one CDF launch on [B, 255], ONE pinned
+    device-to-host copy of the B CDF rows and one stream synchronisation, B range-decoder calls (each stream has its own decoder),
+    ONE host-to-device copy of the B symbols, one `known`.  Each slot's current level (context rows, positions) lies in its region
+    of one device arena; the step's rows are gathered by a device index array that is advanced on the device, so the host work of a
+    step beyond the B range-decoder calls does not grow with B.  A slot that finishes a level expands it for itself
+    (native.decode_expand_octattn, one host sync) and goes on in the next step; a slot whose frame is complete takes the next
+    pending file.  Each stream's symbols, codes and leaves are those of OctAttnFrameDecoder, bit for bit."""
+
+    def __init__(self, model, streams, device=None):
+        self.model = model
+        self.slots = int(streams)
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.context_size = model.cfg.model.context_size
+        self.stats = None             # set to {} to collect wall seconds per stage (a device synchronisation per stamp)
+        self.steps = 0
+        self._pin = torch.empty((self.slots, 256), dtype=torch.int16, pin_memory=True)
+        self._pin_sym = torch.empty((self.slots,), dtype=torch.uint8, pin_memory=True)
+
+    _stamp = OctAttnFrameDecoder._stamp
+
+    def decode(self, jobs):
+        """jobs: dicts(name, stream bytes, n_nodes, depth, level_wise) -> [(codes uint8 [n_nodes] in BFS order, leaves int64 [U, 3])] in
+        the order of `jobs`."""
+        from . import ops
+        from .models.oct_attention import OctAttnBatchStepper
+        import time
+        dev, cs, S = self.device, self.context_size, self.slots
+        prev = self.model.decodable
+        self.model.decodable = True
+        try:
+            with ops.frozen_weights():
+                st = OctAttnBatchStepper(self.model, S)
+                sched = OctAttnLockstep(len(jobs), S, cs, [j["level_wise"] for j in jobs])
+                cap = max(max(int(j["n_nodes"]) for j in jobs), 1)       # a level holds at most all of a frame's nodes
+                ctx_a = torch.empty((S * cap, 12), dtype=torch.uint8, device=dev)
+                pos_a = torch.empty((S * cap, 4, 3), dtype=torch.float32, device=dev)
+                cur = torch.zeros((S,), dtype=torch.int64, device=dev)   # arena row of each slot's next node
+                one = torch.ones((S,), dtype=torch.int64, device=dev)
+                root = torch.tensor([255, 0, 0] * 3 + [255, 1, 1], dtype=torch.uint8, device=dev)     # the root: level 1, octant 1
+                decs, syms, apos, codes, done = [None] * S, [None] * S, [None] * S, [None] * S, [0] * S
+                results = [None] * len(jobs)
+                pin_np, sym_np = self._pin.numpy(), self._pin_sym.numpy()
+                stream_ = torch.cuda.current_stream(dev)
+
+                def start(s, f):
+                    decs[s] = native.AcDecoder(jobs[f]["stream"])
+                    syms[s], codes[s], done[s] = np.empty(1, np.int64), [], 0
+                    apos[s] = torch.zeros((1, 4, 3), dtype=torch.int32, device=dev)
+                    ctx_a[s * cap].copy_(root)
+                    pos_a[s * cap].zero_()
+                    cur[s:s + 1].fill_(s * cap)
+
+                for s, f in sched.refill():
+                    start(s, f)
+                act = sched.active()
+                t = time.perf_counter() if self.stats is not None else 0.0
+                if self.stats is not None:
+                    torch.cuda.synchronize()
+                while act:
+                    rows = sched.step()
+                    for pad in (True, False):
+                        ids = [r[0] for r in rows if r[5] and r[6] == pad]
+                        if ids:
+                            st.reset(ids, pad)
+                    B = len(act)
+                    a64 = st._slot_ids(act)[2]
+                    idx = cur.index_select(0, a64)
+                    crow, prow = ctx_a.index_select(0, idx), pos_a.index_select(0, idx)
+                    logits = st.unknown(act, crow, prow)
+                    t = self._stamp("model_step", t)
+                    self._pin[:B].copy_(native.softmax_cdf(logits, want_lohi=False, want_cdf=True)["cdf"], non_blocking=True)
+                    stream_.synchronize()
+                    t = self._stamp("cdf_d2h", t)
+                    for b, (s, _, i, _, _, _, _) in enumerate(rows):
+                        sym_np[b] = syms[s][i] = decs[s].next(pin_np[b])
+                    t = self._stamp("range_decoder", t)
+                    crow[:, 9] = self._pin_sym[:B].to(dev, non_blocking=True)
+                    st.known(act, crow, prow)
+                    cur.index_add_(0, a64, one[:B])
+                    self.steps += 1
+                    t = self._stamp("model_step", t)
+                    ends = sched.level_ends()
+                    for s in ends:
+                        f, L, job = sched.file[s], sched.L[s], jobs[sched.file[s]]
+                        n, lo = sched.n[s], s * cap
+                        done[s] += n
+                        occ8, cctx, apos[s], cpos = native.decode_expand_octattn(torch.from_numpy(syms[s]).to(dev), ctx_a[lo:lo + n], apos[s], L,
+                                                                                 job["depth"])
+                        codes[s].append(occ8)
+                        m = cctx.shape[0]
+                        if L == job["depth"]:
+                            if done[s] != job["n_nodes"]:
+                                raise native.ScpError(f"{job['name']}: decoded {done[s]} nodes, the side-info says {job['n_nodes']}")
+                            results[f] = (torch.cat(codes[s]), apos[s][:, 3].long())
+                            decs[s] = syms[s] = apos[s] = codes[s] = None
+                            sched.finish(s)
+                            continue
+                        if done[s] + m > job["n_nodes"]:
+                            raise native.ScpError(f"{job['name']}: the octree has more than the side-info's {job['n_nodes']} nodes: stream and "
+                                                  "side-info disagree")
+                        if m == 0:
+                            raise native.ScpError(f"{job['name']}: decoded {done[s]} nodes, the side-info says {job['n_nodes']}")
+                        ctx_a[lo:lo + m].copy_(cctx)
+                        pos_a[lo:lo + m].copy_(cpos)
+                        cur[s:s + 1].fill_(lo)
+                        syms[s] = np.empty(m, np.int64)
+                        sched.next_level(s, m)
+                    if ends:
+                        for s, f in sched.refill():
+                            start(s, f)
+                        act = sched.active()
+                        t = self._stamp("expansion", t)
+        finally:
+            self.model.decodable = prev
+        return results
 
 
 def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False, device=None, profile=None):

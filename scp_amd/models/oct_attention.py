@@ -341,3 +341,135 @@ class OctAttnStepper:
                                             qoff=t)
             E, pa = self._ffn(lyr, att, E)
         self.t = t + 1
+
+
+class OctAttnBatchStepper(OctAttnStepper):
+    """OctAttnStepper for `slots` independent windows, stepped together: a call takes the slots it serves (`slot_ids`, B of them) and one
+    row per slot - row b is row t[slot_ids[b]] of that slot's window.  Every dense launch is the batched forward's kernel on B rows
+    (they are row-invariant: per-row scales, tile picked by N alone); the attention is the one-row-per-stream kernel
+    (native.octattn_attention_rowinv_step), which reads each row's position and cache slot from device arrays.  So the launch count of
+    a call does not depend on B, no call waits for the device, and the logits row of slot s at row t is bit-identical to that row of
+    OctAttention.forward under the decodable profile whatever the other slots hold or do.
+    State: cache [slots, layers, cs, 1280], the unknown stream's query per layer [slots, D], t int32 [slots] on the device (`t_dev`)
+    with a host mirror (`t`)."""
+
+    def __init__(self, model, slots):
+        model._check_decodable()
+        if not model.decodable:
+            raise native.ScpError("OctAttnBatchStepper: the model runs the default (non-decodable) profile; set model.decodable = True")
+        if slots < 1:
+            raise native.ScpError("OctAttnBatchStepper: at least one slot")
+        self.m = model
+        self.device = next(model.parameters()).device
+        self.cs = model.cfg.model.context_size
+        if self.cs > 1024:
+            raise native.ScpError("OctAttnBatchStepper: windows of at most 1024 rows (the step kernel keeps a row's scores in LDS)")
+        self.D = model.embed_dimension
+        self.slots = int(slots)
+        self.nl = len(model.transformer_encoder.layers)
+        dev = self.device
+        self.kv = torch.zeros((self.slots, self.nl, self.cs, 2 * _KV_OFF), dtype=torch.float32, device=dev)
+        self._kv_rows = self.kv.view(-1, 2 * _KV_OFF)
+        self.q = torch.zeros((self.nl, self.slots, self.D), dtype=torch.float32, device=dev)
+        self.h1max = torch.zeros((self.slots,), dtype=torch.int32, device=dev)
+        self.t_dev = torch.zeros((self.slots,), dtype=torch.int32, device=dev)
+        self.t = [0] * self.slots
+        self._ones = torch.ones((self.slots,), dtype=torch.int32, device=dev)
+        self._ids = {}
+
+    def _slot_ids(self, slot_ids):
+        """slot_ids (a sequence of distinct slot numbers) -> (the tuple, int32 and int64 device tensors).  The tensors are made once per
+        distinct tuple (one small host-to-device copy), so a decoder that serves the same set of slots step after step uploads nothing."""
+        key = tuple(int(s) for s in slot_ids)
+        ent = self._ids.get(key)
+        if ent is None:
+            if not key or len(set(key)) != len(key) or min(key) < 0 or max(key) >= self.slots:
+                raise native.ScpError(f"OctAttnBatchStepper: slot ids {key} are not distinct slots of 0 .. {self.slots - 1}")
+            i64 = torch.tensor(key, dtype=torch.int64, device=self.device)
+            ent = self._ids[key] = (key, i64.to(torch.int32), i64)
+        return ent
+
+    def reset(self, slot_ids, pad):
+        """Start a window in each of the slots (OctAttnStepper.reset)."""
+        key, _, i64 = self._slot_ids(slot_ids)
+        t = 0
+        if pad and self.cs > 1:
+            kv_pad = self.prefill_pad()
+            for s in key:
+                self.kv[s, :, :self.cs - 1].copy_(kv_pad)
+            t = self.cs - 1
+        self.t_dev.index_fill_(0, i64, t)
+        for s in key:
+            self.t[s] = t
+
+    def _embed(self, ctx, pos, ts):
+        # scp_octattn_embed takes row r's position-table row as pe[r % c]: the table rows gathered by t with c = B give every row its own
+        m, B = self.m, ctx.shape[0]
+        ap = m.abs_pos_enc
+        cap = 10 if m.cfg.train.type == "obj" else 12
+        pe = m.transformer_encoder.position_enc.pe.index_select(0, ts)
+        return native.octattn_embed(ctx, pos, B, m.occ_enc.weight, m.level_enc.weight, m.octant_enc.weight, ap.weight, ap.bias, pe, cap,
+                                    m.cfg.model.max_octree_level)
+
+    def _ffn(self, lyr, att, E):
+        B = att.shape[0]
+        h1max = self.h1max[:B]
+        E, p1 = native.layernorm_add(att, E, lyr.norm1.weight, lyr.norm1.bias, 1e-5, planes=True)
+        h1max.zero_()
+        h1 = native.linear_split_f16(p1, _ops._split16(lyr.linear1.weight), lyr.linear1.bias, native.ACT_RELU, None, row_max=h1max)
+        y2 = linear(h1, lyr.linear2.weight, lyr.linear2.bias, residual=E, scales=native.RowScales.from_max(h1max))
+        return native.layernorm_add(y2, None, lyr.norm2.weight, lyr.norm2.bias, 1e-5, planes=True)
+
+    def _rows(self, slot_ids, ctx, pos):
+        ent = self._slot_ids(slot_ids)
+        B = len(ent[0])
+        if ctx.shape != (B, 12) or pos.shape != (B, 4, 3):
+            raise native.ScpError(f"OctAttnBatchStepper: ctx [{B}, 12] and pos [{B}, 4, 3] expected (one row per slot)")
+        return ent + (B,)
+
+    @torch.no_grad()
+    def unknown(self, slot_ids, ctx, pos):
+        """ctx uint8 [B, 12], pos float32 [B, 4, 3]: row b = row t of slot slot_ids[b]'s window -> logits float32 [B, 255]."""
+        key, i32, i64, B = self._rows(slot_ids, ctx, pos)
+        if any(self.t[s] >= self.cs for s in key):
+            raise native.ScpError("OctAttnBatchStepper: a window is full (reset it)")
+        m, D = self.m, self.D
+        E2, pa2 = self._embed(ctx, pos, self.t_dev.index_select(0, i64))
+        E, pa = E2[1], pa2.rows(B, 2 * B)
+        for l, lyr in enumerate(m.transformer_encoder.layers):
+            a = lyr.attn
+            wkv, bkv = self._kv(lyr)
+            kvu = native.linear_split_f16(pa, _ops._split16(wkv), bkv, cfg=1)
+            q = native.linear_split_f16(pa, _ops._split16(a.mlp_query.weight), a.mlp_query.bias, native.ACT_NONE, None)
+            self.q[l].index_copy_(0, i64, q)
+            att = torch.empty((B, D), dtype=torch.float32, device=self.device)
+            native.octattn_attention_rowinv_step(q, self.kv[:, l, :, :D], self.kv[:, l, :, _KV_OFF:_KV_OFF + D], self.t_dev, i32, m.heads,
+                                                 k_u=kvu[:, :D], v_u=kvu[:, _KV_OFF:_KV_OFF + D], out_u=att)
+            E, pa = self._ffn(lyr, att, E)
+        d0 = native.linear_split_f16(pa, _ops._split16(m.decoder0.weight), m.decoder0.bias, native.ACT_RELU)
+        return linear(d0, m.decoder1.weight, m.decoder1.bias)
+
+    @torch.no_grad()
+    def known(self, slot_ids, ctx, pos):
+        """The same rows with their own occupancy decoded (ctx[:, 9]): row b's key | value rows go into row t of ITS slot's cache; the
+        t of every slot served advances by one."""
+        key, i32, i64, B = self._rows(slot_ids, ctx, pos)
+        m, D = self.m, self.D
+        ts = self.t_dev.index_select(0, i64)
+        E2, pa2 = self._embed(ctx, pos, ts)
+        E, pa = E2[0], pa2.rows(0, B)
+        row = i64 * (self.nl * self.cs) + ts                # cache row of (slot, layer 0, t) in the [slots * layers * cs, 1280] view
+        layers = m.transformer_encoder.layers
+        for l, lyr in enumerate(layers):
+            wkv, bkv = self._kv(lyr)
+            kvk = native.linear_split_f16(pa, _ops._split16(wkv), bkv, cfg=1)
+            self._kv_rows.index_copy_(0, row + l * self.cs, kvk)
+            if l == len(layers) - 1:                   # the last layer's known stream feeds nothing
+                break
+            att = torch.empty((B, D), dtype=torch.float32, device=self.device)
+            native.octattn_attention_rowinv_step(self.q[l].index_select(0, i64), self.kv[:, l, :, :D], self.kv[:, l, :, _KV_OFF:_KV_OFF + D],
+                                                 self.t_dev, i32, m.heads, out=att)
+            E, pa = self._ffn(lyr, att, E)
+        self.t_dev.index_add_(0, i64, self._ones[:B])
+        for s in key:
+            self.t[s] += 1

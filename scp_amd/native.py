@@ -122,6 +122,8 @@ def lib():
         "scp_octattn_attention_f16x3": (C.c_int, [_vp, _vp, _vp, _vp, _vp, i64, i32, i32, i32, i32, _vp, _vp, _vp, i64, _vp]),
         "scp_octattn_attention_rowinv": (C.c_int, [_vp, i64, i64, _vp, _vp, i64, i64, _vp, _vp, i64, i64, _vp, _vp, i64, i64, i32, i32, i32, i32, i32,
                                                    i32, _vp]),
+        "scp_octattn_attention_rowinv_step": (C.c_int, [_vp, i64, _vp, _vp, i64, i64, i32, i32, _vp, _vp, i64, _vp, _vp, i64, _vp, _vp, i32, i32, i32,
+                                                        _vp]),
         "scp_decode_expand_octattn": (C.c_int, [_vp, _vp, _vp, _vp, i64, i32, i32, i32, _vp, _vp, _vp, _vp, _vp]),
         "scp_split_weight_bf16": (C.c_int, [_vp, i32, i32, i32, i32, _vp, _vp, _vp]),
         "scp_linear_bf16x3": (C.c_int, [_vp, i64, _vp, _vp, i32, _vp, _vp, i64, _vp, i64, i32, i32, i32, i32, _vp]),
@@ -1441,6 +1443,46 @@ def octattn_attention_rowinv(q_u, k, v, heads, k_u=None, v_u=None, out=None, out
     rc = lib().scp_octattn_attention_rowinv(q_u.data_ptr(), qw, qr, k.data_ptr(), v.data_ptr(), kw, kr, ptr(k_u), ptr(v_u), uw, ur, ptr(out),
                                             ptr(out_u), ow, orr, B, int(q0), int(q1), int(qoff), int(heads), D // heads, _stream())
     _check(rc, "scp_octattn_attention_rowinv")
+    return out, out_u
+
+
+def octattn_attention_rowinv_step(q_u, k, v, t, slot, heads, k_u=None, v_u=None, out=None, out_u=None):
+    """The decodable profile's attention for ONE query row per stream (csrc/octattn_rowinv.hip: scp_octattn_attention_rowinv_step).
+    q_u [S, D]: launch row s is the row stream slot[s] is decoding, row t[slot[s]] of its window; k, v [slots, rows, D]: the known
+    stream's cache (column slices allowed: slot and row strides are passed); t int32 [slots], slot int32 [S]: device tensors, read by
+    the kernel (no position is a launch argument, nothing synchronises).  k_u, v_u, out, out_u [S, D]; out / out_u are written in
+    place, one of them may be None.  Row s has the bits of octattn_attention_rowinv(q0=t, q1=t + 1) on that slot's cache."""
+    if out is None and out_u is None:
+        raise ScpError("octattn_attention_rowinv_step: nothing to compute (out and out_u are None)")
+    if q_u.dim() != 2 or k.dim() != 3 or v.shape != k.shape or k.shape[-1] != q_u.shape[-1]:
+        raise ScpError("octattn_attention_rowinv_step: q_u [S, D] and k, v [slots, rows, D] expected")
+    S, D = q_u.shape
+    for x in (t, slot):
+        if not (x.is_cuda and x.dtype == torch.int32 and x.dim() == 1 and x.is_contiguous()):
+            raise ScpError("octattn_attention_rowinv_step: t and slot are contiguous int32 device tensors")
+    if t.shape[0] != k.shape[0] or slot.shape[0] != S:
+        raise ScpError("octattn_attention_rowinv_step: t has one entry per cache slot, slot one per launch row")
+    if out_u is not None and (k_u is None or v_u is None):
+        raise ScpError("octattn_attention_rowinv_step: out_u needs k_u and v_u")
+    for x in (out, out_u) + ((k_u, v_u) if out_u is not None else ()):
+        if x is not None and (x.dim() != 2 or x.shape[0] < S or x.shape[1] != D):
+            raise ScpError("octattn_attention_rowinv_step: k_u, v_u, out, out_u are [S, D]")
+    _, qr = _win_strides(q_u)
+    kw, kr = _win_strides(k)
+    if _win_strides(v) != (kw, kr):
+        raise ScpError("octattn_attention_rowinv_step: k and v must share their strides")
+    ur = 0
+    if out_u is not None:
+        _, ur = _win_strides(k_u)
+        if _win_strides(v_u)[1] != ur:
+            raise ScpError("octattn_attention_rowinv_step: k_u and v_u must share their row stride")
+    _, orr = _win_strides(out if out is not None else out_u)
+    if out is not None and out_u is not None and _win_strides(out_u)[1] != orr:
+        raise ScpError("octattn_attention_rowinv_step: out and out_u must share their row stride")
+    ptr = lambda x: None if x is None else x.data_ptr()        # strided views: the strides above describe them
+    rc = lib().scp_octattn_attention_rowinv_step(q_u.data_ptr(), qr, k.data_ptr(), v.data_ptr(), kw, kr, k.shape[0], k.shape[1], ptr(k_u), ptr(v_u),
+                                                 ur, ptr(out), ptr(out_u), orr, t.data_ptr(), slot.data_ptr(), S, int(heads), D // heads, _stream())
+    _check(rc, "scp_octattn_attention_rowinv_step")
     return out, out_u
 
 
