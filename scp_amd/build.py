@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libscp_hip.so")
 SOURCES = ["api.cpp", "geom.hip", "sort_u64.hip", "cdf.hip", "rangecoder.cpp", "legacy_octree.cpp",
-           "knn.hip", "edge.hip", "attn.hip", "octattn.hip", "octattn_f16.hip", "octattn_embed.hip", "octattn_rowinv.hip", "gemm.hip", "gemm_split.hip", "rowchain.hip", "fused.hip", "metrics.hip", "plan.hip"]
+           "knn.hip", "edge.hip", "attn.hip", "octattn.hip", "octattn_f16.hip", "octattn_embed.hip", "octattn_rowinv.hip", "gemm.hip", "gemm_split.hip", "rowchain.hip", "lnlin2.hip", "fused.hip", "metrics.hip", "plan.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-fvisibility=hidden", "-x", "hip"]
@@ -24,6 +24,7 @@ if os.environ.get("SCP_KNN_DEFS"):     # experiment builds of csrc/knn.hip (e.g.
     EXTRA["knn.hip"] = EXTRA["knn.hip"] + os.environ["SCP_KNN_DEFS"].split()
 if os.environ.get("SCP_RC_DEFS"):      # experiment builds of csrc/rowchain.hip (e.g. SCP_RC_DEFS="-DRC_WAIT0")
     EXTRA["rowchain.hip"] = os.environ["SCP_RC_DEFS"].split()
+EXTRA["lnlin2.hip"] = EXTRA.get("rowchain.hip", [])     # same arithmetic, same bits: same flags
 
 
 def _stale(target, deps):
