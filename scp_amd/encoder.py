@@ -120,43 +120,179 @@ def _quant_of(infos):
     return [dict(qs=[float(v) for v in i.qs], offset=[float(v) for v in i.offset]) for i in infos]
 
 
-class FrameEncoder:
-    def __init__(self, model, data_type=KITTI, lidar_level=12, spher=True, cylin=False, mullevel=False, max_batch=8,
-                 device=None, packed=True, max_tokens=1_000_000, host_transform=None, profile=None):
+def _as_tensor(x, dtype):
+    """numpy array -> host tensor of `dtype` (a view when the array has that type already); a tensor is left as it is."""
+    return torch.from_numpy(np.ascontiguousarray(x, dtype)) if isinstance(x, np.ndarray) else x
+
+
+def _upload_ints(hq, device):
+    """One frame's host integers (per-shell clouds, `host_ints`) -> the per-shell device clouds.  Clouds that are views of one pinned
+    buffer (`hq.packed`) go over in ONE asynchronous copy and come back as views of its device image (`.packed`: no concatenation
+    kernel either).  The copy is made from the PINNED TENSOR itself, never from a numpy view of it: torch's host allocator records the
+    stream use of a tensor it knows, so the block is not handed to the next frame's host_ints while this copy still reads it (a
+    from_numpy view of the same memory is invisible to the allocator: the next frame's integers could overwrite this frame's in flight)."""
+    packed = getattr(hq, "packed", None)
+    if packed is None:       # plain per-shell arrays computed elsewhere: pageable memory, synchronous copies
+        return [_as_tensor(q, np.int32).to(device) for q in hq]
+    qcat = packed.to(device, non_blocking=True)
+    qs, a = _PackedInts(), 0
+    for q in hq:
+        qs.append(qcat[a:a + q.shape[0]])
+        a += q.shape[0]
+    qs.packed = qcat
+    return qs
+
+
+def _result(stream, meta, times, debug=None):
+    """The dict every entry point of both encoders returns: the coded stream and its size, the frame's `meta` fields (what the reference
+    prints, what its file names and the side-info file carry), the wall times; `_debug` (device tensors) from the synchronous calls only."""
+    bits = 8 * len(stream)
+    res = dict(bytes=stream, bits=bits, bpp=bits / meta["n_points"], times=times, **meta)
+    if debug is not None:
+        res["_debug"] = debug
+    return res
+
+
+class _CoderPipeline:
+    """The asynchronous tail of a frame, shared by both encoders' `*_async` calls: the model part of consecutive frames on alternating
+    streams (lanes), the (c_low, c_high) pairs D2H on a copy stream, the serial host range coder on a worker thread (ctypes releases the
+    GIL) - so the caller can enqueue the next frame while this one is being coded.  Created at an encoder's first asynchronous call."""
+
+    def __init__(self, device, lanes_env):
+        self.pool = ThreadPoolExecutor(max_workers=2)
+        self.copy_stream = torch.cuda.Stream(device=device)
+        # the front part of a frame (stage G with its small D2H syncs, the window plans) is launch-bound: on a side stream the syncs wait
+        # for stage G only, not for the previous frames' model kernels queued on a lane; high priority: its tiny kernels slip in between
+        # the model's
+        self.front_stream = torch.cuda.Stream(device=device, priority=-1)
+        # Lanes: consecutive frames run their model part on alternating streams, so the launch gaps and tails of one frame's
+        # kernels are filled by the other's (the kernels are whole-GPU persistent launches: they interleave rather than
+        # co-run).  One lane keeps every frame on the caller's stream.  Two lanes, with four frames in flight, measured on OctAttention:
+        # 56.3 against 47.8 frames/s at L12, 23.1 against 21.0 at L14; three lanes: no better.
+        self.lanes = [torch.cuda.Stream(device=device) for _ in range(max(1, int(os.environ.get(lanes_env, "2"))))]
+        self._lane_i = 0
+
+    def lane(self, caller):
+        """The stream of this frame's model part, ordered behind whatever the caller's stream holds now."""
+        if len(self.lanes) == 1:
+            return caller
+        main = self.lanes[self._lane_i % len(self.lanes)]
+        self._lane_i += 1
+        main.wait_stream(caller)
+        return main
+
+    def submit(self, main, lohi, fills0, cuts=None):
+        """lohi: the frame's pairs, enqueued on `main` (the last thing of its model part).  -> future of the coded stream, or - cuts: row
+        bounds of the frames of a batch - of the list of every frame's own stream.  fills0: native.CACHE_FILLS before the frame began."""
+        done = torch.cuda.Event()
+        done.record(main)
+        if native.CACHE_FILLS != fills0:               # device-side caches were built during this call (first frames only):
+            main.synchronize()                         # finish them before anything is enqueued on another lane
+        host = torch.empty(lohi.shape, dtype=lohi.dtype, pin_memory=True)     # one per call: the worker reads it after this returns
+        with torch.cuda.stream(self.copy_stream):
+            self.copy_stream.wait_event(done)
+            host.copy_(lohi, non_blocking=True)
+            lohi.record_stream(self.copy_stream)
+            copied = torch.cuda.Event(blocking=True)      # the coder thread SLEEPS until the pairs have landed (a default event spins a core)
+            copied.record()
+
+        def work():
+            _wait_event(copied)
+            h = host.numpy()
+            if cuts is None:
+                return native.ac_encode_lohi(h)
+            return [native.ac_encode_lohi(h[a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
+
+        return self.pool.submit(work)
+
+
+class _FrontEnd:
+    """What both encoders do alike in front of their models: the quantiser's parameters per rho shell, stage G's segment list, the
+    device quantiser, and the lazily created coding pipeline of the asynchronous calls."""
+    LANES_ENV = None                      # the environment variable that sets the number of lanes (read at the first asynchronous call)
+
+    def __init__(self, model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform):
         self.model = model
-        self.profile = profile          # native.NumericProfile of THIS encoder (None: the process default); current around every launch
         # strict-identity switch (CLI --host_transform, SCP_XFORM=numpy): the float -> integer step of the reference on the host
         # (numpy float32 arctan2 / arccos, data_preprocess.py:42-70) instead of the device transform, whose float64 atan2 / acos is
         # more accurate and therefore gives other integers for a few points per frame (DESIGN.md 2.1).  Everything after the
         # integers is bit-exact on the device either way.
         self.host_transform = (os.environ.get("SCP_XFORM", "") == "numpy") if host_transform is None else bool(host_transform)
-        self.packed = packed            # one packed forward for all windows (default) vs one forward per group of equal windows
-        self.max_tokens = max_tokens
         self.data_type = data_type
         self.lidar_level = lidar_level
         self.mode = native.CYLIN if cylin else (native.SPHER if spher else native.CART)
         self.spher, self.cylin = spher and not cylin, cylin
         self.mullevel = mullevel
-        if mullevel and self.mode == native.CART:
-            # encode_dataset_ehem_mullevel.py:97-186 has a cylindrical and a spherical branch only
-            raise native.ScpError("--mullevel needs --spher or --cylin (the reference has no Cartesian multi-level path)")
         self.max_batch = max_batch
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.context_size = model.cfg.model.context_size
         self.geom = native.Geom()
         self.cart_offset = -200.0 if data_type == KITTI else -float(2 ** 17)
+        self._infos = []                      # the last quantiser call's per-shell info (quant_info)
+        self._pipe = None
 
-    # ------------------------------------------------------------------------------------------ stage G
     def shells(self):
         L = self.lidar_level
         return [([0, 0], L), ([0, 1], L + 1), ([1], L + 2)] if self.mullevel else [(None, L)]
 
+    def _quant_args(self):
+        """(quantisation step of every shell, Cartesian offset): the arguments of every quantiser, host or device."""
+        return [level_qs(self.data_type, lv) for _, lv in self.shells()], 0.0 if self.mullevel else self.cart_offset
+
+    def _segments(self, clouds):
+        """Geom.build's segment list [(offset, count, path, mullevel)] for integer clouds that lie back to back in one buffer: one frame's
+        shells, or those of several frames, frame after frame."""
+        paths = [path for path, _ in self.shells()]
+        segs, off = [], 0
+        for k, q in enumerate(clouds):
+            segs.append((off, q.shape[0], paths[k % len(paths)], self.mullevel))
+            off += q.shape[0]
+        return segs
+
+    def _build_xyz(self, frames):
+        """Device transform: stage G1 + G2 of the frames as ONE launch sequence (scp_geom_build_xyz: every point transformed once, keys
+        for all shells and the sort's first histogram out of one kernel, two host read-backs) -> the info of every (frame, shell)."""
+        return self.geom.build_xyz(list(frames), self.mode, *self._quant_args(), [(path, self.mullevel) for path, _ in self.shells()])
+
+    def _quantize_device(self, xyz_dev):
+        """The device quantiser, shell by shell -> per-shell integer clouds (device int32 [P,3]); their infos in `_infos`."""
+        qs, offset = self._quant_args()
+        out = [native.quantize(xyz_dev, self.mode, q, offset) for q in qs]
+        self._infos = [o[1] for o in out]
+        return [o[0] for o in out]
+
+    def quant_info(self):
+        """Per shell the (qs[3], offset[3]) the last quantiser call made its integers with - the cylindrical z offset (the frame's z
+        minimum) included: what a decoder needs to de-quantise (OctAttnFrameEncoder.encode_ints(..., quant=))."""
+        return _quant_of(self._infos)
+
+    def _pipeline(self):
+        if self._pipe is None:
+            self._pipe = _CoderPipeline(self.device, self.LANES_ENV)
+        return self._pipe
+
+
+class FrameEncoder(_FrontEnd):
+    LANES_ENV = "SCP_LANES"
+
+    def __init__(self, model, data_type=KITTI, lidar_level=12, spher=True, cylin=False, mullevel=False, max_batch=8,
+                 device=None, packed=True, max_tokens=1_000_000, host_transform=None, profile=None):
+        if mullevel and not (spher or cylin):
+            # encode_dataset_ehem_mullevel.py:97-186 has a cylindrical and a spherical branch only
+            raise native.ScpError("--mullevel needs --spher or --cylin (the reference has no Cartesian multi-level path)")
+        super().__init__(model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform)
+        self.profile = profile          # native.NumericProfile of THIS encoder (None: the process default); current around every launch
+        self.packed = packed            # one packed forward for all windows (default) vs one forward per group of equal windows
+        self.max_tokens = max_tokens
+        self._front_pool = None         # front_async's one thread
+
+    # ------------------------------------------------------------------------------------------ stage G
     def host_ints(self, xyz):
         """The strict-identity front end: numpy [P,>=3] float32 -> (per-shell int32 arrays, infos) exactly as the reference computes
         them (scp_amd/data_preproc/data_preprocess.py: host_quantize).  Runs on the host; the CLI calls it on its reader thread."""
         from .data_preproc.data_preprocess import host_quantize_shells
         xyz = np.ascontiguousarray(xyz.cpu().numpy() if isinstance(xyz, torch.Tensor) else xyz, np.float32)
-        out = host_quantize_shells(xyz, self.mode, [level_qs(self.data_type, lv) for _, lv in self.shells()], 0.0 if self.mullevel else self.cart_offset)
+        out = host_quantize_shells(xyz, self.mode, *self._quant_args())
         # the shells' integers back to back in ONE pinned buffer (this runs on the reader / prefetch thread): the launch thread then issues a
         # single asynchronous host -> device copy and no concatenation kernel; the list holds numpy views of the buffer
         n = [q.shape[0] for q, _ in out]
@@ -173,27 +309,12 @@ class FrameEncoder:
     def quantize(self, xyz_dev, ints=None):
         """xyz -> list of per-shell integer clouds (device int32 [P,3]) + (bin_num, z_offset)."""
         if self.host_transform or ints is not None:
-            hq, infos = ints if ints is not None else self.host_ints(xyz_dev)
-            self._infos = infos
-            packed = getattr(hq, "packed", None)
-            if packed is not None:       # one pinned buffer -> one async copy; the per-shell clouds are views of it
-                qcat = packed.to(self.device, non_blocking=True)
-                qs, a = _PackedInts(), 0
-                for q in hq:
-                    qs.append(qcat[a:a + q.shape[0]])
-                    a += q.shape[0]
-                qs.packed = qcat
-            else:
-                qs = [torch.from_numpy(np.ascontiguousarray(q, np.int32)).to(self.device, non_blocking=True) for q in hq]
-            return qs, infos[0].bin_num, (infos[0].offset[2] if self.cylin else 0.0)
-        qs, infos = [], []
-        for path, lv in self.shells():
-            q, qi, _ = native.quantize(xyz_dev, self.mode, level_qs(self.data_type, lv),
-                                       0.0 if self.mullevel else self.cart_offset)
-            qs.append(q)
-            infos.append(qi)
-        self._infos = infos
-        return qs, infos[0].bin_num, (infos[0].offset[2] if self.cylin else 0.0)
+            hq, self._infos = ints if ints is not None else self.host_ints(xyz_dev)
+            qs = _upload_ints(hq, self.device)
+        else:
+            qs = self._quantize_device(xyz_dev)
+        first = self._infos[0]
+        return qs, first.bin_num, (first.offset[2] if self.cylin else 0.0)
 
     def distortion(self, xyz_dev, infos=None):
         """Chamfer distance and D1 PSNR of the frame just encoded (the octree of the last `encode` / `preprocess` call) against
@@ -208,16 +329,13 @@ class FrameEncoder:
 
     def preprocess(self, xyz_dev, ints=None):
         if ints is None and not self.host_transform:
-            # device transform: stage G1 + G2 as ONE launch sequence (scp_geom_build_xyz: every point transformed once, keys for all
-            # shells and the sort's first histogram out of one kernel, two host read-backs per frame)
-            self._infos = self.geom.build_xyz([xyz_dev], self.mode, [level_qs(self.data_type, lv) for _, lv in self.shells()],
-                                              0.0 if self.mullevel else self.cart_offset, [(path, self.mullevel) for path, _ in self.shells()])
+            self._infos = self._build_xyz([xyz_dev])
             pre = self._tables(self._infos[0].bin_num, self._infos[0].offset[2] if self.cylin else 0.0, xyz_dev.shape[0])
         else:
             qs, bin_num, z_off = self.quantize(xyz_dev, ints)
             pre = self.preprocess_ints(qs, bin_num, z_off, xyz_dev.shape[0])
         pre["bin_nums"] = [float(i.bin_num) for i in self._infos]      # every shell's own (the file name carries the first)
-        pre["quant"] = _quant_of(self._infos)                          # the steps and offsets the integers were made with (sidecar)
+        pre["quant"] = self.quant_info()                               # the steps and offsets the integers were made with (sidecar)
         return pre
 
     def _tables(self, bin_num, z_offset, n_points):
@@ -237,11 +355,7 @@ class FrameEncoder:
         (the reference's --preproc_path flow).  -> ctx/pos/sym device tensors for all shells, level sizes, meta."""
         packed = getattr(qs, "packed", None)
         q = packed if packed is not None else (torch.cat(qs) if len(qs) > 1 else qs[0])
-        segs, off = [], 0
-        for (path, _), qq in zip(self.shells(), qs):
-            segs.append((off, qq.shape[0], path, self.mullevel))
-            off += qq.shape[0]
-        self.geom.build(q.contiguous(), segs)
+        self.geom.build(q.contiguous(), self._segments(qs))
         return self._tables(bin_num, z_offset, n_points)
 
     def preprocess_records(self, records, bin_num, z_offset, n_points):
@@ -326,8 +440,7 @@ class FrameEncoder:
         """xyz: numpy / torch float32 [P,3].  Returns dict(bytes, bits, bpp, n_nodes, n_points, bin_num, z_offset,
         n_levels, pos_mm (numpy [n_levels,2]), times)."""
         t0 = time.perf_counter()
-        if isinstance(xyz, np.ndarray):
-            xyz = torch.from_numpy(np.ascontiguousarray(xyz, np.float32))
+        xyz = _as_tensor(xyz, np.float32)
         ints = self.host_ints(xyz) if self.host_transform else None        # from the caller's copy (no D2H of a frame just uploaded)
         xyz_dev = xyz.to(self.device, non_blocking=True)
         return self._encode_pre(self.preprocess(xyz_dev, ints), t0, timing)
@@ -335,42 +448,30 @@ class FrameEncoder:
     def encode_ints(self, qs, bin_num, z_offset, n_points, timing=False):
         """Encode from already-quantised integer coordinates (list of per-shell int32 [P_s,3] arrays / tensors)."""
         t0 = time.perf_counter()
-        dq = [(torch.from_numpy(np.ascontiguousarray(q, np.int32)) if isinstance(q, np.ndarray) else q).to(self.device)
-              for q in qs]
+        dq = [_as_tensor(q, np.int32).to(self.device) for q in qs]
         return self._encode_pre(self.preprocess_ints(dq, bin_num, z_offset, n_points), t0, timing)
 
     # ------------------------------------------------------------------------------------------ pipelined variant
-    def _init_streams(self):
-        if hasattr(self, "_pool"):
-            return
-        self._pool = ThreadPoolExecutor(max_workers=2)
-        self._front_pool = ThreadPoolExecutor(max_workers=1)     # front_async: stage G + plans of the next frame (see there)
-        self._copy_stream = torch.cuda.Stream(device=self.device)
-        self._front_stream = torch.cuda.Stream(device=self.device, priority=-1)   # high priority: its tiny kernels slip in between the model's
-        # Lanes: consecutive frames run their model part on alternating streams, so the launch gaps and tails of one frame's
-        # kernels are filled by the other's (the kernels are whole-GPU persistent launches: they interleave rather than
-        # co-run).  SCP_LANES=1 keeps every frame on the caller's stream.
-        self._lanes = [torch.cuda.Stream(device=self.device) for _ in range(max(1, int(os.environ.get("SCP_LANES", "2"))))]
-        self._lane_i = 0
-
-    def _front(self, xyz, ints, caller):
-        """Stage G and the window plans of one frame on the front stream (a side stream: launch-bound work with two small D2H syncs, which
-        runs under the previous frames' model kernels).  -> everything the model part needs + the event it waits for."""
+    def _front(self, xyz, ints, caller, batch=False):
+        """Stage G and the window plans of one frame - batch: of a list of frames as ONE sequence of levels (preprocess_batch) - on the
+        front stream (a side stream: launch-bound work with two small D2H syncs, which runs under the previous frames' model kernels
+        instead of in front of this frame's).  -> everything the model part needs + the event it waits for."""
         torch.cuda.set_device(self.device)                     # (the current device is per host thread: this may be the front thread)
-        if isinstance(xyz, np.ndarray):
-            xyz = torch.from_numpy(np.ascontiguousarray(xyz, np.float32))
-        if self.host_transform and ints is None:
-            ints = self.host_ints(xyz)
-        with torch.cuda.stream(self._front_stream):
-            self._front_stream.wait_stream(caller)             # whatever produced `xyz` on the caller's stream
-            pre = self.preprocess(xyz.to(self.device, non_blocking=True), ints)
+        frames = [_as_tensor(x, np.float32) for x in (xyz if batch else [xyz])]
+        if self.host_transform and ints is None and not batch:
+            ints = self.host_ints(frames[0])                   # from the caller's copy (no D2H of a frame just uploaded)
+        front_stream = self._pipeline().front_stream
+        with torch.cuda.stream(front_stream):
+            front_stream.wait_stream(caller)                   # whatever produced `xyz` on the caller's stream
+            dev_frames = [x.to(self.device, non_blocking=True) for x in frames]
+            pre, metas = self.preprocess_batch(dev_frames, ints) if batch else (self.preprocess(dev_frames[0], ints), None)
             plan = EncodePlan(pre["level_sizes"], self.context_size)
             if self.packed:
                 pre["packed_plans"] = self.packed_plans(plan)
             sym_coded = self._sym_coded(pre, plan)
             ready = torch.cuda.Event()
             ready.record()
-        return dict(pre=pre, plan=plan, sym_coded=sym_coded, ready=ready)
+        return dict(pre=pre, metas=metas, plan=plan, sym_coded=sym_coded, ready=ready, dev_frames=dev_frames)
 
     def front_async(self, xyz, ints=None):
         """Start a frame's front part (stage G, plans) on the encoder's FRONT THREAD and return a future for `encode_async(..., front=)`.
@@ -378,54 +479,33 @@ class FrameEncoder:
         whole-GPU model kernels of the frames in flight (33 - 43 ms per frame in `bench.py`, against 0.4 ms alone on the GPU) - so a loop that
         calls this one frame ahead keeps the launch thread free for the model part (ctypes and torch release the GIL while they wait).
         Call order = frame order: the front thread takes the frames one at a time (one `scp_geom` handle)."""
-        self._init_streams()
+        self._pipeline()
+        if self._front_pool is None:
+            self._front_pool = ThreadPoolExecutor(max_workers=1)
         caller = torch.cuda.current_stream(self.device)
         return self._front_pool.submit(self._front, xyz, ints, caller)
 
+    def _model_async(self, front, main, fills0, t0, cuts=None):
+        """The model part and the CDF launch of a front part on the lane `main`, the range coder behind them -> the handle.  The handle
+        keeps the front part (everything allocated on the front stream: frames, tables, plans), the logits table and the pairs referenced
+        until finish(), i.e. past their last use on `main`, so the caching allocator cannot hand them out again early."""
+        main.wait_event(front["ready"])
+        with torch.cuda.stream(main):
+            table = self.logits_in_coding_order(front["pre"], front["plan"])
+            lohi = native.softmax_cdf(table, front["sym_coded"])["lohi"]
+        return dict(future=self._pipeline().submit(main, lohi, fills0, cuts), t0=t0, front=front, keep=(table, lohi))
+
     def encode_async(self, xyz, ints=None, front=None):
-        """Like encode(), but the D2H copy of the (c_low, c_high) pairs and the serial host range coder run on a worker
-        thread (ctypes releases the GIL) behind an event on a side stream, so the caller can enqueue the next frame while this
-        one is being coded.  Returns a handle; `finish(handle)` blocks and returns the usual result dict.
+        """Like encode(), but the front part runs on the front stream, the model part on the next lane, and the D2H copy of the
+        (c_low, c_high) pairs and the serial host range coder on a worker thread (_CoderPipeline), so the caller can enqueue the next
+        frame while this one is being coded.  Returns a handle; `finish(handle)` blocks and returns the usual result dict.
         ints: the result of `host_ints(xyz)` when the caller has already computed it (strict-identity mode, CLI reader thread).
         front: the future `front_async(xyz, ints)` returned for this frame (then xyz / ints are not looked at again)."""
         t0 = time.perf_counter()
-        self._init_streams()
-        # Front part on its own stream: stage G (with its small D2H syncs) and the window plans (one plan_kernel launch per chunk)
-        # are launch-bound; on a side stream they run under the previous frame's model kernels instead of in front of this
-        # frame's.  Everything allocated there stays referenced by the handle until finish(), i.e. past its last use on the
-        # main stream, so the caching allocator cannot hand it out again early.
         caller = torch.cuda.current_stream(self.device)
-        if len(self._lanes) > 1:
-            main = self._lanes[self._lane_i % len(self._lanes)]
-            self._lane_i += 1
-            main.wait_stream(caller)
-        else:
-            main = caller
+        main = self._pipeline().lane(caller)
         fills0 = native.CACHE_FILLS
-        f = front.result() if front is not None else self._front(xyz, ints, caller)
-        pre, plan, sym_coded, ready = f["pre"], f["plan"], f["sym_coded"], f["ready"]
-        main.wait_event(ready)
-        with torch.cuda.stream(main):
-            table = self.logits_in_coding_order(pre, plan)
-            lohi = native.softmax_cdf(table, sym_coded)["lohi"]
-            done = torch.cuda.Event()
-            done.record()
-            if native.CACHE_FILLS != fills0:               # device-side caches were built during this call (first frames only):
-                main.synchronize()                         # finish them before anything is enqueued on another lane
-        host = torch.empty(lohi.shape, dtype=lohi.dtype, pin_memory=True)
-        with torch.cuda.stream(self._copy_stream):
-            self._copy_stream.wait_event(done)
-            host.copy_(lohi, non_blocking=True)
-            lohi.record_stream(self._copy_stream)
-            copied = torch.cuda.Event(blocking=True)      # the coder thread SLEEPS until the pairs have landed (a default event spins a core)
-            copied.record()
-
-        def work():
-            _wait_event(copied)
-            return native.ac_encode_lohi(host.numpy())
-
-        fut = self._pool.submit(work)
-        return dict(future=fut, pre=pre, plan=plan, t0=t0, keep=(sym_coded, table, lohi))
+        return self._model_async(front.result() if front is not None else self._front(xyz, ints, caller), main, fills0, t0)
 
     # ------------------------------------------------------------------------------------------ batches of small frames
     def preprocess_batch(self, frames, ints=None):
@@ -441,27 +521,11 @@ class FrameEncoder:
             qs_all, infos = [], []
             for f, xyz_dev in enumerate(frames):
                 hq, inf = ints[f] if ints is not None else self.host_ints(xyz_dev)
-                # copy from the PINNED TENSOR itself, as quantize() does: torch's host allocator records the stream use of a tensor it knows,
-                # so the block is not handed to the next frame's host_ints while this asynchronous copy still reads it (a from_numpy view of
-                # the same memory is invisible to the allocator: the next frame's integers could overwrite an earlier frame's in flight)
-                packed = getattr(hq, "packed", None)
-                if packed is not None:
-                    qcat, a = packed.to(self.device, non_blocking=True), 0
-                    for q in hq:
-                        qs_all.append(qcat[a:a + q.shape[0]])
-                        a += q.shape[0]
-                else:      # plain per-shell arrays computed elsewhere (as quantize() accepts them): pageable memory, synchronous copies
-                    qs_all += [torch.from_numpy(np.ascontiguousarray(q, np.int32)).to(self.device) for q in hq]
+                qs_all += _upload_ints(hq, self.device)
                 infos += inf
-            segs, off = [], 0
-            for f in range(len(frames)):
-                for (path, _), qq in zip(self.shells(), qs_all[f * ns:(f + 1) * ns]):
-                    segs.append((off, qq.shape[0], path, self.mullevel))
-                    off += qq.shape[0]
-            self.geom.build(torch.cat(qs_all).contiguous(), segs)
+            self.geom.build(torch.cat(qs_all).contiguous(), self._segments(qs_all))
         else:
-            infos = self.geom.build_xyz(list(frames), self.mode, [level_qs(self.data_type, lv) for _, lv in self.shells()],
-                                        0.0 if self.mullevel else self.cart_offset, [(path, self.mullevel) for path, _ in self.shells()])
+            infos = self._build_xyz(frames)
         self._infos = infos[-ns:]
         pre = self._tables(infos[0].bin_num, 0.0, 0)
         metas, sizes, mm0 = [], pre["level_sizes"], 0
@@ -478,53 +542,16 @@ class FrameEncoder:
 
     def encode_batch_async(self, frames, ints=None):
         """k frames through ONE stage G, ONE packed forward and ONE CDF launch (the small-frame configurations: a level-12 frame has
-        22 windows, far too few for an MI355X - BASELINE.json configs[1] is a batch of 16 of them).  The streams are byte-identical
-        to the per-frame path (every kernel is per window / per row).  Returns a handle for finish_batch().
+        22 windows, far too few for an MI355X - BASELINE.json configs[1] is a batch of 16 of them), on the same streams as encode_async.
+        The streams are byte-identical to the per-frame path (every kernel is per window / per row).  Returns a handle for finish_batch().
         ints: [host_ints(frame) for every frame] when the caller has them already (strict-identity mode)."""
         t0 = time.perf_counter()
-        self._init_streams()
-        # the same stream structure as encode_async: stage G + plans on the high-priority front stream, the model part on the next lane
         caller = torch.cuda.current_stream(self.device)
-        if len(self._lanes) > 1:
-            main = self._lanes[self._lane_i % len(self._lanes)]
-            self._lane_i += 1
-            main.wait_stream(caller)
-        else:
-            main = caller
+        main = self._pipeline().lane(caller)
         fills0 = native.CACHE_FILLS
-        with torch.cuda.stream(self._front_stream):
-            self._front_stream.wait_stream(caller)
-            dev_frames = [(torch.from_numpy(np.ascontiguousarray(x, np.float32)) if isinstance(x, np.ndarray) else x).to(self.device, non_blocking=True)
-                          for x in frames]
-            pre, metas = self.preprocess_batch(dev_frames, ints)
-            plan = EncodePlan(pre["level_sizes"], self.context_size)
-            if self.packed:
-                pre["packed_plans"] = self.packed_plans(plan)
-            sym_coded = self._sym_coded(pre, plan)
-            ready = torch.cuda.Event()
-            ready.record()
-        main.wait_event(ready)
-        with torch.cuda.stream(main):
-            table = self.logits_in_coding_order(pre, plan)
-            lohi = native.softmax_cdf(table, sym_coded)["lohi"]
-            done = torch.cuda.Event()
-            done.record()
-            if native.CACHE_FILLS != fills0:
-                main.synchronize()
-        host = torch.empty(lohi.shape, dtype=lohi.dtype, pin_memory=True)
-        with torch.cuda.stream(self._copy_stream):
-            self._copy_stream.wait_event(done)
-            host.copy_(lohi, non_blocking=True)
-            lohi.record_stream(self._copy_stream)
-            copied = torch.cuda.Event(blocking=True)      # the coder thread SLEEPS until the pairs have landed (a default event spins a core)
-            copied.record()
-        cuts = np.concatenate(([0], np.cumsum([m["n_nodes"] for m in metas])))
-
-        def work():
-            _wait_event(copied)
-            h = host.numpy()
-            return [native.ac_encode_lohi(h[cuts[f]:cuts[f + 1]]) for f in range(len(metas))]
-        return dict(future=self._pool.submit(work), metas=metas, t0=t0, keep=(pre, plan, sym_coded, table, lohi, dev_frames))
+        front = self._front(frames, ints, caller, batch=True)
+        cuts = np.concatenate(([0], np.cumsum([m["n_nodes"] for m in front["metas"]])))
+        return self._model_async(front, main, fills0, t0, cuts)
 
     def _sym_coded(self, pre, plan):
         """The coded symbols in coding order: written by the context kernel itself (scp_geom_context_ehem_all), or - for tables that
@@ -533,23 +560,21 @@ class FrameEncoder:
             return pre["sym_coded"]
         return pre["sym"][plan.coding_order_device(self.device)].contiguous()
 
+    @staticmethod
+    def _meta(pre, n_nodes):
+        """The result fields of one frame out of its `pre` (preprocess*), or out of its entry of preprocess_batch's per-frame list."""
+        return dict(n_nodes=n_nodes, n_points=pre["n_points"], bin_num=pre["bin_num"], z_offset=pre["z_offset"], n_levels=len(pre["level_sizes"]),
+                    pos_mm=pre["pos_mm"].cpu().numpy(), level_sizes=pre["level_sizes"], bin_nums=pre.get("bin_nums", [float(pre["bin_num"])]),
+                    quant=pre.get("quant"))
+
     def finish_batch(self, h):
-        out = []
-        for stream, m in zip(h["future"].result(), h["metas"]):
-            bits = 8 * len(stream)
-            out.append(dict(bytes=stream, bits=bits, bpp=bits / m["n_points"], n_nodes=m["n_nodes"], n_points=m["n_points"], bin_num=m["bin_num"],
-                            z_offset=m["z_offset"], n_levels=len(m["level_sizes"]), pos_mm=m["pos_mm"].cpu().numpy(), level_sizes=m["level_sizes"],
-                            bin_nums=m["bin_nums"], quant=m.get("quant"), times=dict(total=(time.perf_counter() - h["t0"]) / len(h["metas"]))))
-        return out
+        metas = h["front"]["metas"]
+        return [_result(stream, self._meta(m, m["n_nodes"]), dict(total=(time.perf_counter() - h["t0"]) / len(metas)))
+                for stream, m in zip(h["future"].result(), metas)]
 
     def finish(self, h):
         stream = h["future"].result()
-        pre, plan = h["pre"], h["plan"]
-        bits = 8 * len(stream)
-        return dict(bytes=stream, bits=bits, bpp=bits / pre["n_points"], n_nodes=plan.n_rows, n_points=pre["n_points"],
-                    bin_num=pre["bin_num"], z_offset=pre["z_offset"], n_levels=len(pre["level_sizes"]),
-                    pos_mm=pre["pos_mm"].cpu().numpy(), level_sizes=pre["level_sizes"], bin_nums=pre.get("bin_nums", [float(pre["bin_num"])]),
-                    quant=pre.get("quant"), times=dict(total=time.perf_counter() - h["t0"]))
+        return _result(stream, self._meta(h["front"]["pre"], h["front"]["plan"].n_rows), dict(total=time.perf_counter() - h["t0"]))
 
     def _encode_pre(self, pre, t0, timing):
         if timing:
@@ -565,12 +590,8 @@ class FrameEncoder:
         t3 = time.perf_counter()
         stream = native.ac_encode_lohi(lohi)
         t4 = time.perf_counter()
-        bits = 8 * len(stream)
-        return dict(bytes=stream, bits=bits, bpp=bits / pre["n_points"], n_nodes=plan.n_rows, n_points=pre["n_points"],
-                    bin_num=pre["bin_num"], z_offset=pre["z_offset"], n_levels=len(pre["level_sizes"]),
-                    pos_mm=pre["pos_mm"].cpu().numpy(), level_sizes=pre["level_sizes"], bin_nums=pre.get("bin_nums", [float(pre["bin_num"])]),
-                    quant=pre.get("quant"), times=dict(geom=t1 - t0, model=t2 - t1, cdf=t3 - t2, coder=t4 - t3, total=t4 - t0),
-                    _debug=dict(table=table, sym_coded=sym_coded, pre=pre))
+        return _result(stream, self._meta(pre, plan.n_rows), dict(geom=t1 - t0, model=t2 - t1, cdf=t3 - t2, coder=t4 - t3, total=t4 - t0),
+                       debug=dict(table=table, sym_coded=sym_coded, pre=pre))
 
     def outfile(self, base, res):
         """encode.py:140-144 file name."""
@@ -581,7 +602,7 @@ class FrameEncoder:
         return base + "_" + str(res["n_levels"]) + "_" + str(int(res["bin_num"])) + "_" + str(int(res["z_offset"])) + ".bin"
 
 
-class OctAttnFrameEncoder:
+class OctAttnFrameEncoder(_FrontEnd):
     """OctAttention path.  Same-level (encode.py:23-82 `compress` + dataloaders/encode_dataset.py:32-55): one BFS sequence,
     front-padded with context_size-1 rows (occ 255), cut into consecutive 1024-windows; node r is predicted at position
     (r+1023) % 1024 of window (r+1023) // 1024.  Plain BFS coding order.  `--cylin` is wired here (the reference forgot to, SURVEY B-7).
@@ -592,63 +613,38 @@ class OctAttnFrameEncoder:
     its own, positions divided by 2^(the shell's deepest level); the PMF rows of the chunks are stacked in order
     (`probabilities[:-1023]`) and coded as one stream.  File name `<base>[_spher]_<chunks>_<bin_num>_0.bin`."""
 
+    LANES_ENV = "SCP_LANES_OCTATTN"
+
     def __init__(self, model, data_type=KITTI, lidar_level=12, spher=True, cylin=False, max_batch=128, device=None, mullevel=False,
                  level_wise=False, named=False, host_transform=None, decodable=False):
-        self.model = model
         # decodable=True: the octattn/1d numeric profile (models/oct_attention.py) - every PMF row a function of its own window's rows
         # 0..t, so OctAttnFrameDecoder can reproduce it node by node; the default (octattn/1) keeps the round-6 bits
         self.decodable = bool(decodable)
         if self.decodable and mullevel:
             raise native.ScpError("--decodable: multi-level OctAttention streams (three shells) have no decoder; encode with encode.py")
-        self.host_transform = (os.environ.get("SCP_XFORM", "") == "numpy") if host_transform is None else bool(host_transform)   # see FrameEncoder
-        self.data_type = data_type
-        self.lidar_level = lidar_level
-        self.mode = native.CYLIN if cylin else (native.SPHER if spher else native.CART)
-        self.spher, self.cylin = spher and not cylin, cylin
-        self.mullevel = mullevel
-        self.level_wise = level_wise
-        self.named = named or mullevel        # encode_mullevel.py's file-name scheme (also for its single-shell Cartesian input)
-        if mullevel and self.mode != native.SPHER:
+        if mullevel and (cylin or not spher):
             # encode_dataset_mullevel.py:76-86: the three-shell records exist for --spher only
             raise native.ScpError("OctAttention multi-level encoding needs --spher (encode_dataset_mullevel.py:76)")
-        self.max_batch = max_batch
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        self.context_size = model.cfg.model.context_size
-        self.geom = native.Geom()
-        self.cart_offset = -200.0 if data_type == KITTI else -float(2 ** 17)
-        self._infos = []                      # the last quantiser call's per-shell info (quant_info)
-
-    def shells(self):
-        L = self.lidar_level
-        return [([0, 0], L), ([0, 1], L + 1), ([1], L + 2)] if self.mullevel else [(None, L)]
+        super().__init__(model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform)
+        self.level_wise = level_wise
+        self.named = named or mullevel        # encode_mullevel.py's file-name scheme (also for its single-shell Cartesian input)
 
     def quantize(self, xyz_dev):
         if self.host_transform:
             from .data_preproc.data_preprocess import host_quantize_shells
-            xyz = np.ascontiguousarray(xyz_dev.cpu().numpy(), np.float32)
-            out = host_quantize_shells(xyz, self.mode, [level_qs(self.data_type, lv) for _, lv in self.shells()], 0.0 if self.mullevel else self.cart_offset)
+            out = host_quantize_shells(np.ascontiguousarray(xyz_dev.cpu().numpy(), np.float32), self.mode, *self._quant_args())
             self._infos = [i for _, i in out]
-            return [torch.from_numpy(q).to(self.device) for q, _ in out], out[0][1].bin_num
-        qs, infos = [], []
-        for path, lv in self.shells():
-            q, qi, _ = native.quantize(xyz_dev, self.mode, level_qs(self.data_type, lv), 0.0 if self.mullevel else self.cart_offset)
-            qs.append(q)
-            infos.append(qi)
-        self._infos = infos
-        return qs, infos[0].bin_num
-
-    def quant_info(self):
-        """Per shell the (qs[3], offset[3]) the last `quantize` / `build_from_xyz` made its integers with - the cylindrical z offset
-        (the frame's z minimum) included: what a decoder needs to de-quantise (encode_ints(..., quant=))."""
-        return _quant_of(self._infos)
+            qs = [torch.from_numpy(q).to(self.device) for q, _ in out]
+        else:
+            qs = self._quantize_device(xyz_dev)
+        return qs, self._infos[0].bin_num
 
     def profile_string(self):
         return native.numeric_profile("OctAttention", None, decodable=self.decodable)
 
     def encode(self, xyz, timing=False, sequential=False):
         t0 = time.perf_counter()
-        if isinstance(xyz, np.ndarray):
-            xyz = torch.from_numpy(np.ascontiguousarray(xyz, np.float32))
+        xyz = _as_tensor(xyz, np.float32)
         xyz_dev = xyz.to(self.device)
         if not self.host_transform:
             bin_num = self.build_from_xyz(xyz_dev)
@@ -674,10 +670,8 @@ class OctAttnFrameEncoder:
 
     def build_from_xyz(self, xyz_dev):
         """Device transform: stage G1 + G2 in one launch sequence (scp_geom_build_xyz) -> bin_num of the first shell."""
-        infos = self.geom.build_xyz([xyz_dev], self.mode, [level_qs(self.data_type, lv) for _, lv in self.shells()],
-                                    0.0 if self.mullevel else self.cart_offset, [(path, self.mullevel) for path, _ in self.shells()])
-        self._infos = infos
-        return infos[0].bin_num
+        self._infos = self._build_xyz([xyz_dev])
+        return self._infos[0].bin_num
 
     def _front(self, qs):
         """stage G + the front-padded context sequences (encode_dataset.py:32-55 / encode_dataset_mullevel.py:44-73) on the
@@ -688,11 +682,7 @@ class OctAttnFrameEncoder:
                 qs = [qs]
             if len(qs) != len(self.shells()):
                 raise native.ScpError(f"expected {len(self.shells())} integer cloud(s), got {len(qs)}")
-            segs, off = [], 0
-            for (path, _), qq in zip(self.shells(), qs):
-                segs.append((off, qq.shape[0], path, self.mullevel))
-                off += qq.shape[0]
-            self.geom.build((torch.cat(qs) if len(qs) > 1 else qs[0]).contiguous(), segs)
+            self.geom.build((torch.cat(qs) if len(qs) > 1 else qs[0]).contiguous(), self._segments(qs))
         segs = self.geom.segments
         cs = self.context_size
         pad_ctx = torch.zeros((cs - 1, 12), dtype=torch.uint8, device=self.device)
@@ -776,7 +766,7 @@ class OctAttnFrameEncoder:
         t0 = t0 or time.perf_counter()
         if front is None:
             qs = q if isinstance(q, (list, tuple)) else [q]
-            qs = [(torch.from_numpy(np.ascontiguousarray(x, np.int32)) if isinstance(x, np.ndarray) else x).to(self.device) for x in qs]
+            qs = [_as_tensor(x, np.int32).to(self.device) for x in qs]
             front = self._front(qs)
         chunks, sym, N = front
         if sequential and self.decodable:
@@ -801,37 +791,20 @@ class OctAttnFrameEncoder:
         if defer:
             return lohi, meta, (table, sym, chunks)
         stream = native.ac_encode_lohi(lohi.cpu().numpy())
-        bits = 8 * len(stream)
-        return dict(bytes=stream, bits=bits, bpp=bits / n_points, times=dict(total=time.perf_counter() - t0),
-                    _debug=dict(table=table, sym_coded=sym), **meta)
+        return _result(stream, meta, dict(total=time.perf_counter() - t0), debug=dict(table=table, sym_coded=sym))
 
     def encode_async(self, xyz):
-        """Like encode(), but the D2H copy of the (c_low, c_high) pairs and the serial host range coder run on a worker thread
-        behind an event on a side stream (the same scheme as FrameEncoder.encode_async): the caller can enqueue the next frame
-        while this one is being coded.  `finish(handle)` blocks and returns the usual result dict."""
+        """Like encode(), but stage G runs on the front stream, the model part on the next lane, and the D2H copy of the (c_low, c_high)
+        pairs and the serial host range coder on a worker thread (_CoderPipeline): the caller can enqueue the next frame while this
+        one is being coded.  `finish(handle)` blocks and returns the usual result dict."""
         t0 = time.perf_counter()
-        if isinstance(xyz, np.ndarray):
-            xyz = torch.from_numpy(np.ascontiguousarray(xyz, np.float32))
-        if not hasattr(self, "_pool"):
-            self._pool = ThreadPoolExecutor(max_workers=2)
-            self._copy_stream = torch.cuda.Stream(device=self.device)
-            self._front_stream = torch.cuda.Stream(device=self.device, priority=-1)
-            # two lanes (with four frames in flight: 56.3 against 47.8 frames/s at L12, 23.1 against 21.0 at L14; three lanes: no better)
-            self._lanes = [torch.cuda.Stream(device=self.device) for _ in range(max(1, int(os.environ.get("SCP_LANES_OCTATTN", "2"))))]
-            self._lane_i = 0
-        # stage G has small D2H syncs: on a high-priority side stream they wait for stage G only, not for the previous frame's
-        # model kernels still queued on the main stream; consecutive frames run their model part on alternating streams (lanes,
-        # see FrameEncoder.encode_async)
+        xyz = _as_tensor(xyz, np.float32)
+        pipe = self._pipeline()
         caller = torch.cuda.current_stream(self.device)
-        if len(self._lanes) > 1:
-            main = self._lanes[self._lane_i % len(self._lanes)]
-            self._lane_i += 1
-            main.wait_stream(caller)
-        else:
-            main = caller
+        main = pipe.lane(caller)
         fills0 = native.CACHE_FILLS
-        with torch.cuda.stream(self._front_stream):
-            self._front_stream.wait_stream(caller)
+        with torch.cuda.stream(pipe.front_stream):
+            pipe.front_stream.wait_stream(caller)
             xyz_dev = xyz.to(self.device, non_blocking=True)
             if not self.host_transform:
                 q, bin_num = None, self.build_from_xyz(xyz_dev)
@@ -843,28 +816,13 @@ class OctAttnFrameEncoder:
         main.wait_event(ready)
         with torch.cuda.stream(main):
             lohi, meta, keep = self.encode_ints(q, bin_num, xyz_dev.shape[0], t0, defer=True, front=front, quant=self.quant_info())
-            done = torch.cuda.Event()
-            done.record()
-            if native.CACHE_FILLS != fills0:
-                main.synchronize()
-        host = torch.empty(lohi.shape, dtype=lohi.dtype, pin_memory=True)
-        with torch.cuda.stream(self._copy_stream):
-            self._copy_stream.wait_event(done)
-            host.copy_(lohi, non_blocking=True)
-            lohi.record_stream(self._copy_stream)
-            copied = torch.cuda.Event(blocking=True)      # the coder thread SLEEPS until the pairs have landed (a default event spins a core)
-            copied.record()
-
-        def work():
-            _wait_event(copied)
-            return native.ac_encode_lohi(host.numpy())
-
-        return dict(future=self._pool.submit(work), meta=meta, t0=t0, keep=(keep, lohi, q, xyz_dev))
+        # (the handle keeps what the front stream allocated - the frame, its integers, the context sequences - and the table referenced
+        # until finish(): see FrameEncoder._model_async)
+        return dict(future=pipe.submit(main, lohi, fills0), meta=meta, t0=t0, keep=(keep, lohi, q, xyz_dev))
 
     def finish(self, h):
         stream = h["future"].result()
-        bits = 8 * len(stream)
-        return dict(bytes=stream, bits=bits, bpp=bits / h["meta"]["n_points"], times=dict(total=time.perf_counter() - h["t0"]), **h["meta"])
+        return _result(stream, h["meta"], dict(total=time.perf_counter() - h["t0"]))
 
     def outfile(self, base, res):
         """encode.py:24 (`<base>.bin`) / encode_mullevel.py:68-72 (`<base>[_spher|_cylin]_<chunks>_<bin_num>_0.bin`)."""

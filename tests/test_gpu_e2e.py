@@ -108,16 +108,27 @@ def _ints_of(enc, xyz):
     return qs, infos[0].bin_num, (infos[0].offset[2] if enc.cylin else 0.0), xyz.shape[0]
 
 
+def _result_diff(a, b):
+    """Keys in which two result dicts of one frame differ: a field only one of them has, or - `times` aside - another value.  `_debug` (the
+    synchronous entry points' device tensors) is not a field of the result."""
+    ka, kb = set(a) - {"_debug"}, set(b) - {"_debug"}
+    same = lambda k: np.array_equal(a[k], b[k]) if k == "pos_mm" else a[k] == b[k]
+    return sorted(ka ^ kb) + sorted(k for k in (ka & kb) - {"times"} if not same(k))
+
+
 def test_async_pipeline_equals_sync(enc_parts):
     from scp_amd.encoder import FrameEncoder, EncodePlan
     from scp_amd.synth import synth_frame
     model, dev = enc_parts
     enc = FrameEncoder(model, "kitti", 12, spher=True, device=dev)
     frames = [synth_frame(s)[::12].copy() for s in (1, 2, 3)]
-    want = [enc.encode(f)["bytes"] for f in frames]
+    sync = [enc.encode(f) for f in frames]
+    want = [r["bytes"] for r in sync]
     hs = [enc.encode_async(f) for f in frames]
-    got = [enc.finish(h)["bytes"] for h in hs]
+    res = [enc.finish(h) for h in hs]
+    got = [r["bytes"] for r in res]
     assert got == want
+    assert [_result_diff(a, b) for a, b in zip(sync, res)] == [[]] * len(frames)
     plan = EncodePlan([1, 6, 8193, 7, 2], 8192)
     assert np.array_equal(plan.coding_order_device(dev).cpu().numpy(), plan.coding_order())
 
@@ -244,6 +255,7 @@ def test_octattn_async_pipeline_equals_sync():
     got = [enc.finish(h) for h in hs]
     assert [g["bytes"] for g in got] == [w["bytes"] for w in want]
     assert [g["n_nodes"] for g in got] == [w["n_nodes"] for w in want] and got[0]["bpp"] == want[0]["bpp"]
+    assert [_result_diff(w, g) for w, g in zip(want, got)] == [[]] * len(frames)
 
 
 def test_numpyac_api_roundtrip():
@@ -969,6 +981,7 @@ def test_batched_frames_give_the_per_frame_streams(enc_parts, mul, level):
         assert a["bytes"] == b["bytes"] and a["n_nodes"] == b["n_nodes"] and a["n_points"] == b["n_points"] and a["bin_num"] == b["bin_num"]
         assert a["level_sizes"] == b["level_sizes"] and np.array_equal(a["pos_mm"], b["pos_mm"]) and a["bin_nums"] == b["bin_nums"]
         assert enc.outfile("x", a) == enc.outfile("x", b)
+    assert [_result_diff(a, b) for a, b in zip(single, got)] == [[]] * len(frames)
     # a second batch on the same encoder (workspace reuse) and a batch of one
     again = enc.finish_batch(enc.encode_batch_async(frames[::-1]))
     assert [r["bytes"] for r in again] == [r["bytes"] for r in single[::-1]]
