@@ -39,9 +39,106 @@ def build_one(dev, pts, path=None, drop=False):
 
 
 # ----------------------------------------------------------------------------------------------- a2/a3
+# The device quantiser against the correctly rounded reference of tests/quantiser_ref.py (vouched for on the CPU by
+# tests/test_quantiser_ref.py): bit for bit, except values whose float64 angle lies next to a float32 rounding midpoint.
+AMBIGUOUS_CAP = 2e-5          # at most 2 such values per 100 000 points; test_quantiser_ref.py counts 0 on every input used here
+
+
+def assert_info_is_cr(info, ref):
+    assert info.bin_num == ref.bin_num
+    assert list(info.qs) == ref.qs and list(info.offset) == ref.offset
+    assert info.max_coord == ref.max_coord and info.min_coord == ref.min_coord
+
+
+def assert_quantised_is_cr(q, ref, tr=None):
+    """q [n,3] (numpy) == the reference's integers on every row without an ambiguous value, tr (if given) bit-identical on every
+    non-ambiguous value; -> number of values left out."""
+    import quantiser_ref as R
+    amb = R.ambiguous(ref.raw64)
+    left_out = int(amb.sum())
+    assert left_out <= AMBIGUOUS_CAP * len(ref.q), left_out
+    if tr is not None:
+        ok = (tr.view(np.int32) == ref.tr.view(np.int32)) | amb
+        assert ok.all(), (int((~ok).sum()), np.argwhere(~ok)[:8].tolist(), tr[~ok][:8].tolist(), ref.tr[~ok][:8].tolist())
+    rows = ~amb.any(1)
+    ok = (q == ref.q)[rows]
+    assert ok.all(), (int((~ok).sum()), np.argwhere(~ok)[:8].tolist())
+    return left_out
+
+
+def cr_inputs():
+    import quantiser_ref as R
+    from scp_amd.synth import ford_like, synth_frame
+    kitti = [(400 / (2 ** L - 1), f"L{L}") for L in (12, 16, 18)]
+    d = {"xform_s0": (lambda m: golden("xform_s0")["xyz"], kitti), "xform_s1": (lambda m: golden("xform_s1")["xyz"], kitti),
+         "edge": (R.edge_points, kitti),
+         "ford29": (lambda m: ford_like(synth_frame(0))[::29].copy(), [(2.0, "step2"), (0.5, "step0.5")])}
+    for n in (1, 2, 63, 65, 257, 4001):
+        d[f"synth7_{n}"] = (lambda m, n=n: synth_frame(7)[:n].copy(), kitti)
+    return d
+
+
+@pytest.mark.parametrize("name", ["xform_s0", "xform_s1", "edge", "synth7_1", "synth7_2", "synth7_63", "synth7_65", "synth7_257",
+                                  "synth7_4001", "ford29"])
+@pytest.mark.parametrize("mode", ["spher", "cylin"])
+def test_transform_is_correctly_rounded(dev, mode, name):
+    """scp_quantize (transform_kernel + quantize_kernel): the transformed float32 coordinates are the correctly rounded ones of
+    DESIGN.md 2.1 bit for bit - axes, the +-pi seam, the poles and denormal coordinates included - the integers are the exact float64
+    function of them, and scp_quant_info reports the reference's bin_num, steps, offsets and extreme integers."""
+    import torch
+    import quantiser_ref as R
+    from conftest import parity_record
+    from scp_amd import native
+    make, steps = cr_inputs()[name]
+    xyz = np.ascontiguousarray(make(mode), np.float32)
+    x = torch.from_numpy(xyz).to(dev)
+    mi = {"spher": native.SPHER, "cylin": native.CYLIN}[mode]
+    for qs, tag in steps:
+        ref = R.cr_quantise(xyz, qs, mode, -200.0)
+        q, info, tr = native.quantize(x, mi, qs, -200.0, want_transformed=True)
+        left_out = assert_quantised_is_cr(q.cpu().numpy(), ref, tr.cpu().numpy())
+        assert_info_is_cr(info, ref)
+        parity_record(f"quantiser-cr/{name}/{mode}/{tag}", points=len(xyz), values_left_out_as_ambiguous=left_out)
+
+
+@pytest.mark.parametrize("mode", ["spher", "cylin"])
+def test_fused_front_is_correctly_rounded(dev, mode):
+    """scp_geom_build_xyz (front_transform_kernel + front_key_kernel) on three frames in one call - the crafted edge set, a frame that
+    leaves the last tile ragged, a 7-point frame: the integers of every (frame, shell) segment and its scp_quant_info equal the
+    correctly rounded reference's, and the depth derived from the extreme COORDINATES (the quantiser is monotone) is the depth of
+    the largest INTEGER."""
+    import torch
+    import quantiser_ref as R
+    from conftest import parity_record
+    from scp_amd import native
+    from scp_amd.synth import synth_frame
+    frames = [R.edge_points(mode), synth_frame(3)[:4097].copy(), synth_frame(1)[:7].copy()]
+    if mode == "spher":
+        mi, off, levels, shells = native.SPHER, 0.0, (16, 17, 18), [([0, 0], True), ([0, 1], True), ([1], True)]
+    else:
+        mi, off, levels, shells = native.CYLIN, -200.0, (12,), [(None, False)]
+    qs_list = [400 / (2 ** L - 1) for L in levels]
+    g = native.Geom()
+    infos, q = g.build_xyz([torch.from_numpy(f).to(dev) for f in frames], mi, qs_list, off, shells, want_q=True)
+    q = q.cpu().numpy()
+    assert len(infos) == len(frames) * len(shells) and q.shape == (sum(len(f) for f in frames) * len(shells), 3)
+    row = left_out = 0
+    for f, xyz in enumerate(frames):
+        for s, qs in enumerate(qs_list):
+            ref = R.cr_quantise(xyz, qs, mode, off)
+            left_out += assert_quantised_is_cr(q[row:row + len(xyz)], ref)
+            assert_info_is_cr(infos[f * len(shells) + s], ref)
+            seg = g.info[f * len(shells) + s]
+            assert seg.depth == R.depth_of(ref.max_coord) and seg.max_coord == ref.max_coord
+            row += len(xyz)
+    assert row == len(q)
+    parity_record(f"quantiser-cr/fused/{mode}", points=row, values_left_out_as_ambiguous=left_out)
+
+
 @pytest.mark.parametrize("seed", [0, 1])
 def test_quantizer_vs_reference(dev, orc, seed):
     import torch
+    import quantiser_ref as R
     from scp_amd import native
     z = golden(f"xform_s{seed}")
     xyz = torch.from_numpy(z["xyz"]).to(dev)
@@ -50,6 +147,10 @@ def test_quantizer_vs_reference(dev, orc, seed):
         for L in (12, 14, 16, 18):
             q, info, tr = native.quantize(xyz, mi, 400 / (2 ** L - 1), -200.0, want_transformed=True)
             q = q.cpu().numpy()
+            ref = R.cr_quantise(z["xyz"], 400 / (2 ** L - 1), mode, -200.0)
+            assert_quantised_is_cr(q, ref, tr.cpu().numpy())
+            assert_info_is_cr(info, ref)
+            assert R.unexplained(mode, ref, z[f"{mode}_L{L}_q"])[2] == 0
             if mode != "cart":
                 assert info.bin_num == float(z[f"{mode}_L{L}_bin"])
                 ref = z[f"{mode}_tr"]
@@ -157,15 +258,19 @@ def test_full_frame_checksums(dev):
     """BASELINE-size frames (configs[1..4] geometry): the REFERENCE quantiser's integers in (tests/golden/frame_ints.npz, made by
     running data_preprocess.py:40-68 in the build container) -> node counts per level, sha256 of the occupancy stream and of the
     [N,4,6] K-records must equal what the reference's octree builders produced (frame_facts.json) - asserted unconditionally -
-    and the device quantiser's own integers may differ from the reference's for at most the measured handful of points."""
+    and the device quantiser's own integers are exactly the correctly rounded ones (tests/quantiser_ref.py), which differ from the
+    reference's in the pinned number of points (853 at L12 spherical, 6 at L18, 0 elsewhere), each a +-1 at a rounding boundary."""
     import torch
+    import quantiser_ref as R
     from conftest import parity_record
     from scp_amd import native
     from scp_amd.synth import synth_frame
     facts = json.load(open(os.path.join(GOLDEN, "frame_facts.json")))
     ints = golden("frame_ints")
-    xyz = torch.from_numpy(synth_frame(0)).to(dev)
+    xyz_np = synth_frame(0)
+    xyz = torch.from_numpy(xyz_np).to(dev)
     n = xyz.shape[0]
+    mode_name = {native.SPHER: "spher", native.CYLIN: "cylin", native.CART: "cart"}
     # measured on MI355X (profiles/parity_r2.json): points whose device-quantised integers differ from this fixture's
     max_diff_pts = {"L12-s": 900, "L16-s": 0, "C14": 0, "L12-c": 0, "L17": 0, "L18": 8}      # measured: 853, 0, 0, 0, 0, 6
     for key, mode, name, L in (("L12-s", native.SPHER, "q_spher_L12", 12), ("L16-s", native.SPHER, "q_spher_L16", 16),
@@ -175,8 +280,14 @@ def test_full_frame_checksums(dev):
         assert info.bin_num == f["bin_num"]
         q_ref = np.ascontiguousarray(ints[name])
         ndiff = int((q_dev.cpu().numpy() != q_ref).any(1).sum())
-        parity_record(f"quantiser/{key}", points=n, points_differing_from_reference_ints=ndiff)
+        # the device's integers are the correctly rounded reference's, which differs from the fixture in exactly the pinned, explained points
+        ref = R.cr_quantise(xyz_np, 400 / (2 ** L - 1), mode_name[mode], -200.0)
+        assert_quantised_is_cr(q_dev.cpu().numpy(), ref)
+        assert_info_is_cr(info, ref)
+        cols, pts, bad = R.unexplained(mode_name[mode], ref, q_ref)
+        parity_record(f"quantiser/{key}", points=n, points_differing_from_reference_ints=ndiff, coordinates_explained=sum(cols) - bad)
         assert ndiff <= max_diff_pts[key], (key, ndiff)
+        assert bad == 0 and ndiff == pts == R.FRAME_DIFF_POINTS[name], (key, ndiff, pts, bad)
         g = native.Geom()
         g.build(torch.from_numpy(q_ref).to(dev), [(0, n, None, False)])
         i = g.info[0]
@@ -192,8 +303,13 @@ def test_full_frame_checksums(dev):
         assert info.bin_num == shells[k]["bin_num"]
         q_ref = np.ascontiguousarray(ints[f"q_spher_L{16 + k}"])
         ndiff = int((q_dev.cpu().numpy() != q_ref).any(1).sum())
-        parity_record(f"quantiser/L16-m shell {k}", points=n, points_differing_from_reference_ints=ndiff)
+        ref = R.cr_quantise(xyz_np, 400 / (2 ** (16 + k) - 1), "spher", 0.0)
+        assert_quantised_is_cr(q_dev.cpu().numpy(), ref)
+        assert_info_is_cr(info, ref)
+        cols, pts, bad = R.unexplained("spher", ref, q_ref)
+        parity_record(f"quantiser/L16-m shell {k}", points=n, points_differing_from_reference_ints=ndiff, coordinates_explained=sum(cols) - bad)
         assert ndiff <= max_diff_pts[("L16-s", "L17", "L18")[k]], (k, ndiff)
+        assert bad == 0 and ndiff == pts == R.FRAME_DIFF_POINTS[f"q_spher_L{16 + k}"], (k, ndiff, pts, bad)
         qs_list.append(torch.from_numpy(q_ref).to(dev))
     g = native.Geom()
     g.build(torch.cat(qs_list), [(0, n, [0, 0], True), (n, n, [0, 1], True), (2 * n, n, [1], True)])
@@ -385,6 +501,8 @@ def test_quantizer_any_point_count(dev, orc, n):
     """Point counts of every parity and size (a scratch pointer derived from an odd-sized allocation once made every odd-n frame
     fault on a misaligned atomic): same integers as the oracle up to the float -> int boundary points, all three modes."""
     import torch
+    import quantiser_ref as R
+    from conftest import parity_record
     from scp_amd import native
     from scp_amd.synth import synth_frame
     xyz = synth_frame(7)[:n].copy()
@@ -395,6 +513,12 @@ def test_quantizer_any_point_count(dev, orc, n):
         assert got.shape == (n, 3) and info.bin_num == bin_num
         # (synthetic rings can sit on a rounding boundary of theta / qs as a whole: DESIGN.md 2.1)
         assert (got != pt.astype(np.int64)).any(1).sum() <= max(2, n // 40)
+        ref = R.cr_quantise(xyz, 400 / (2 ** 12 - 1), name, -200.0)           # ... and exactly the correctly rounded integers
+        assert_quantised_is_cr(got, ref)
+        assert_info_is_cr(info, ref)
+        cols, pts, bad = R.unexplained(name, ref, pt)
+        assert bad == 0, (name, cols, bad)
+        parity_record(f"quantiser-any-n/{n}/{name}", points=n, points_differing_from_oracle_ints=pts, coordinates_explained=sum(cols) - bad)
         g = native.Geom()
         g.build(q, [(0, n, None, False)])
         assert g.info[0].n_leaves == len(np.unique(got, axis=0))
@@ -441,6 +565,13 @@ def test_fused_front_equals_the_separate_launches(dev, mode, level, mul, ford, n
     for a, b in zip(infos, ref_info):
         assert a.bin_num == b.bin_num and list(a.qs) == list(b.qs) and list(a.offset) == list(b.offset)
         assert a.max_coord == b.max_coord and a.min_coord == b.min_coord
+    # ... and both are the correctly rounded reference's (the two transform kernels are separate copies of one arithmetic)
+    import quantiser_ref as R
+    for s, q_ in enumerate(qs_list):
+        ref = R.cr_quantise(xyz, q_, mode, off)
+        assert_quantised_is_cr(ref_q[s].cpu().numpy(), ref)
+        assert_info_is_cr(infos[s], ref)
+        assert g1.info[s].depth == R.depth_of(ref.max_coord)
     for s in range(len(shells)):
         assert g0.level_counts(s) == g1.level_counts(s) and g0.info[s].depth == g1.info[s].depth and g0.info[s].n_leaves == g1.info[s].n_leaves
         assert torch.equal(g0.leaves(s), g1.leaves(s))
