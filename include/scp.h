@@ -44,7 +44,7 @@ extern "C" {
  *        kernel that applies it; scp_swin_post_attn expects fc1 scaled by scp_gelu_prescale() and fc2 by its inverse.
  *        (additive, no new version: scp_decode_expand, scp_linear_split_f16_max, scp_row_scale_from_max, scp_octattn_attention_f16x3_vmax;
  *        round 6: scp_linear_split_hier2, scp_mlp3_rows; scp_octattn_attention_rowinv, scp_decode_expand_octattn, scp_octattn_attention_rowinv_step - existing entry points keep their bits, the EHEM model's numeric profile moved to ehem/6
- *        because models/packed.py now calls the two new ones.) */
+ *        because models/packed.py now calls the two new ones; D2 PSNR: scp_estimate_normals_f64, scp_nn_tieset_f64.) */
 #define SCP_ABI_VERSION 220
 SCP_API int scp_version(void);
 SCP_API int scp_last_hip_error(void);
@@ -443,6 +443,27 @@ SCP_API int int_get(void *codes, int i);
  * utils/__init__.py:3-15); the host side (scp_amd/metrics.py) forms chamfer = max(mean sqrt d2_ab, mean sqrt d2_ba) and
  * PSNR = 10 log10(3 peak^2 / max(mean d2_ab, mean d2_ba)). */
 SCP_API int scp_nn_sqdist_f64(const double *a, int64_t na, const double *b, int64_t nb, double *d2, void *stream);
+
+/* D2 (point-to-plane) distortion, float64, device pointers (csrc/normals.hip; host side: scp_amd/metrics.py estimate_normals / d2_psnr).
+ *
+ * scp_estimate_normals_f64: what data_preproc/gene_normals.py gets from open3d (hybrid search + orientation towards the sensor).
+ * The neighbours of point i are the up to max_nn (1 .. 32) nearest points with d2 <= radius^2, i itself included, ordered by d2 and
+ * then by index, d2 = (dx*dx + dy*dy) + dz*dz as in scp_nn_sqdist_f64.  normals [n][3] = unit eigenvector of the smallest eigenvalue
+ * of their centred covariance (cyclic Jacobi), (0,0,1) with fewer than 3 neighbours, flipped where n . (view - p) < 0; view = 3 HOST
+ * doubles.  count [n] = neighbours found; idx [n][max_nn] = their indices, -1 padded (NULL: not wanted).  n <= 2^30.
+ *
+ * scp_nn_tieset_f64: the reductions of the MPEG pc_error tool's p2plane metric over tie sets.  p_j is a nearest neighbour of q_i iff
+ * its recomputed d2 equals the minimum scp_nn_sqdist_f64 stored, bit for bit; every equal-distance neighbour counts.  Sums run in index
+ * order and are divided by the count once, so the results are reproducible bit for bit.
+ *   SCP_TIE_MEAN_NORMAL  dmin [np] (p against q) and nrm [np][3] belong to p; out [nq][3] = mean of nrm[j] over {j : q_i is a nearest
+ *                        neighbour of p_j}, not renormalised; 0 where no p_j points at q_i.
+ *   SCP_TIE_PLANE_ERROR  dmin [nq] (q against p) belongs to q, nrm [np][3] to p; out [nq] = mean over the nearest neighbours p_j of q_i
+ *                        of ((q_i - p_j) . nrm[j])^2, the product summed as (dx*nx + dy*ny) + dz*nz. */
+enum { SCP_TIE_MEAN_NORMAL = 0, SCP_TIE_PLANE_ERROR = 1 };
+SCP_API int scp_estimate_normals_f64(const double *xyz, int64_t n, double radius, int32_t max_nn, const double *view, double *normals,
+                                     int32_t *count, int32_t *idx, void *stream);
+SCP_API int scp_nn_tieset_f64(int32_t mode, const double *q, int64_t nq, const double *p, int64_t np, const double *dmin, const double *nrm,
+                              double *out, void *stream);
 
 /* Input stage of the packed EHEM forward: embeddings of dgcnn.py:121-128 fused with the packed layout's input gather.
  * ctx u8 [T][12] = 4 x (level, octant, occ) (scp_geom_context_ehem), pos f32 [T][3], inmap i64 [rows] (== n_tokens: pad token);

@@ -9,6 +9,8 @@ same stdout block per frame, same summary file.  Differences, all additive:
   * `--test_files` accepts a glob, a directory or a list (the reference's `glob.glob(list)` cannot work, SURVEY B-3).
   * `--metrics`: chamfer distance and D1 PSNR of every frame, computed on the device (scp_amd/metrics.py; the reference
     shells out to pc_error and a CPU KD-tree for these) - they enter the per-frame block and the all-reduced summary.
+  * `--normals estimate|DIR` (with `--metrics`, EHEM): the D2 (point-to-plane) PSNR as well, on normals estimated on the device or
+    read from the `<DIR>/<sequence>/<frame>.ply` files `gene_normals.py` writes; one more line per frame, `PSNR_D2:` in the summary.
 """
 import argparse
 import glob
@@ -72,6 +74,9 @@ def get_args(argv=None, mullevel=False):
     p.add_argument("--random_weights", type=int, default=None)
     p.add_argument("--out_dir", type=str, default=None)
     p.add_argument("--metrics", action="store_true", help="chamfer distance + D1 PSNR per frame (computed on the device)")
+    p.add_argument("--normals", type=str, default=None, metavar="estimate|DIR",
+                   help="with --metrics (EHEM): also the D2 (point-to-plane) PSNR, on normals estimated on the device (`estimate`) or read "
+                        "from <DIR>/<sequence>/<frame>.ply as written by gene_normals.py")
     p.add_argument("--decodable", action="store_true",
                    help="OctAttention only: code under the decodable numeric profile (octattn/1d) so that decode.py can rebuild the stream; "
                         "EHEM streams are decodable already")
@@ -121,6 +126,8 @@ def refuse_unsupported(args, name, mullevel):
         raise native.ScpError("--preproc_path with OctAttention is not supported (records are rebuilt on the device from the frame)")
     if name == "OctAttention" and args.metrics:
         raise native.ScpError("--metrics is available for the EHEM encoders only")
+    if getattr(args, "normals", None) and (name == "OctAttention" or not args.metrics):
+        raise native.ScpError("--normals adds the D2 PSNR to --metrics, which the EHEM encoders have: give --metrics as well, with an EHEM model")
     if args.type == "obj" and (args.spher or args.cylin or mullevel and name != "OctAttention"):
         raise native.ScpError("--type obj is Cartesian and single-level in the reference (proc_pc defaults); drop --spher/--cylin/mullevel")
     if args.sequential and name != "OctAttention":
@@ -146,6 +153,58 @@ def spawn_ranks(n, argv0, argv):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), argv0] + list(argv)
     return subprocess.call(cmd)
+
+
+def normals_file(root, ori):
+    """The file gene_normals.py writes for the original file `ori`: `<root>/<sequence>/<frame>.ply`, the sequence being the third path
+    component from the end (KITTI: <sequence>/velodyne/<frame>.bin; gene_normals.py:36-39)."""
+    parts = str(ori).split("/")
+    return os.path.join(root, parts[-3] if len(parts) >= 3 else "", Path(ori).stem + ".ply")
+
+
+def frame_normals(source, ori, x_dev):
+    """`--normals`: one normal per input point, float32 values on the device.  `estimate`: the device estimator with gene_normals.py's
+    parameters, rounded to the float32 its file would carry - so both sources give the same D2.  Otherwise the file of `normals_file`,
+    whose points must be the frame's, in the frame's order."""
+    from . import metrics
+    if source == "estimate":
+        return metrics.estimate_normals(x_dev).float()
+    path = normals_file(source, ori)
+    if not os.path.exists(path):
+        raise native.ScpError(f"--normals {source}: no {path} for {ori} (gene_normals.py --ori_dir ... --out_dir {source} writes it)")
+    pts, nrm = pointCloud.load_ply_normals(path)
+    if pts.shape[0] != x_dev.shape[0] or not np.array_equal(pts, x_dev.cpu().numpy()):
+        raise native.ScpError(f"{path} does not hold the points of {ori} in its order: normals belong to points by position")
+    return torch.from_numpy(nrm).to(x_dev.device)
+
+
+def gene_normals_main(argv=None):
+    """Drop-in for data_preproc/gene_normals.py: for every KITTI `.bin` matching `--ori_dir` (a glob; `--parts i/n` takes the i-th of n
+    slices) write `<out_dir>/<sequence>/<frame>.ply`, ascii x y z nx ny nz declared float32, with normals from the device estimator
+    (radius 1.0, at most 30 neighbours, turned towards the sensor at the origin) where the reference calls open3d."""
+    from . import metrics
+    p = argparse.ArgumentParser()
+    p.add_argument("--ori_dir", type=str, required=True)
+    p.add_argument("--out_dir", type=str, required=True)
+    p.add_argument("--parts", type=str, default="-1/-1")
+    args = p.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise native.ScpError("gene_normals needs an MI355X: the normal estimator has no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    native.lib()
+    files = sorted(glob.glob(args.ori_dir))
+    part, total = (0, 1) if args.parts.startswith("-1") else (int(args.parts.split("/")[0]), int(args.parts.split("/")[1]))
+    start, end = len(files) * part // total, len(files) * (part + 1) // total
+    written = []
+    for i, ori in enumerate(files[start:end]):
+        print(f"part {part}/{total}: {i}/{end - start}")
+        out = normals_file(args.out_dir, ori)
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        pc = pointCloud.loadbin(ori)[0]
+        nrm = metrics.estimate_normals(torch.from_numpy(np.ascontiguousarray(pc, np.float32)).to(dev))
+        pointCloud.write_ply_normals(out, pc, nrm.float().cpu().numpy())
+        written.append(out)
+    return written
 
 
 class Prefetch:
@@ -227,7 +286,7 @@ def main(argv=None, mullevel=False):
     host_ints = enc.host_ints if (pipelined and name != "OctAttention" and enc.host_transform) else None
     reader = Prefetch(mine, post=host_ints)
     pending = []
-    sums = [0.0, 0.0, 0.0, 0.0, 0.0]
+    sums = [0.0, 0.0, 0.0, 0.0, 0.0] + ([0.0] if args.normals else [])      # --normals: one more number in the reduced summary
     last_done = [time.time()]
 
     def stem_of(cur):
@@ -256,6 +315,9 @@ def main(argv=None, mullevel=False):
         if dist:
             print("chamfer distance            :", dist["chamfer"])
             print("PSNR (D1)                   :", dist["psnr"])
+            if "psnr_d2" in dist:
+                print("PSNR (D2)                   :", dist["psnr_d2"])
+                sums[5] += dist["psnr_d2"]
         sums[0] += res["bpp"]; sums[1] += dist["psnr"] if dist else 0.0; sums[2] += dist["chamfer"] if dist else 0.0
         sums[3] += elapsed; sums[4] += 1
 
@@ -304,7 +366,8 @@ def main(argv=None, mullevel=False):
         else:
             res = enc.encode(xyz)
             if args.metrics:
-                dist = enc.distortion(torch.from_numpy(np.ascontiguousarray(xyz[:, :3], np.float32)).to(dev))
+                x_dev = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], np.float32)).to(dev)
+                dist = enc.distortion(x_dev, normals=frame_normals(args.normals, cur, x_dev) if args.normals else None)
         report(cur, res, t0, dist)
     for c0, h0, ts in pending:
         report(c0, enc.finish(h0), ts)
@@ -314,10 +377,12 @@ def main(argv=None, mullevel=False):
         print("sample number:", m["count"])
         print("times:", m["time"])
         print("bpp:", m["bpp"])
+        if args.normals:
+            print("PSNR_D2:", m["psnr_d2"])
         if combine and args.type in ("kitti", "ford"):
             tag = "mul" if mullevel else "same"
             out = (f"{tag} {args.lidar_level} {args.test_files} {args.ckpt_path}\nsample number: {m['count']}\ntimes: {m['time']}\n"
-                   f"bpp: {m['bpp']}\nchamfer_dist: {m['chamfer']}\nPSNR: {m['psnr']}\n\n")
+                   f"bpp: {m['bpp']}\nchamfer_dist: {m['chamfer']}\nPSNR: {m['psnr']}\n" + (f"PSNR_D2: {m['psnr_d2']}\n" if args.normals else "") + "\n")
             with open(f"test_results_{tag}_{args.type}_{args.lidar_level}.txt", "a") as f:
                 f.write(out)
     D.finalize()

@@ -1,8 +1,9 @@
 """Point-cloud readers / writers of the encode path (drop-in for the input half of data_preproc/pt.py).
 
 Only the formats the encode CLI touches: KITTI `.bin` (pt.py:190), ascii `.ply` (pt.py:224, the reference parses it line
-by line and skips every line that does not start with three floats) and the ascii PLY writer used for `_quant.ply`.
-PSNR / chamfer tooling (pc_error subprocess, KD-tree) is out of scope.
+by line and skips every line that does not start with three floats), the ascii PLY writer used for `_quant.ply`, and the
+ascii PLY with normals that data_preproc/gene_normals.py leaves behind (x y z nx ny nz, declared float32) for the D2 PSNR.
+The metrics themselves (chamfer, D1, D2) run on the device: scp_amd/metrics.py; no pc_error subprocess, no KD-tree.
 """
 import os
 
@@ -50,3 +51,32 @@ def write_ply_data(filename, points):
                 % len(points))
         for p in points:
             f.write("%s %s %s\n" % (repr(float(p[0])), repr(float(p[1])), repr(float(p[2]))))
+
+
+def write_ply_normals(filename, points, normals):
+    """ascii PLY with x y z nx ny nz, every property declared `float32` (gene_normals.py:46-52 rewrites open3d's `double` header that
+    way).  Values are rounded to float32 and written with the digits that read back to the same float32."""
+    points, normals = np.asarray(points, np.float32), np.asarray(normals, np.float32)
+    if points.shape != normals.shape or points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f"points {points.shape} and normals {normals.shape} must both be [n,3]")
+    with open(filename, "w") as f:
+        f.write("ply\nformat ascii 1.0\nelement vertex %d\n" % len(points))
+        f.write("".join("property float32 %s\n" % c for c in ("x", "y", "z", "nx", "ny", "nz")) + "end_header\n")
+        for row in np.hstack((points, normals)):
+            f.write(" ".join(str(v) for v in row) + "\n")            # str(np.float32): the shortest text that reads back exactly
+
+
+def load_ply_normals(filename):
+    """-> (xyz float32 [n,3], normals float32 [n,3]) of an ascii PLY whose vertex lines hold x y z nx ny nz."""
+    rows = []
+    with open(filename) as f:
+        for line in f:
+            w = line.split()
+            try:
+                rows.append([float(t) for t in w[:6]])
+            except ValueError:
+                continue
+            if len(rows[-1]) < 6:
+                rows.pop()
+    a = np.array(rows, dtype=np.float64).reshape(-1, 6).astype(np.float32)
+    return a[:, :3].copy(), a[:, 3:].copy()

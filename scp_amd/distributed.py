@@ -158,7 +158,8 @@ def shard(items, rank, world):
 
 
 def reduce_summary(sums, device=None):
-    """sums: [sum_bpp, sum_psnr, sum_chamfer, sum_time, count] of this rank -> the same five numbers over all ranks."""
+    """sums: [sum_bpp, sum_psnr, sum_chamfer, sum_time, count] of this rank (encode --normals: + [sum_psnr_d2]) -> the same numbers over
+    all ranks."""
     t = torch.tensor([float(x) for x in sums], dtype=torch.float64, device=device)
     if dist.is_available() and dist.is_initialized():          # (a world of one - init(force=True) - runs the collective too)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
@@ -167,7 +168,10 @@ def reduce_summary(sums, device=None):
 
 def summary_means(total):
     n = max(total[4], 1.0)
-    return dict(bpp=total[0] / n, psnr=total[1] / n, chamfer=total[2] / n, time=total[3] / n, count=int(total[4]))
+    m = dict(bpp=total[0] / n, psnr=total[1] / n, chamfer=total[2] / n, time=total[3] / n, count=int(total[4]))
+    if len(total) > 5:          # encode --normals: the sum of the D2 PSNRs rides along
+        m["psnr_d2"] = total[5] / n
+    return m
 
 
 def finalize():

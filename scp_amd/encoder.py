@@ -316,16 +316,23 @@ class FrameEncoder(_FrontEnd):
         first = self._infos[0]
         return qs, first.bin_num, (first.offset[2] if self.cylin else 0.0)
 
-    def distortion(self, xyz_dev, infos=None):
+    def distortion(self, xyz_dev, infos=None, normals=None):
         """Chamfer distance and D1 PSNR of the frame just encoded (the octree of the last `encode` / `preprocess` call) against
         its input cloud, on the device - what the reference gets from distChamfer + the pc_error tool
-        (encode_dataset_ehem.py:170-171, encode_dataset_ehem_mullevel.py:141-144; scp_amd/metrics.py)."""
+        (encode_dataset_ehem.py:170-171, encode_dataset_ehem_mullevel.py:141-144; scp_amd/metrics.py).  With `normals` (device [P,3], one
+        per input point: metrics.estimate_normals or a gene_normals.py file) the dict gains the D2 (point-to-plane) PSNR `psnr_d2` and its
+        two directions `mse_ab_d2`, `mse_ba_d2`."""
         from . import metrics
         pts = []
         for s, info in enumerate(infos or self._infos):   # infos: per shell, anything with .qs[3] and .offset[3] (tests: the oracle's)
             pts.append(metrics.dequantize(self.geom.leaves(s), info.qs, info.offset, spher=self.spher, cylin=self.cylin,
                                           f32=not self.mullevel).double())
-        return metrics.chamfer_psnr(xyz_dev, torch.cat(pts), metrics.PEAK.get(self.data_type, 1.0))
+        quant, peak = torch.cat(pts), metrics.PEAK.get(self.data_type, 1.0)
+        d = metrics.chamfer_psnr(xyz_dev, quant, peak)
+        if normals is not None:
+            p2 = metrics.d2_psnr(xyz_dev, normals, quant, peak)
+            d.update(psnr_d2=p2["psnr_d2"], mse_ab_d2=p2["mse_ab"], mse_ba_d2=p2["mse_ba"])
+        return d
 
     def preprocess(self, xyz_dev, ints=None):
         if ints is None and not self.host_transform:

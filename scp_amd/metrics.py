@@ -6,6 +6,18 @@ tool it shells out to with `-r peak` (pt.py:13-85; `get_psnr`, utils/__init__.py
     mse_ab = mean_i min_j |a_i - b_j|^2,  mseF = max(mse_ab, mse_ba),  PSNR = 10 log10(3 peak^2 / mseF)
 peak = 59.70 (KITTI) / 30000 (Ford) (encode_dataset_ehem.py:115-117).  pc_error merges exactly duplicated input points
 before measuring (--dropdups=2, its default): `chamfer_psnr(..., dropdups=True)` does the same for the PSNR only.
+
+`estimate_normals` + `d2_psnr` = the D2 (point-to-plane) column: data_preproc/gene_normals.py (open3d hybrid search, radius 1.0, at most
+30 neighbours, normals turned towards the sensor) and the "mseF,PSNR (p2plane)" lines of the same pc_error run.  With A the cloud that
+carries normals and B the other one, T_A(i) = every b_j at the minimum distance from a_i (all equal-distance neighbours, not the first):
+    n_B[j]  = mean of n_A[i] over {i : j in T_A(i)}            (plain mean, not renormalised; an unreferenced b_j never enters)
+    e_AB[i] = mean over j in T_A(i) of ((a_i - b_j) . n_B[j])^2,   e_BA[j] = mean over i in T_B(j) of ((b_j - a_i) . n_A[i])^2
+    mseF = max(mean e_AB, mean e_BA),  PSNR = 10 log10(3 peak^2 / mseF)
+which reproduces the tool to its six printed digits on tie-free and tie-laden clouds (tests/golden/d2_metrics.json).  Exactly duplicated
+points of A are merged as for D1 and take the mean of their normals; the tool's own rule for duplicates that carry DIFFERENT normals was
+not identified (a probe printed 0.919601 / 1.98458, which none of keep-all / mean / first / last / sum / normalised mean gives).
+The normals are not open3d's bit for bit: the neighbour sets agree except at exact distance ties, but the covariance is the centred
+two-pass one and the eigenvector comes from Jacobi sweeps - D2 on estimated normals is this project's number, D2 on given normals the tool's.
 """
 import math
 
@@ -36,6 +48,48 @@ def chamfer_psnr(pc, quant, peak, dropdups=True):
     mse = max(m_ab, m_ba)
     psnr = 10.0 * math.log10(3.0 * peak * peak / mse) if mse > 0 else float("inf")
     return dict(chamfer=chamfer, psnr=psnr, mse_ab=m_ab, mse_ba=m_ba)
+
+
+def estimate_normals(xyz, radius=1.0, max_nn=30, view=(0.0, 0.0, 0.0)):
+    """xyz [n,3] device tensor -> unit normals float64 [n,3], oriented towards `view` (gene_normals.py:43-44)."""
+    return native.estimate_normals(xyz, radius, max_nn, view)[0]
+
+
+def _merge_duplicates(a, normals):
+    """Exactly duplicated points -> one point with the mean of their normals (summed in index order by the tie-set kernel: the
+    duplicates of u are the points at distance 0).  Clouds without duplicates come back untouched, in their own order."""
+    u = _unique_rows(a)
+    if u.shape[0] == a.shape[0]:
+        return a, normals
+    zero = torch.zeros((a.shape[0],), dtype=torch.float64, device=a.device)
+    return u, native.nn_tieset(native.TIE_MEAN_NORMAL, u, a, zero, normals)
+
+
+def d2_terms(a, normals, b):
+    """Per-point terms of the p2plane metric, float64 device tensors, no duplicate handling: (n_B [nb,3], e_AB [na], e_BA [nb])."""
+    dab = native.nn_sqdist(a, b)
+    dba = native.nn_sqdist(b, a)
+    n_b = native.nn_tieset(native.TIE_MEAN_NORMAL, b, a, dab, normals)
+    e_ab = native.nn_tieset(native.TIE_PLANE_ERROR, a, b, dab, n_b)
+    e_ba = native.nn_tieset(native.TIE_PLANE_ERROR, b, a, dba, normals)
+    return n_b, e_ab, e_ba
+
+
+def d2_psnr(pc, normals, quant, peak, dropdups=True):
+    """pc [P,3] with normals [P,3], quant [U,3]: device tensors (compared in float64).  Returns dict(mse_ab, mse_ba, psnr_d2)."""
+    a = pc.to(torch.float64).contiguous()
+    n_a = normals.to(torch.float64).contiguous()
+    b = quant.to(torch.float64).contiguous()
+    if n_a.shape != a.shape:
+        raise native.ScpError(f"d2_psnr: {tuple(n_a.shape)} normals for a cloud of shape {tuple(a.shape)}")
+    if dropdups:
+        a, n_a = _merge_duplicates(a, n_a)
+        b = b if _unique_rows(b).shape[0] == b.shape[0] else _unique_rows(b)
+    _, e_ab, e_ba = d2_terms(a, n_a, b)
+    m_ab, m_ba = float(e_ab.mean().item()), float(e_ba.mean().item())
+    mse = max(m_ab, m_ba)
+    psnr = 10.0 * math.log10(3.0 * peak * peak / mse) if mse > 0 else float("inf")
+    return dict(mse_ab=m_ab, mse_ba=m_ba, psnr_d2=psnr)
 
 
 def dequantize(leaves, qs, offset, spher=False, cylin=False, f32=False):

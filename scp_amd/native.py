@@ -109,6 +109,8 @@ def lib():
         "scp_set_knn_workgroup": (C.c_int, [i32]),
         "scp_knn_debug_buffer": (C.c_int, [_vp]),
         "scp_nn_sqdist_f64": (C.c_int, [_vp, i64, _vp, i64, _vp, _vp]),
+        "scp_estimate_normals_f64": (C.c_int, [_vp, i64, C.c_double, i32, _vp, _vp, _vp, _vp, _vp]),
+        "scp_nn_tieset_f64": (C.c_int, [i32, _vp, i64, _vp, i64, _vp, _vp, _vp, _vp]),
         "scp_edge_gather_max_ld": (C.c_int, [_vp, i64, _vp, i64, _vp, _vp, _vp, i32, i32, i32, i32, _vp, i32, _vp]),
         "scp_embed_gather": (C.c_int, [_vp, _vp, _vp, i64, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp]),
         "scp_packed_plan_sizes": (C.c_int, [_vp, i32, _vp]),
@@ -464,6 +466,35 @@ def _dev_f64(t):
     if not t.is_cuda:
         raise ScpError("device tensor required (there is no CPU path in the product)")
     return t.to(torch.float64).contiguous()
+
+
+TIE_MEAN_NORMAL, TIE_PLANE_ERROR = 0, 1     # include/scp.h: SCP_TIE_*
+
+
+def estimate_normals(xyz, radius=1.0, max_nn=30, view=(0.0, 0.0, 0.0), want_idx=False):
+    """xyz [n,3] device tensor -> (normals float64 [n,3], count int32 [n], idx int32 [n,max_nn] or None): scp_estimate_normals_f64."""
+    x = _dev_f64(xyz)
+    n = x.shape[0]
+    normals = torch.empty((n, 3), dtype=torch.float64, device=x.device)
+    count = torch.empty((n,), dtype=torch.int32, device=x.device)
+    idx = torch.empty((n, int(max_nn)), dtype=torch.int32, device=x.device) if want_idx else None
+    v = (C.c_double * 3)(*[float(c) for c in view])
+    _check(lib().scp_estimate_normals_f64(x.data_ptr(), n, float(radius), int(max_nn), C.cast(v, _vp), normals.data_ptr(), count.data_ptr(),
+                                          None if idx is None else idx.data_ptr(), _stream()), "scp_estimate_normals_f64")
+    return normals, count, idx
+
+
+def nn_tieset(mode, q, p, dmin, nrm):
+    """scp_nn_tieset_f64 on float64 device tensors.  TIE_MEAN_NORMAL: dmin [np], nrm [np,3] of the streamed cloud p -> [nq,3];
+    TIE_PLANE_ERROR: dmin [nq] of the queries, nrm [np,3] of p -> [nq]."""
+    q, p, dmin, nrm = _dev_f64(q), _dev_f64(p), _dev_f64(dmin), _dev_f64(nrm)
+    nq, np_ = q.shape[0], p.shape[0]
+    if nrm.shape != (np_, 3) or dmin.shape != ((np_,) if mode == TIE_MEAN_NORMAL else (nq,)):
+        raise ScpError(f"nn_tieset: dmin {tuple(dmin.shape)} / normals {tuple(nrm.shape)} do not fit {nq} queries against {np_} points")
+    out = torch.empty((nq, 3) if mode == TIE_MEAN_NORMAL else (nq,), dtype=torch.float64, device=q.device)
+    _check(lib().scp_nn_tieset_f64(int(mode), q.data_ptr(), nq, p.data_ptr(), np_, dmin.data_ptr(), nrm.data_ptr(), out.data_ptr(), _stream()),
+           "scp_nn_tieset_f64")
+    return out
 
 
 def embed_gather(ctx, pos, inmap, occ_enc, level_enc, octant_enc):
