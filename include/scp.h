@@ -27,7 +27,7 @@ extern "C" {
 #define SCP_ESTATE (-5)   /* calls made out of order on a handle                            */
 
 #define SCP_MAX_DEPTH 21      /* 3*21 = 63 Morton bits                     */
-#define SCP_MAX_SEGMENTS 62   /* trees built by one scp_geom_build call    */
+#define SCP_MAX_SEGMENTS 62   /* trees built by one scp_geom_build call (15 / 1 when a tree has 20 / 21 levels) */
 
 /* SCP_ABI_VERSION is what this header describes, scp_version() what the loaded library implements; a caller compares the two once
  * after loading (scp_amd/native.py does) instead of finding out through wrong numbers.  History of incompatible changes:

@@ -16,9 +16,14 @@
 #include "scp_internal.h"
 
 #define NLV (SCP_MAX_DEPTH + 2)  // level slots 1..D+1 (slot 0 unused)
-#define SENTINEL_SEG 63
-#define SEG_SHIFT 58
+#define SENTINEL_SEG 63  // in-kernel marker of "no segment" (a filtered-out point's key is all ones whatever the shift)
+#define SEG_SHIFT 58     // segment field of the key for trees of up to 19 levels: 6 bits above 57 Morton bits
 #define WG 256
+
+// Deeper trees (20 and 21 levels = SCP_MAX_DEPTH) need 60 / 63 Morton bits: the segment field moves up and shrinks to 4 bits / 1 bit, so such a
+// build holds at most 15 / 1 trees.  Every kernel that takes a key apart gets the shift of its build as an argument.
+static inline int seg_shift_for(int dmax) { return dmax <= 19 ? SEG_SHIFT : 3 * dmax; }
+static inline int seg_capacity(int shift) { const int bits = 64 - shift; return bits >= 6 ? 62 : (1 << bits) - 1; }
 
 // ------------------------------------------------------------------------------------------------ device tables
 struct SegTab {                 // one per segment, lives in device memory
@@ -207,6 +212,7 @@ struct scp_geom {
     uint64_t *sorted = nullptr;
     int64_t n_keys = 0, total_nodes = 0, total_leaves = 0;
     int nseg = 0, lmax = 0, ntiles = 0;
+    int seg_shift = SEG_SHIFT;    // of the last build: seg_shift_for(its deepest tree)
     bool built = false;
 };
 
@@ -233,14 +239,14 @@ __global__ __launch_bounds__(WG) void seg_minmax_kernel(const int32_t *__restric
     }
 }
 
-__global__ __launch_bounds__(WG) void morton_key_kernel(const int32_t *__restrict__ q, const SegTab *__restrict__ tab,
+__global__ __launch_bounds__(WG) void morton_key_kernel(const int32_t *__restrict__ q, const SegTab *__restrict__ tab, int seg_shift,
                                                        uint64_t *__restrict__ keys) {
     const SegTab &s = tab[blockIdx.y];
     const int D = s.depth;
     for (int64_t i = (int64_t)blockIdx.x * WG + threadIdx.x; i < s.pt_count; i += (int64_t)gridDim.x * WG) {
         const int64_t g = s.pt_begin + i;
         const uint32_t x = (uint32_t)q[3 * g], y = (uint32_t)q[3 * g + 1], z = (uint32_t)q[3 * g + 2];
-        uint64_t key = ((uint64_t)blockIdx.y << SEG_SHIFT) | (spread3(x) << 2) | (spread3(y) << 1) | spread3(z);
+        uint64_t key = ((uint64_t)blockIdx.y << seg_shift) | (spread3(x) << 2) | (spread3(y) << 1) | spread3(z);
         // rho-shell filter, Octree.py:188: the top path_len bits of the x axis must equal the path
         if (s.path_len > 0 && (int)(x >> (D - s.path_len)) != s.path_bits) key = ~0ull;
         keys[s.key_begin + i] = key;
@@ -248,37 +254,37 @@ __global__ __launch_bounds__(WG) void morton_key_kernel(const int32_t *__restric
 }
 
 // number of leading 3-bit digits two keys of the same segment share (D = all digits -> duplicate point)
-__device__ __forceinline__ int shared_digits(uint64_t a, uint64_t b, int D) {
-    const uint64_t x = (a ^ b) & ((1ull << SEG_SHIFT) - 1ull);
+__device__ __forceinline__ int shared_digits(uint64_t a, uint64_t b, int D, int seg_shift) {
+    const uint64_t x = (a ^ b) & ((1ull << seg_shift) - 1ull);
     if (x == 0) return D;
     const int hb = 63 - __clzll((long long)x);  // highest differing bit, < 3D
     return D - 1 - hb / 3;
 }
 
 // lowest tree level at which sorted key i starts a new node (1 => segment start, D+2 => duplicate: never)
-__device__ __forceinline__ int head_level(const uint64_t *__restrict__ keys, int64_t i, int64_t n, const SegTab *__restrict__ tab,
+__device__ __forceinline__ int head_level(const uint64_t *__restrict__ keys, int64_t i, int64_t n, const SegTab *__restrict__ tab, int seg_shift,
                                           int &seg, int &D, uint64_t &key) {
     seg = SENTINEL_SEG; D = 0; key = ~0ull;
     if (i >= n) return 1 << 20;
     key = keys[i];
-    seg = (int)(key >> SEG_SHIFT);
-    if (seg == SENTINEL_SEG) return 1 << 20;
+    if (key == ~0ull) return 1 << 20;
+    seg = (int)(key >> seg_shift);
     D = tab[seg].depth;
     if (i == 0) return 1;
     const uint64_t prev = keys[i - 1];
-    if ((int)(prev >> SEG_SHIFT) != seg) return 1;
-    return shared_digits(key, prev, D) + 2;
+    if ((int)(prev >> seg_shift) != seg) return 1;
+    return shared_digits(key, prev, D, seg_shift) + 2;
 }
 
 // T1: per-block head counts for every level, laid out [level][block]
-__global__ __launch_bounds__(WG) void tree_count_kernel(const uint64_t *__restrict__ keys, int64_t n, const SegTab *__restrict__ tab,
+__global__ __launch_bounds__(WG) void tree_count_kernel(const uint64_t *__restrict__ keys, int64_t n, const SegTab *__restrict__ tab, int seg_shift,
                                                        int lmax, uint32_t *__restrict__ blkcnt, int nblk) {
     __shared__ uint32_t cnt[NLV];
     if (threadIdx.x < NLV) cnt[threadIdx.x] = 0;
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * WG + threadIdx.x;
     int seg, D; uint64_t key;
-    const int hl = head_level(keys, i, n, tab, seg, D, key);
+    const int hl = head_level(keys, i, n, tab, seg_shift, seg, D, key);
     for (int L = 1; L <= lmax; ++L) {
         const uint64_t b = __ballot(hl <= L && L <= D + 1);
         if ((threadIdx.x & 63) == 0 && b) atomicAdd(&cnt[L], (uint32_t)__popcll(b));
@@ -308,12 +314,12 @@ __device__ __forceinline__ void level_ranks(int hl, int D, int lmax, const uint3
 }
 
 // T2: ranks of every segment's first key -> tab[s].rank0[L]
-__global__ __launch_bounds__(WG) void tree_segrank_kernel(const uint64_t *__restrict__ keys, int64_t n, SegTab *__restrict__ tab, int lmax,
+__global__ __launch_bounds__(WG) void tree_segrank_kernel(const uint64_t *__restrict__ keys, int64_t n, SegTab *__restrict__ tab, int seg_shift, int lmax,
                                                          const uint32_t *__restrict__ blkscan, int nblk) {
     __shared__ uint32_t wc[NLV][4];
     const int64_t i = (int64_t)blockIdx.x * WG + threadIdx.x;
     int seg, D; uint64_t key;
-    const int hl = head_level(keys, i, n, tab, seg, D, key);
+    const int hl = head_level(keys, i, n, tab, seg_shift, seg, D, key);
     uint32_t rank[NLV];
     level_ranks(hl, D, lmax, blkscan, nblk, wc, rank);
     if (hl == 1)
@@ -321,19 +327,19 @@ __global__ __launch_bounds__(WG) void tree_segrank_kernel(const uint64_t *__rest
 }
 
 // T3: every head writes its node; heads of the leaf pseudo-level D+1 write the leaf key / last digit
-__global__ __launch_bounds__(WG) void tree_write_kernel(const uint64_t *__restrict__ keys, int64_t n, const SegTab *__restrict__ tab, int lmax,
+__global__ __launch_bounds__(WG) void tree_write_kernel(const uint64_t *__restrict__ keys, int64_t n, const SegTab *__restrict__ tab, int seg_shift, int lmax,
                                                        const uint32_t *__restrict__ blkscan, int nblk, uint8_t *__restrict__ level,
                                                        uint8_t *__restrict__ octant, int32_t *__restrict__ parent, int32_t *__restrict__ pos,
                                                        int32_t *__restrict__ fchild, uint64_t *__restrict__ leafkey, uint8_t *__restrict__ leafoct) {
     __shared__ uint32_t wc[NLV][4];
     const int64_t i = (int64_t)blockIdx.x * WG + threadIdx.x;
     int seg, D; uint64_t key;
-    const int hl = head_level(keys, i, n, tab, seg, D, key);
+    const int hl = head_level(keys, i, n, tab, seg_shift, seg, D, key);
     uint32_t rank[NLV];
     level_ranks(hl, D, lmax, blkscan, nblk, wc, rank);
     if (seg == SENTINEL_SEG || hl > D + 1) return;
     const SegTab &s = tab[seg];
-    const uint64_t m = key & ((1ull << SEG_SHIFT) - 1ull);
+    const uint64_t m = key & ((1ull << seg_shift) - 1ull);
     const uint32_t x = compact3(m >> 2), y = compact3(m >> 1), z = compact3(m);
     for (int L = hl; L <= D; ++L) {
         const int64_t nd = s.node_base + s.level_off[L] + ((int64_t)rank[L] - s.rank0[L]);
@@ -442,7 +448,7 @@ static int geom_build_sorted(scp_geom *g, scp_segment_info *info, int dmax, hipS
     int rc;
     int plo[16], pnb[16], np = 0;
     for (int b = 0; b < 3 * dmax; b += 8) { plo[np] = b; pnb[np] = (3 * dmax - b) < 8 ? (3 * dmax - b) : 8; ++np; }
-    plo[np] = SEG_SHIFT; pnb[np] = 6; ++np;  // segment id (and the all-ones sentinel of filtered points) last
+    plo[np] = g->seg_shift; pnb[np] = std::min(6, 64 - g->seg_shift); ++np;  // segment id (and the all-ones sentinel of filtered points) last
     rc = scp_radix_sort_u64(g->keys_a.as<uint64_t>(), g->keys_b.as<uint64_t>(), nk, plo, pnb, np, &g->radix, st, &g->sorted, first_hist_done);
     if (rc) return rc;
 
@@ -451,11 +457,11 @@ static int geom_build_sorted(scp_geom *g, scp_segment_info *info, int dmax, hipS
     g->ntiles = nblk;
     if ((rc = g->blkcnt.reserve(sizeof(uint32_t) * (size_t)(lmax + 2) * nblk + 64))) return rc;
     uint32_t *blk = g->blkcnt.as<uint32_t>();
-    hipLaunchKernelGGL(tree_count_kernel, dim3(nblk), dim3(WG), 0, st, (const uint64_t *)g->sorted, nk, (const SegTab *)dtab, lmax, blk, nblk);
+    hipLaunchKernelGGL(tree_count_kernel, dim3(nblk), dim3(WG), 0, st, (const uint64_t *)g->sorted, nk, (const SegTab *)dtab, g->seg_shift, lmax, blk, nblk);
     LAUNCH_CHECK();
     scp_launch_scan_u32(blk, (int64_t)(lmax + 2) * nblk, st);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(tree_segrank_kernel, dim3(nblk), dim3(WG), 0, st, (const uint64_t *)g->sorted, nk, dtab, lmax, (const uint32_t *)blk, nblk);
+    hipLaunchKernelGGL(tree_segrank_kernel, dim3(nblk), dim3(WG), 0, st, (const uint64_t *)g->sorted, nk, dtab, g->seg_shift, lmax, (const uint32_t *)blk, nblk);
     LAUNCH_CHECK();
     std::vector<SegTab> back(nseg);
     std::vector<uint32_t> lvl_first(lmax + 2, 0u);
@@ -510,7 +516,7 @@ static int geom_build_sorted(scp_geom *g, scp_segment_info *info, int dmax, hipS
     }
     if (!g->h2d_done) HIP_TRY(hipEventCreateWithFlags(&g->h2d_done, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(g->h2d_done, st));
-    hipLaunchKernelGGL(tree_write_kernel, dim3(nblk), dim3(WG), 0, st, (const uint64_t *)g->sorted, nk, (const SegTab *)dtab, lmax,
+    hipLaunchKernelGGL(tree_write_kernel, dim3(nblk), dim3(WG), 0, st, (const uint64_t *)g->sorted, nk, (const SegTab *)dtab, g->seg_shift, lmax,
                        (const uint32_t *)blk, nblk, g->level.as<uint8_t>(), g->octant.as<uint8_t>(), g->parent.as<int32_t>(),
                        g->pos.as<int32_t>(), g->fchild.as<int32_t>(), g->leafkey.as<uint64_t>(), g->leafoct.as<uint8_t>());
     LAUNCH_CHECK();
@@ -585,7 +591,7 @@ extern "C" int scp_geom_build(scp_geom *g, const int32_t *q, int64_t n, const sc
         if (mn < 0) return SCP_EINVAL;
         const int d = depth_of(mx);
         // depth 0 (all-zero cloud) aborts inside the reference as well
-        if (d == 0 || d > SCP_MAX_DEPTH - 2 || g->segs[s].path_len > d) return SCP_EINVAL;
+        if (d == 0 || d > SCP_MAX_DEPTH || g->segs[s].path_len > d) return SCP_EINVAL;
         g->segs[s].depth = d;
         if (d > dmax) dmax = d;
         memset(&info[s], 0, sizeof(info[s]));
@@ -593,9 +599,12 @@ extern "C" int scp_geom_build(scp_geom *g, const int32_t *q, int64_t n, const sc
         info[s].max_coord = mx;
     }
 
+    g->seg_shift = seg_shift_for(dmax);
+    if (nseg > seg_capacity(g->seg_shift)) return SCP_EINVAL;
+
     // --- keys -----------------------------------------------------------------------------------------------
     HIP_TRY(hipMemcpyAsync(dtab, g->segs.data(), sizeof(SegTab) * nseg, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(morton_key_kernel, dim3(grid_for(maxcount), nseg), dim3(WG), 0, st, q, (const SegTab *)dtab, g->keys_a.as<uint64_t>());
+    hipLaunchKernelGGL(morton_key_kernel, dim3(grid_for(maxcount), nseg), dim3(WG), 0, st, q, (const SegTab *)dtab, g->seg_shift, g->keys_a.as<uint64_t>());
     LAUNCH_CHECK();
     return geom_build_sorted(g, info, dmax, st, false);
 }
@@ -674,7 +683,7 @@ static inline int32_t quant1_host(float t, const QuantParams &p, int k) {      /
     return (int32_t)rint(qd);
 }
 
-__global__ __launch_bounds__(WG) void front_key_kernel(const float *__restrict__ tr, const FrontSeg *__restrict__ segs, int nseg, int64_t nk,
+__global__ __launch_bounds__(WG) void front_key_kernel(const float *__restrict__ tr, const FrontSeg *__restrict__ segs, int nseg, int64_t nk, int seg_shift,
                                                       uint64_t *__restrict__ keys, int32_t *__restrict__ q_out /* optional [nk][3] */,
                                                       uint32_t mask0, uint32_t *__restrict__ counts, int ntiles) {
     __shared__ uint32_t hist[256];
@@ -705,7 +714,7 @@ __global__ __launch_bounds__(WG) void front_key_kernel(const float *__restrict__
         const float *t = tr + 3 * (sg.tr_begin + i);
         const int32_t qx = quant1(t[0], sg.qp, 0), qy = quant1(t[1], sg.qp, 1), qz = quant1(t[2], sg.qp, 2);
         if (q_out) { q_out[3 * k] = qx; q_out[3 * k + 1] = qy; q_out[3 * k + 2] = qz; }
-        uint64_t key = ((uint64_t)(s0 + si) << SEG_SHIFT) | (spread3((uint32_t)qx) << 2) | (spread3((uint32_t)qy) << 1) | spread3((uint32_t)qz);
+        uint64_t key = ((uint64_t)(s0 + si) << seg_shift) | (spread3((uint32_t)qx) << 2) | (spread3((uint32_t)qy) << 1) | spread3((uint32_t)qz);
         if (sg.path_len > 0 && (int)((uint32_t)qx >> (sg.depth - sg.path_len)) != sg.path_bits) key = ~0ull;
         keys[k] = key;
         atomicAdd(&hist[(uint32_t)key & mask0], 1u);
@@ -795,7 +804,7 @@ extern "C" int scp_geom_build_xyz(scp_geom *g, const float *const *frames, const
             qi.max_coord = mx; qi.min_coord = mn;
             if (mn < 0) return SCP_EINVAL;
             const int d = depth_of(mx);
-            if (d == 0 || d > SCP_MAX_DEPTH - 2 || g->segs[sidx].path_len > d) return SCP_EINVAL;
+            if (d == 0 || d > SCP_MAX_DEPTH || g->segs[sidx].path_len > d) return SCP_EINVAL;
             g->segs[sidx].depth = d;
             if (d > dmax) dmax = d;
             memset(&info[sidx], 0, sizeof(info[sidx]));
@@ -806,6 +815,8 @@ extern "C" int scp_geom_build_xyz(scp_geom *g, const float *const *frames, const
             o.depth = d; o.path_len = g->segs[sidx].path_len; o.path_bits = g->segs[sidx].path_bits; o.pad = 0;
         }
     }
+    g->seg_shift = seg_shift_for(dmax);
+    if (nseg > seg_capacity(g->seg_shift)) return SCP_EINVAL;
     HIP_TRY(hipMemcpyAsync(dfs, fs.data(), sizeof(FrontSeg) * nseg, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(g->segtab.p, g->segs.data(), sizeof(SegTab) * nseg, hipMemcpyHostToDevice, st));
     int ntiles = 0;
@@ -814,7 +825,7 @@ extern "C" int scp_geom_build_xyz(scp_geom *g, const float *const *frames, const
     const int nb0 = 3 * dmax < 8 ? 3 * dmax : 8;
     {
         SCP_PROF(SCP_PROF_GEOM, st, 12.0 * g->n_keys + 8.0 * g->n_keys);
-        hipLaunchKernelGGL(front_key_kernel, dim3(ntiles), dim3(WG), 0, st, g->tr.as<float>(), (const FrontSeg *)dfs, nseg, g->n_keys,
+        hipLaunchKernelGGL(front_key_kernel, dim3(ntiles), dim3(WG), 0, st, g->tr.as<float>(), (const FrontSeg *)dfs, nseg, g->n_keys, g->seg_shift,
                            g->keys_a.as<uint64_t>(), q_out, (1u << nb0) - 1u, counts, ntiles);
     }
     LAUNCH_CHECK();
@@ -836,10 +847,10 @@ extern "C" int scp_geom_emit_nodes(scp_geom *g, uint8_t *occ, uint8_t *level, ui
     return SCP_OK;
 }
 
-__global__ __launch_bounds__(WG) void leaves_kernel(const uint64_t *__restrict__ leafkey, int64_t base, int64_t n, int32_t *__restrict__ pts) {
+__global__ __launch_bounds__(WG) void leaves_kernel(const uint64_t *__restrict__ leafkey, int64_t base, int64_t n, int seg_shift, int32_t *__restrict__ pts) {
     const int64_t i = (int64_t)blockIdx.x * WG + threadIdx.x;
     if (i >= n) return;
-    const uint64_t m = leafkey[base + i] & ((1ull << SEG_SHIFT) - 1ull);
+    const uint64_t m = leafkey[base + i] & ((1ull << seg_shift) - 1ull);
     pts[3 * i] = (int32_t)compact3(m >> 2); pts[3 * i + 1] = (int32_t)compact3(m >> 1); pts[3 * i + 2] = (int32_t)compact3(m);
 }
 
@@ -848,7 +859,7 @@ extern "C" int scp_geom_emit_leaves(scp_geom *g, int32_t seg, int32_t *pts, void
     if (seg < 0 || seg >= g->nseg || !pts) return SCP_EINVAL;
     const SegTab &t = g->segs[seg];
     hipLaunchKernelGGL(leaves_kernel, dim3((int)cdiv64(t.n_leaves, WG)), dim3(WG), 0, (hipStream_t)stream, g->leafkey.as<uint64_t>(),
-                       t.leaf_base, t.n_leaves, pts);
+                       t.leaf_base, t.n_leaves, g->seg_shift, pts);
     LAUNCH_CHECK();
     return SCP_OK;
 }
@@ -860,6 +871,15 @@ __device__ __forceinline__ void ancestors(const int32_t *__restrict__ parent, in
     a[2] = parent[nd];
     a[1] = a[2] >= 0 ? parent[a[2]] : -1;
     a[0] = a[1] >= 0 ? parent[a[1]] : -1;
+}
+
+// The LAST CHUNK of a segment's context tables is its deepest level that has coded rows: `depth`, or `depth - 1` when drop_last leaves the
+// last level empty (a one-leaf shell: the level held the dropped node alone).  encode_dataset_ehem.py:86 clips the level bytes of that
+// chunk and the multi-level position normalisation divides without the epsilon there; the reference sees the chunk in its record file,
+// which ends one level early for such a shell.
+__host__ __device__ __forceinline__ int last_coded_level(const SegTab &s) {
+    const int D = s.depth;
+    return (s.drop_last && D > 1 && s.level_off[D + 1] - s.level_off[D] == 1) ? D - 1 : D;
 }
 
 // reference record, data_preprocess.py:74: int64 [rows][4][6] = (occ, level, octant, x, y, z); pad rows (256,0,0,0,0,0)
@@ -898,14 +918,14 @@ extern "C" int scp_geom_krecords_i64(scp_geom *g, int32_t seg, int64_t *out, voi
 __global__ __launch_bounds__(WG) void ctx_ehem_kernel(const uint8_t *__restrict__ occ, const uint8_t *__restrict__ level,
                                                      const uint8_t *__restrict__ octant, const int32_t *__restrict__ parent,
                                                      const int32_t *__restrict__ pos, const int32_t *__restrict__ posmm /* [NLV][2] of this segment */,
-                                                     int64_t base, int64_t rows, int depth, int pos_mode, int lidar_level,
+                                                     int64_t base, int64_t rows, int depth, int last_level, int pos_mode, int lidar_level,
                                                      uint8_t *__restrict__ ctx, float *__restrict__ posn, uint8_t *__restrict__ sym) {
     const int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x;
     if (r >= rows) return;
     int64_t a[4];
     ancestors(parent, base + r, a);
     const int L = level[base + r];
-    const bool last = (L == depth);
+    const bool last = (L == last_level);
     uint8_t c[12];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -955,8 +975,8 @@ extern "C" int scp_geom_context_ehem(scp_geom *g, int32_t seg, int32_t pos_mode,
     const int32_t *mm = g->posmm.as<int32_t>() + (size_t)seg * NLV * 2;
     if (rows > 0) {
         hipLaunchKernelGGL(ctx_ehem_kernel, dim3((int)cdiv64(rows, WG)), dim3(WG), 0, st, g->occ.as<uint8_t>(), g->level.as<uint8_t>(),
-                           g->octant.as<uint8_t>(), g->parent.as<int32_t>(), g->pos.as<int32_t>(), mm, t.node_base, rows, t.depth, pos_mode,
-                           lidar_level, ctx, pos, sym);
+                           g->octant.as<uint8_t>(), g->parent.as<int32_t>(), g->pos.as<int32_t>(), mm, t.node_base, rows, t.depth, last_coded_level(t),
+                           pos_mode, lidar_level, ctx, pos, sym);
         LAUNCH_CHECK();
     }
     if (pos_mm) {
@@ -978,7 +998,7 @@ __global__ __launch_bounds__(WG) void ctx_ehem_all_kernel(const SegTab *__restri
                                                          int64_t *__restrict__ pos_mm_out, const int64_t *__restrict__ mm_base) {
     const SegTab &s = tab[blockIdx.y];
     const int64_t rows = s.n_nodes - s.drop_last, rb = row_base[blockIdx.y];
-    const int depth = s.depth;
+    const int depth = s.depth, last_level = last_coded_level(s);
     const int32_t *mm = posmm + (size_t)blockIdx.y * NLV * 2;
     if (pos_mm_out && blockIdx.x == 0 && (int)threadIdx.x < depth) {
         const int L = threadIdx.x + 1;
@@ -990,7 +1010,7 @@ __global__ __launch_bounds__(WG) void ctx_ehem_all_kernel(const SegTab *__restri
         int64_t a[4];
         ancestors(parent, nd, a);
         const int L = level[nd];
-        const bool last = (L == depth);
+        const bool last = (L == last_level);
         uint8_t c[12];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -1008,7 +1028,7 @@ __global__ __launch_bounds__(WG) void ctx_ehem_all_kernel(const SegTab *__restri
         cw[2] = c[8] | (c[9] << 8) | (c[10] << 16) | ((uint32_t)c[11] << 24);
         if (sym_coded) {
             const int64_t l0 = s.level_off[L];
-            const int64_t nl = s.level_off[L + 1] - l0 - ((last && s.drop_last) ? 1 : 0);      // coded rows of this level
+            const int64_t nl = s.level_off[L + 1] - l0 - ((L == depth && s.drop_last) ? 1 : 0);      // coded rows of this level
             const int64_t i = r - l0, w0 = (i / cs) * cs, p = i - w0;
             const int64_t cw_len = (nl - w0) < cs ? (nl - w0) : cs, ne = (cw_len + 1) >> 1;
             sym_coded[rb + l0 + w0 + ((p & 1) ? ne + (p >> 1) : (p >> 1))] = (uint8_t)(occ[nd] - 1);
@@ -1051,7 +1071,8 @@ extern "C" int scp_geom_context_ehem_all(scp_geom *g, int32_t pos_mode, int32_t 
     return SCP_OK;
 }
 
-// OctAttention context, encode_dataset.py:32-55: ctx = (occ-1, level, octant) x 4; pos = xyz / 2^D for all four rows
+// OctAttention context, encode_dataset.py:32-55: ctx = (occ-1, level, octant) x 4; pos = xyz / 2^(deepest level of the records) for all
+// four rows: `depth` is last_coded_level() of the segment
 __global__ __launch_bounds__(WG) void ctx_octattn_kernel(const uint8_t *__restrict__ occ, const uint8_t *__restrict__ level,
                                                         const uint8_t *__restrict__ octant, const int32_t *__restrict__ parent,
                                                         const int32_t *__restrict__ pos, int64_t base, int64_t rows, int depth,
@@ -1085,7 +1106,7 @@ extern "C" int scp_geom_context_octattn(scp_geom *g, int32_t seg, uint8_t *ctx, 
     if (rows <= 0) return SCP_OK;
     hipLaunchKernelGGL(ctx_octattn_kernel, dim3((int)cdiv64(rows, WG)), dim3(WG), 0, (hipStream_t)stream, g->occ.as<uint8_t>(),
                        g->level.as<uint8_t>(), g->octant.as<uint8_t>(), g->parent.as<int32_t>(), g->pos.as<int32_t>(), t.node_base, rows,
-                       t.depth, ctx, pos, sym);
+                       last_coded_level(t), ctx, pos, sym);
     LAUNCH_CHECK();
     return SCP_OK;
 }

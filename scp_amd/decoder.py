@@ -657,9 +657,15 @@ class FrameDecoder:
         octant = torch.ones(1, dtype=torch.uint8, device=dev)
         pos = torch.zeros((1, 3), dtype=torch.int32, device=dev)
 
+        # the last chunk is the deepest level with coded rows: a one-leaf shell's last level holds the dropped node alone, its (min, max)
+        # row still carries the build's initial words (min > max), and the clip and the epsilon-free division move up one level
+        last_coded = depth
+        if self.mullevel and self.polar and depth > 1 and float(pos_mm[depth - 1][0]) > float(pos_mm[depth - 1][1]):
+            last_coded = depth - 1
+
         def level_params(L):
             """(lv, ancestor level clamp, mn, den) of level L's inputs."""
-            last = L == depth
+            last = L == last_coded
             lv = min(L, self.lidar_level) if last else L                      # encode_dataset_ehem.py:86 clips the last chunk
             if self.polar:
                 mn, mx = float(pos_mm[L - 1][0]), float(pos_mm[L - 1][1])

@@ -701,9 +701,8 @@ class OctAttnFrameEncoder(_FrontEnd):
             counts = self.geom.level_counts(s)
             if self.mullevel:
                 counts[-1] -= 1                      # the records drop the last BFS node (Octree.py:259-262)
-                if counts[-1] == 0:                  # ... and with it the deepest level: positions are over 2^(max level present)
+                if counts[-1] == 0:                  # ... and with it the deepest level (the kernel's positions are over 2^(max level present))
                     counts.pop()
-                    pos = pos * 2.0
             syms.append(sym)
             cuts = counts if self.level_wise else [ctx.shape[0]]
             a = 0

@@ -761,23 +761,33 @@ def test_degenerate_frames_roundtrip(enc_parts, case, spher):
 @pytest.mark.gpu
 def test_mullevel_one_leaf_shells_roundtrip(enc_parts):
     """Three points, one per rho shell: every shell's octree is one chain whose last level holds only the dropped node (n == 1,
-    symbol unknown, no children: `native.decode_expand` with m == 0).  The decoder regenerates the leaves of all three shells."""
+    symbol unknown, no children: `native.decode_expand` with m == 0).  The decoder regenerates the leaves of all three shells.
+    Second frame: the far point lies beyond 200 m, so the far shell's chain is deeper than lidar_level + 1 and off the diagonal - its
+    records end at depth - 1, which is the chunk encode_dataset_ehem.py:86 clips; encoder and decoder must both clip THAT level."""
     from oracle import scp_oracle as orc
     from scp_amd.decoder import FrameDecoder
     from scp_amd.encoder import FrameEncoder
     model, dev = enc_parts
-    xyz = np.array([[r * 0.8, r * 0.6, -1.0] for r in (5, 30, 70)], np.float32)
-    shells = orc.mullevel_shells(xyz, 12, "spher")
-    assert [s["tree"].n - s["records"].shape[0] for s in shells] == [1, 1, 1] and all(s["tree"].n == s["tree"].depth for s in shells)
-    enc = FrameEncoder(model, "kitti", 12, spher=True, mullevel=True, device=dev)
-    res = enc.encode(xyz)
-    out = FrameDecoder(model, 12, mullevel=True, polar=True, device=dev).decode(res["bytes"], res["n_levels"], res["pos_mm"])
-    assert len(out) == 3
-    for k, (codes, leaves) in enumerate(out):
-        occ = shells[k]["tree"].occ
-        got = torch.cat(codes).cpu().numpy()
-        assert np.array_equal(got[:-1], occ[:-1]) and got[-1] == 0            # the dropped node's occupancy is never coded
-        assert leaves.shape[0] == 0                                            # ... so its leaf is not regenerated (decode_ehem_mullevel.py:100-130)
+    for radii in ((5, 30, 70), (50, 150, 300)):
+        xyz = np.array([[r * 0.8, r * 0.6, -1.0] for r in radii], np.float32)
+        shells = orc.mullevel_shells(xyz, 12, "spher")
+        assert [s["tree"].n - s["records"].shape[0] for s in shells] == [1, 1, 1] and all(s["tree"].n == s["tree"].depth for s in shells)
+        if radii[-1] > 200:
+            far = shells[2]
+            depth = far["tree"].depth
+            assert depth > 12 + 1 and int(far["records"][:, 3, 1].max()) == depth - 1
+            assert len(set(far["tree"].pos[depth - 2].tolist())) > 1                      # the last coded node is off the diagonal: no 0 / 0
+            _, pos, _, data, _ = orc.ehem_level_split(far["records"], 12, True, mul=True)
+            assert (data[-1][:, -1, 0] == 12).all() and len(data) == depth - 1 and np.isfinite(pos[-1]).all()
+        enc = FrameEncoder(model, "kitti", 12, spher=True, mullevel=True, device=dev)
+        res = enc.encode(xyz)
+        out = FrameDecoder(model, 12, mullevel=True, polar=True, device=dev).decode(res["bytes"], res["n_levels"], res["pos_mm"])
+        assert len(out) == 3
+        for k, (codes, leaves) in enumerate(out):
+            occ = shells[k]["tree"].occ
+            got = torch.cat(codes).cpu().numpy()
+            assert np.array_equal(got[:-1], occ[:-1]) and got[-1] == 0            # the dropped node's occupancy is never coded
+            assert leaves.shape[0] == 0                                            # ... so its leaf is not regenerated (decode_ehem_mullevel.py:100-130)
 
 
 @pytest.mark.gpu
