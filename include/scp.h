@@ -43,7 +43,7 @@ extern "C" {
  *   220  GELU (round 5, numeric profile ehem/5): max(y, 0) - |y| exp(-beta y^2) / P4(|y|) instead of the degree-12 erf polynomial, in every
  *        kernel that applies it; scp_swin_post_attn expects fc1 scaled by scp_gelu_prescale() and fc2 by its inverse.
  *        (additive, no new version: scp_decode_expand, scp_linear_split_f16_max, scp_row_scale_from_max, scp_octattn_attention_f16x3_vmax;
- *        round 6: scp_linear_split_hier2, scp_mlp3_rows; scp_octattn_attention_rowinv, scp_decode_expand_octattn, scp_octattn_attention_rowinv_step - existing entry points keep their bits, the EHEM model's numeric profile moved to ehem/6
+ *        round 6: scp_linear_split_hier2, scp_mlp3_rows; scp_octattn_attention_rowinv, scp_decode_expand_octattn, scp_octattn_attention_rowinv_step, scp_decode_expand_batch - existing entry points keep their bits, the EHEM model's numeric profile moved to ehem/6
  *        because models/packed.py now calls the two new ones; D2 PSNR: scp_estimate_normals_f64, scp_nn_tieset_f64.) */
 #define SCP_ABI_VERSION 220
 SCP_API int scp_version(void);
@@ -498,6 +498,28 @@ SCP_API int scp_packed_plan(const int64_t *lengths, int32_t W, int64_t *tables_d
 SCP_API int scp_decode_expand(const int64_t *sym, const int64_t *cum, const int32_t *pos, const uint8_t *anc, const uint8_t *octant, int64_t n,
                               int32_t L, int32_t shift, int32_t lv_next, int32_t lv_clamp, int32_t polar, double mn, double den, int32_t *cpos,
                               uint8_t *canc, uint8_t *coct, uint8_t *cctx, float *cposn, uint8_t *occ8, void *stream);
+
+/* The same for the decoded levels of S (1 .. 64) streams at once, ONE launch (the lockstep decoder, scp_amd/decoder.py: EhemBatchDecoder).
+ * The parents of the streams ("segments") lie back to back in sym / pos / anc / octant [n]; cum is the inclusive scan of popcount(sym + 1)
+ * over the WHOLE array.  seg[S] (host memory): per segment its first parent row and parent count (first[0] = 0, contiguous, count >= 1),
+ * scp_decode_expand's scalars (L, shift, lv_next, lv_clamp, polar, mn, den: the streams differ in depth, lidar level and coordinate
+ * system), cfirst = its first child row (= the scan's value before the segment; the children of all segments back to back, M in all)
+ * and coded <= its child count = the children that get model-input rows.  Child c of segment s: state row cfirst[s] + c of cpos / canc /
+ * coct [M]; for c < coded[s], input row wbase[(c / cs) * S + s] + c % cs of cctx u8[T][12] / cposn f32[T][3] - wbase i64[K][S] (host
+ * memory) = the first row of window k of segment s in the caller's window order (-1: no such window).  Per-element arithmetic and bits
+ * are scp_decode_expand's.  table_dev: the caller's DEVICE copy of both tables, uploaded on `stream` before the call - seg[S] at byte 0,
+ * wbase[K][S] at byte 64 * sizeof(scp_expand_seg); the entry copies nothing and waits for nothing.  Everything is checked on the
+ * host (on the host tables) before any launch (SCP_EINVAL): pointers, S, cs, K, the level and shift ranges of scp_decode_expand, the segment table's
+ * consistency with n and M, and that every window a coded child lands in lies inside [0, T).  Additive: no new ABI version. */
+typedef struct scp_expand_seg {
+    int64_t first, count, cfirst, coded;
+    int32_t L, shift, lv_next, lv_clamp, polar, reserved;
+    double mn, den;
+} scp_expand_seg;
+SCP_API int scp_decode_expand_batch(const int64_t *sym, const int64_t *cum, const int32_t *pos, const uint8_t *anc, const uint8_t *octant,
+                                    int64_t n, const scp_expand_seg *seg, int32_t S, int32_t cs, const int64_t *wbase, int32_t K, int64_t M,
+                                    int64_t T, void *table_dev, int32_t *cpos, uint8_t *canc, uint8_t *coct, uint8_t *cctx, float *cposn,
+                                    uint8_t *occ8, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Swin blocks on the row-chain kernels (csrc/rowchain.hip): a workgroup keeps 128 token rows in registers as the B operand of

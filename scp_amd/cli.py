@@ -402,6 +402,9 @@ def get_decode_args(argv=None):
     p.add_argument("--out_dir", type=str, default=None)
     p.add_argument("--lidar_level", type=int, default=None, help="overrides the side-info file / the reference's level-count rule")
     p.add_argument("--type", type=str, default=None, choices=[None, "obj", "kitti", "ford"])
+    p.add_argument("--streams", type=_streams_arg, default=1,
+                   help="decode this many files at a time in lockstep, one packed forward serving one level of each (1 .. 64; default 1: one "
+                        "file after the other).  With more than one, the time printed per file is the total over the number of files")
     return p.parse_args(argv)
 
 
@@ -538,7 +541,8 @@ def decode_main(argv=None, mullevel=False):
     test_output directory (`find_stream`: the exact name the encoder wrote, sequence included), decode it with the side info of `extract_info`,
     check the occupancy codes against the `--preproc_path` record files when they exist (the reference asserts this window by
     window, decode_ehem.py:184), rebuild the points (DeOctree -> de-quantise -> spher2cart / cylin2cart) and write
-    `<test_output>/<stream stem>.ply` (KITTI: `<sequence><frame>.ply`, so two sequences never overwrite each other)."""
+    `<test_output>/<stream stem>.ply` (KITTI: `<sequence><frame>.ply`, so two sequences never overwrite each other).  `--streams S` (S > 1)
+    decodes the files S at a time in lockstep (decoder.decode_files): the same checks, files and printed lines per file."""
     args = get_decode_args(argv)
     if not torch.cuda.is_available():
         raise native.ScpError("decode needs an MI355X: the SCP hot path has no CPU fallback")
@@ -565,14 +569,27 @@ def decode_main(argv=None, mullevel=False):
     else:
         files = expand_files(files)
     elapsed, results = 0.0, []
+    outs = None
+    if args.streams > 1:
+        # every stream is located first; then the files are decoded `streams` at a time in lockstep (every side-info file checked before the
+        # first is decoded), and the loop below reports them one by one
+        from .decoder import decode_files
+        found = [find_stream(out_root, ori) for ori in files]
+        t0 = time.time()
+        outs = decode_files([out_root + name for name, _ in found], model, args.streams, args.lidar_level, args.type, mullevel, dev)
+        torch.cuda.synchronize()
+        each = (time.time() - t0) / max(len(files), 1)
     for i, ori in enumerate(files):
         print(f"{i}/{len(files)}")
-        name, stem = find_stream(out_root, ori)                # the stem that matched, not string surgery on the stream name
-        binfile = out_root + name
-        t0 = time.time()
-        out = decode_file(binfile, model, args.lidar_level, args.type, mullevel, dev)
-        torch.cuda.synchronize()
-        t = time.time() - t0
+        if outs is not None:
+            (name, stem), out, t = found[i], outs[i], each
+        else:
+            name, stem = find_stream(out_root, ori)            # the stem that matched, not string surgery on the stream name
+            binfile = out_root + name
+            t0 = time.time()
+            out = decode_file(binfile, model, args.lidar_level, args.type, mullevel, dev)
+            torch.cuda.synchronize()
+            t = time.time() - t0
         elapsed += t
         # the reference needs the record files (their length drives its loop and every window is asserted against them); here
         # they are an optional check

@@ -215,6 +215,43 @@ struct ExpandArgs {
     float *cposn;
 };
 
+// The children of parent i (symbol s, occupancy occ != 0): their state rows c, c + 1, ... of cpos / canc / coct, and for every child the
+// model-input row `row_of(child row)` of cctx / cposn (negative: the child gets none).  One code path for scp_decode_expand (row = child
+// row) and scp_decode_expand_batch (row = the child's place in the next round's window order): the same arithmetic, the same bits.
+template <class RowOf>
+__device__ __forceinline__ void expand_children(int64_t i, int64_t s, unsigned occ, int64_t c, const int32_t *__restrict__ pos,
+                                                const uint8_t *__restrict__ anc, const uint8_t *__restrict__ octant, int L, int shift, int lv_next,
+                                                int lv_clamp, int polar, double mn, double den, int32_t *__restrict__ cpos,
+                                                uint8_t *__restrict__ canc, uint8_t *__restrict__ coct, uint8_t *__restrict__ cctx,
+                                                float *__restrict__ cposn, RowOf row_of) {
+    const int px = pos[3 * i], py = pos[3 * i + 1], pz = pos[3 * i + 2];
+    uint8_t an[9];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) an[j] = anc[9 * i + 3 + j];
+    an[6] = (uint8_t)L; an[7] = octant[i]; an[8] = (uint8_t)s;
+    for (int d = 0; d < 8; ++d) {
+        if (!((occ >> d) & 1)) continue;
+        const int x = px + (((d >> 2) & 1) << shift), y = py + (((d >> 1) & 1) << shift), z = pz + ((d & 1) << shift);
+        cpos[3 * c] = x; cpos[3 * c + 1] = y; cpos[3 * c + 2] = z;
+        coct[c] = (uint8_t)(d + 1);
+#pragma unroll
+        for (int j = 0; j < 9; ++j) canc[9 * c + j] = an[j];
+        const int64_t r = row_of(c);
+        if (r >= 0) {
+#pragma unroll
+            for (int j = 0; j < 9; ++j) cctx[12 * r + j] = (j % 3 == 0 && an[j] > lv_clamp) ? (uint8_t)lv_clamp : an[j];
+            cctx[12 * r + 9] = (uint8_t)lv_next; cctx[12 * r + 10] = (uint8_t)(d + 1); cctx[12 * r + 11] = 255;
+            if (polar) {
+                cposn[3 * r] = (float)(((double)x - mn) / den); cposn[3 * r + 1] = (float)(((double)y - mn) / den);
+                cposn[3 * r + 2] = (float)(((double)z - mn) / den);
+            } else {
+                cposn[3 * r] = (float)((double)x / den); cposn[3 * r + 1] = (float)((double)y / den); cposn[3 * r + 2] = (float)((double)z / den);
+            }
+        }
+        ++c;
+    }
+}
+
 __global__ __launch_bounds__(256) void decode_expand_kernel(const ExpandArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n) return;
@@ -222,31 +259,8 @@ __global__ __launch_bounds__(256) void decode_expand_kernel(const ExpandArgs a) 
     const unsigned occ = (unsigned)((s + 1) & 0xff);
     a.occ8[i] = (uint8_t)occ;
     if (!occ) return;
-    int64_t c = a.cum[i] - __popc(occ);
-    const int px = a.pos[3 * i], py = a.pos[3 * i + 1], pz = a.pos[3 * i + 2];
-    uint8_t an[9];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) an[j] = a.anc[9 * i + 3 + j];
-    an[6] = (uint8_t)a.L; an[7] = a.octant[i]; an[8] = (uint8_t)s;
-    for (int d = 0; d < 8; ++d) {
-        if (!((occ >> d) & 1)) continue;
-        const int x = px + (((d >> 2) & 1) << a.shift), y = py + (((d >> 1) & 1) << a.shift), z = pz + ((d & 1) << a.shift);
-        a.cpos[3 * c] = x; a.cpos[3 * c + 1] = y; a.cpos[3 * c + 2] = z;
-        a.coct[c] = (uint8_t)(d + 1);
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            a.canc[9 * c + j] = an[j];
-            a.cctx[12 * c + j] = (j % 3 == 0 && an[j] > a.lv_clamp) ? (uint8_t)a.lv_clamp : an[j];
-        }
-        a.cctx[12 * c + 9] = (uint8_t)a.lv_next; a.cctx[12 * c + 10] = (uint8_t)(d + 1); a.cctx[12 * c + 11] = 255;
-        if (a.polar) {
-            a.cposn[3 * c] = (float)(((double)x - a.mn) / a.den); a.cposn[3 * c + 1] = (float)(((double)y - a.mn) / a.den);
-            a.cposn[3 * c + 2] = (float)(((double)z - a.mn) / a.den);
-        } else {
-            a.cposn[3 * c] = (float)((double)x / a.den); a.cposn[3 * c + 1] = (float)((double)y / a.den); a.cposn[3 * c + 2] = (float)((double)z / a.den);
-        }
-        ++c;
-    }
+    expand_children(i, s, occ, a.cum[i] - __popc(occ), a.pos, a.anc, a.octant, a.L, a.shift, a.lv_next, a.lv_clamp, a.polar, a.mn, a.den, a.cpos,
+                    a.canc, a.coct, a.cctx, a.cposn, [](int64_t c) { return c; });
 }
 
 extern "C" SCP_API int scp_decode_expand(const int64_t *sym, const int64_t *cum, const int32_t *pos, const uint8_t *anc, const uint8_t *octant, int64_t n,
@@ -259,6 +273,89 @@ extern "C" SCP_API int scp_decode_expand(const int64_t *sym, const int64_t *cum,
     a.sym = sym; a.cum = cum; a.pos = pos; a.anc = anc; a.octant = octant; a.n = n; a.L = L; a.shift = shift; a.lv_next = lv_next;
     a.lv_clamp = lv_clamp; a.polar = polar; a.mn = mn; a.den = den; a.cpos = cpos; a.canc = canc; a.coct = coct; a.cctx = cctx; a.cposn = cposn; a.occ8 = occ8;
     hipLaunchKernelGGL(decode_expand_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, a);
+    LAUNCH_CHECK();
+    return SCP_OK;
+}
+
+// The lockstep decoder's form: the decoded levels of S <= 64 streams ("segments": parents concatenated segment after segment, ONE scan
+// `cum` over all of them) in one launch.  Child c of segment s gets state row cfirst[s] + c (the segments' children back to back, which
+// is where the global scan puts them) and, when c < coded[s], the model-input row wbase[(c / cs) * S + s] + c % cs: the next round's
+// windows are ordered (window index, segment), so the inputs come out in the order the round's packed forward reads them.  One thread
+// per parent; a thread finds its segment among the <= 64 segment starts (LDS); no thread waits for another.
+struct ExpandBatchArgs {
+    const int64_t *sym, *cum;
+    const int32_t *pos;
+    const uint8_t *anc, *octant;
+    const scp_expand_seg *seg;       // device copy of the table
+    const int64_t *wbase;            // device copy, [K][S]
+    int64_t n, M, T;
+    int32_t S, K, cs;
+    int32_t *cpos;
+    uint8_t *canc, *coct, *cctx, *occ8;
+    float *cposn;
+};
+
+__global__ __launch_bounds__(256) void decode_expand_batch_kernel(const ExpandBatchArgs a) {
+    __shared__ int64_t first[64];
+    if ((int)threadIdx.x < a.S) first[threadIdx.x] = a.seg[threadIdx.x].first;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    int sg = 0;
+    for (int s = 1; s < a.S; ++s) sg += (i >= first[s]) ? 1 : 0;     // the starts ascend (checked on the host): the count is the segment
+    const int64_t s = a.sym[i];
+    const unsigned occ = (unsigned)((s + 1) & 0xff);
+    a.occ8[i] = (uint8_t)occ;
+    if (!occ) return;
+    const int64_t c0 = a.cum[i] - __popc(occ);
+    if (c0 < 0 || c0 + __popc(occ) > a.M) return;                     // a scan that is not this array's: nothing is written out of bounds
+    const scp_expand_seg g = a.seg[sg];
+    const int64_t *wbase = a.wbase;
+    const int64_t cfirst = g.cfirst, coded = g.coded, T = a.T;
+    const int S = a.S, K = a.K, cs = a.cs;
+    expand_children(i, s, occ, c0, a.pos, a.anc, a.octant, g.L, g.shift, g.lv_next, g.lv_clamp, g.polar, g.mn, g.den, a.cpos, a.canc, a.coct, a.cctx,
+                    a.cposn, [=](int64_t c) -> int64_t {
+                        const int64_t lc = c - cfirst;
+                        if (lc < 0 || lc >= coded) return -1;
+                        const int64_t k = lc / cs;
+                        if (k >= K) return -1;
+                        const int64_t b = wbase[k * S + sg];
+                        const int64_t r = b + lc % cs;
+                        return (b < 0 || r >= T) ? -1 : r;
+                    });
+}
+
+extern "C" SCP_API int scp_decode_expand_batch(const int64_t *sym, const int64_t *cum, const int32_t *pos, const uint8_t *anc, const uint8_t *octant,
+                                               int64_t n, const scp_expand_seg *seg, int32_t S, int32_t cs, const int64_t *wbase, int32_t K,
+                                               int64_t M, int64_t T, void *table_dev, int32_t *cpos, uint8_t *canc, uint8_t *coct, uint8_t *cctx,
+                                               float *cposn, uint8_t *occ8, void *stream) {
+    // cctx / cposn may be null when no child gets an input row (T == 0: every segment sits on its tree's last level)
+    if (!sym || !cum || !pos || !anc || !octant || !seg || !wbase || !table_dev || !cpos || !canc || !coct || !occ8 || (T > 0 && (!cctx || !cposn)) ||
+        S < 1 || S > 64 || cs < 1 || K < 1 || n <= 0 || M <= 0 || T < 0)
+        return SCP_EINVAL;
+    int64_t row = 0, child = 0;
+    for (int s = 0; s < S; ++s) {
+        const scp_expand_seg &g = seg[s];
+        if (g.first != row || g.count < 1 || g.cfirst != child || g.coded < 0 || g.L < 1 || g.L > 254 || g.shift < 0 || g.shift > 30 || g.lv_next < 0 ||
+            g.lv_next > 255 || g.lv_clamp < 0 || g.lv_clamp > 255 || !(g.den == g.den) || g.den == 0.0)
+            return SCP_EINVAL;
+        const int64_t m = (s + 1 < S ? seg[s + 1].cfirst : M) - g.cfirst;
+        if (m < 0 || g.coded > m || g.coded > (int64_t)K * cs) return SCP_EINVAL;
+        for (int64_t k = 0; k * cs < g.coded; ++k) {                 // every window a coded child lands in lies inside the input arrays
+            const int64_t b = wbase[k * S + s], len = g.coded - k * cs < cs ? g.coded - k * cs : cs;
+            if (b < 0 || b + len > T) return SCP_EINVAL;
+        }
+        row += g.count;
+        child += m;
+    }
+    if (row != n || child != M) return SCP_EINVAL;
+    // table_dev holds the caller's device copy of both tables (uploaded on this stream): nothing is copied or awaited here
+    hipStream_t st = (hipStream_t)stream;
+    ExpandBatchArgs a;
+    a.sym = sym; a.cum = cum; a.pos = pos; a.anc = anc; a.octant = octant; a.seg = (const scp_expand_seg *)table_dev;
+    a.wbase = (const int64_t *)((const char *)table_dev + 64 * sizeof(scp_expand_seg));
+    a.n = n; a.M = M; a.T = T; a.S = S; a.K = K; a.cs = cs; a.cpos = cpos; a.canc = canc; a.coct = coct; a.cctx = cctx; a.cposn = cposn; a.occ8 = occ8;
+    hipLaunchKernelGGL(decode_expand_batch_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, st, a);
     LAUNCH_CHECK();
     return SCP_OK;
 }

@@ -431,11 +431,9 @@ class OctAttnBatchDecoder:
         return results
 
 
-def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False, device=None, profile=None):
-    """A stream file written by the encode CLIs -> dict(codes per shell, leaves per shell, points [U,3] float64 Cartesian).
-    Side information exactly as the reference's decoders take it (`extract_info`); the `.scp.json` written next to the stream
-    supplies what that cannot carry.  Without it the reference's own rules apply: lidar level = the level count (decode_ehem.py:218),
-    integer z offset, and - for the two outer shells - bin numbers extrapolated from the first shell's."""
+def _ehem_job(binfile, lidar_level=None, data_type=None, mullevel=False, profile=None):
+    """Everything decode_file knows about a stream before it decodes it: the side information of `extract_info`, the `.scp.json` (its
+    numeric profile checked against this process's), the reference's rules where it is missing, and the stream's bytes."""
     spher, cylin, pos_mm, n_levels, bin_num, z_offset = extract_info(binfile)
     side = read_sidecar(binfile)
     if side is not None:
@@ -454,10 +452,20 @@ def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False
         bins = side["bin_nums"]
     else:
         bins = [bin_num] + [round((bin_num - 1) * qs[0] / q) + 1 for q in qs[1:]]
-    dec = FrameDecoder(model, lidar_level, mullevel=mullevel, polar=spher or cylin, device=device, profile=profile)
     with open(binfile, "rb") as f:
         stream = f.read()
-    shells = dec.decode(stream, n_levels, pos_mm)
+    return dict(name=binfile, stream=stream, side=side, spher=spher, cylin=cylin, polar=spher or cylin, pos_mm=pos_mm, n_levels=n_levels,
+                bin_num=bin_num, z_offset=z_offset, lidar_level=lidar_level, data_type=data_type, mullevel=mullevel, qs=qs, bins=bins)
+
+
+def _obj_without_quant(binfile):
+    return native.ScpError(f"{binfile}: --type obj streams are quantised with the frame's per-axis minimum as offset "
+                           "(data_preprocess.py:31-37), which only the sidecar's `quant` entry records - it is missing here")
+
+
+def _ehem_result(job, shells):
+    """The decoded shells [(codes per level, leaf integers)] of a job -> the dict decode_file returns."""
+    binfile, side, spher, cylin, data_type = job["name"], job["side"], job["spher"], job["cylin"], job["data_type"]
     # KITTI / Ford: the reference decoder's own rule (steps from the integer bin_num in float64, decode_ehem.py:237-249) - the cloud it
     # would write.  obj: there is no rule (the offset is the frame's per-axis minimum): the sidecar's `quant` entry, or nothing.
     quant = side.get("quant") if side is not None else None
@@ -465,12 +473,49 @@ def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False
         from . import metrics
         pts = [metrics.dequantize(lv, qd["qs"], qd["offset"], spher=spher, cylin=cylin) for (_, lv), qd in zip(shells, quant)]
     elif data_type == "obj":
-        raise native.ScpError(f"{binfile}: --type obj streams are quantised with the frame's per-axis minimum as offset "
-                              "(data_preprocess.py:31-37), which only the sidecar's `quant` entry records - it is missing here")
+        raise _obj_without_quant(binfile)
     else:
-        pts = [dequantise_leaves(lv, q, b, z_offset, spher, cylin, data_type) for (_, lv), q, b in zip(shells, qs, bins)]
+        pts = [dequantise_leaves(lv, q, b, job["z_offset"], spher, cylin, data_type) for (_, lv), q, b in zip(shells, job["qs"], job["bins"])]
     return dict(codes=[torch.cat(c) for c, _ in shells], leaves=[lv for _, lv in shells], points=torch.cat(pts),
-                spher=spher, cylin=cylin, n_levels=n_levels, bin_num=bin_num, z_offset=z_offset, lidar_level=lidar_level)
+                spher=spher, cylin=cylin, n_levels=job["n_levels"], bin_num=job["bin_num"], z_offset=job["z_offset"],
+                lidar_level=job["lidar_level"])
+
+
+def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False, device=None, profile=None):
+    """A stream file written by the encode CLIs -> dict(codes per shell, leaves per shell, points [U,3] float64 Cartesian).
+    Side information exactly as the reference's decoders take it (`extract_info`); the `.scp.json` written next to the stream
+    supplies what that cannot carry.  Without it the reference's own rules apply: lidar level = the level count (decode_ehem.py:218),
+    integer z offset, and - for the two outer shells - bin numbers extrapolated from the first shell's."""
+    job = _ehem_job(binfile, lidar_level, data_type, mullevel, profile)
+    dec = FrameDecoder(model, job["lidar_level"], mullevel=mullevel, polar=job["polar"], device=device, profile=profile)
+    return _ehem_result(job, dec.decode(job["stream"], job["n_levels"], job["pos_mm"]))
+
+
+def shell_depths(n_levels, mullevel):
+    """The octree depths of a stream's shells: one tree, or the three of a multi-level frame (decode_ehem_mullevel.py:199)."""
+    if mullevel:
+        m = n_levels // 3
+        return [m - 1, m, m + 1]
+    return [n_levels]
+
+
+def last_coded_level(depth, pos_mm, mullevel, polar):
+    """The last chunk is the deepest level with coded rows: a one-leaf shell's last level holds the dropped node alone, its (min, max)
+    row still carries the build's initial words (min > max), and the clip and the epsilon-free division move up one level."""
+    if mullevel and polar and depth > 1 and float(pos_mm[depth - 1][0]) > float(pos_mm[depth - 1][1]):
+        return depth - 1
+    return depth
+
+
+def ehem_level_params(L, depth, last_coded, pos_mm, lidar_level, mullevel, polar):
+    """(lv, ancestor level clamp, mn, den) of the model inputs of level L of a tree of `depth` levels."""
+    last = L == last_coded
+    lv = min(L, lidar_level) if last else L                                # encode_dataset_ehem.py:86 clips the last chunk
+    if polar:
+        mn, mx = float(pos_mm[L - 1][0]), float(pos_mm[L - 1][1])
+        eps = 0.0 if (mullevel and last) else 1e-9
+        return lv, (lidar_level if last else 255), mn, mx - mn + eps
+    return lv, (lidar_level if last else 255), 0.0, float(2 ** depth)
 
 
 class FrameDecoder:
@@ -657,21 +702,10 @@ class FrameDecoder:
         octant = torch.ones(1, dtype=torch.uint8, device=dev)
         pos = torch.zeros((1, 3), dtype=torch.int32, device=dev)
 
-        # the last chunk is the deepest level with coded rows: a one-leaf shell's last level holds the dropped node alone, its (min, max)
-        # row still carries the build's initial words (min > max), and the clip and the epsilon-free division move up one level
-        last_coded = depth
-        if self.mullevel and self.polar and depth > 1 and float(pos_mm[depth - 1][0]) > float(pos_mm[depth - 1][1]):
-            last_coded = depth - 1
+        last_coded = last_coded_level(depth, pos_mm, self.mullevel, self.polar)
 
         def level_params(L):
-            """(lv, ancestor level clamp, mn, den) of level L's inputs."""
-            last = L == last_coded
-            lv = min(L, self.lidar_level) if last else L                      # encode_dataset_ehem.py:86 clips the last chunk
-            if self.polar:
-                mn, mx = float(pos_mm[L - 1][0]), float(pos_mm[L - 1][1])
-                eps = 0.0 if (self.mullevel and last) else 1e-9
-                return lv, (self.lidar_level if last else 255), mn, mx - mn + eps
-            return lv, (self.lidar_level if last else 255), 0.0, float(2 ** depth)
+            return ehem_level_params(L, depth, last_coded, pos_mm, self.lidar_level, self.mullevel, self.polar)
 
         # level 1: the root
         lv, clamp, mn, den = level_params(1)
@@ -700,11 +734,7 @@ class FrameDecoder:
         """stream: bytes; n_levels: total level count from the file name; pos_mm: [n_levels,2] array from the .dat file.
         Returns list of (codes_per_level, leaf_points int64 [U,3]) - one entry per shell."""
         dec = native.AcDecoder(stream)
-        if self.mullevel:
-            m = n_levels // 3                                                   # decode_ehem_mullevel.py:199
-            depths = [m - 1, m, m + 1]
-        else:
-            depths = [n_levels]
+        depths = shell_depths(n_levels, self.mullevel)
         out, off = [], 0
         from . import ops
         with native.use_profile(self.profile), ops.frozen_weights():            # (the weights do not change inside a frame: validated once per frame)
@@ -712,3 +742,415 @@ class FrameDecoder:
                 out.append(self._decode_tree(dec, d, pos_mm[off:off + d] if self.polar else None))
                 off += d
         return out
+
+
+# ------------------------------------------------------------------------------------------------ several EHEM streams in lockstep
+def window_lengths(rows, cs):
+    """The windows of a level with `rows` coded nodes (FrameDecoder._decode_level)."""
+    return [min(cs, rows - i) for i in range(0, rows, cs)]
+
+
+def chunk_steps(steps, max_tokens=1_000_000, max_rows=None):
+    """Cut a round (steps[k] = the window lengths of step k) into the runs of WHOLE steps that one phase-1 forward takes:
+    [(first step, one past the last)].  A run holds at most `max_tokens` real tokens and `max_rows` rows of the padded layout
+    (encoder.MAX_PACKED_ROWS: the bounds of the encoder's own packed forwards, encoder.chunk_windows); a step is never split - one step of
+    64 slots x 8192 tokens fits both bounds, and a step that did not would go alone."""
+    if max_rows is None:
+        from .encoder import MAX_PACKED_ROWS as max_rows
+    out, i = [], 0
+    while i < len(steps):
+        j, tok, rows = i, 0, 0
+        while j < len(steps):
+            t = sum(steps[j])
+            r = sum(-(-(c + (c & 1)) // 512) * 512 for c in steps[j])
+            if j > i and (tok + t > max_tokens or rows + r > max_rows):
+                break
+            tok += t
+            rows += r
+            j += 1
+        out.append((i, j))
+        i = j
+    return out
+
+
+class EhemLockstep:
+    """The host bookkeeping of the lockstep EHEM decoder, free of any device state (tests drive it with made-up level sizes).  `slots`
+    slots each hold one file's position: tree (of the file's 1 or 3), level L of the tree's depth, node count n of the level.  A ROUND
+    decodes the current level of every active slot; its coded rows are n, or n - 1 on the last level of a tree whose last node is dropped
+    (multi-level shells), and may be 0.  Within a round, STEP k holds window k of every slot that has more than k windows
+    (`window_lengths`); the round's windows are ordered step-major, then slot, so the windows of a step are adjacent in every stage of
+    the round's packed layout.  After a round every slot is advanced with its child count: the next level, the root of the file's next
+    tree, or - the file done - idle, to be refilled in file order (lowest idle slot first, as OctAttnLockstep does)."""
+
+    def __init__(self, depths, drops, slots, context_size):
+        self.cs = int(context_size)
+        self.depths = [[int(d) for d in ds] for ds in depths]
+        self.drops = [bool(x) for x in drops]
+        assert len(self.drops) == len(self.depths) and slots >= 1 and self.cs >= 1
+        self.pending = list(range(len(self.depths)))[::-1]
+        self.file = [None] * slots
+        self.tree = [0] * slots
+        self.L = [0] * slots
+        self.n = [0] * slots
+
+    def refill(self):
+        """-> [(slot, file)] newly started: tree 0, level 1, the root node alone."""
+        new = []
+        for s in range(len(self.file)):
+            if self.file[s] is None and self.pending:
+                self.file[s] = self.pending.pop()
+                self.tree[s], self.L[s], self.n[s] = 0, 1, 1
+                new.append((s, self.file[s]))
+        return new
+
+    def active(self):
+        return tuple(s for s, f in enumerate(self.file) if f is not None)
+
+    def depth(self, slot):
+        return self.depths[self.file[slot]][self.tree[slot]]
+
+    def round(self):
+        """The current level of every active slot, in slot order -> [(slot, file, tree, L, n, coded rows)] (nothing is advanced)."""
+        out = []
+        for s, f in enumerate(self.file):
+            if f is not None:
+                drop = self.drops[f] and self.L[s] == self.depth(s)
+                out.append((s, f, self.tree[s], self.L[s], self.n[s], self.n[s] - (1 if drop else 0)))
+        return out
+
+    def advance(self, slot, m):
+        """The slot's level is decoded and has m children -> "level" (on to the next level, m nodes), "tree" (the tree is complete: on to the
+        root of the file's next tree) or "file" (the file is complete: the slot is idle)."""
+        f = self.file[slot]
+        if self.L[slot] < self.depth(slot):
+            self.L[slot] += 1
+            self.n[slot] = int(m)
+            return "level"
+        if self.tree[slot] + 1 < len(self.depths[f]):
+            self.tree[slot] += 1
+            self.L[slot], self.n[slot] = 1, 1
+            return "tree"
+        self.file[slot] = None
+        return "file"
+
+    @staticmethod
+    def layout(rows, cs):
+        """The layout of a round from the coded-row counts of its slots (one column each) -> (steps, wbase): steps[k] = [(column, window
+        length)] of the columns with more than k windows, in column order - the round's window list is their concatenation; wbase int64
+        [K, columns] (K >= 1) = the first row of window k of a column in the round's dense input arrays, -1 where there is none."""
+        wins = [window_lengths(int(r), cs) for r in rows]
+        K = max([len(w) for w in wins] + [1])
+        wbase = np.full((K, len(wins)), -1, np.int64)
+        steps, row = [], 0
+        for k in range(max(len(w) for w in wins) if wins else 0):
+            step = []
+            for col, w in enumerate(wins):
+                if len(w) > k:
+                    step.append((col, w[k]))
+                    wbase[k, col] = row
+                    row += w[k]
+            steps.append(step)
+        return steps, wbase
+
+
+# range-decoder threads of the lockstep decoder (1 = the calls of a step one after the other on the decoding thread)
+CODER_THREADS = int(os.environ.get("SCP_DEC_CODER_THREADS", "1"))
+
+
+def _stage_rows(c, nst):
+    """Rows of a window of c nodes in every cross stage (models/packed.py: StageLayout - every stage pads a window to x512 rows)."""
+    rows, L = [], (c + (c & 1)) // 2
+    for _ in range(nst):
+        rows.append(-(-L // 512) * 512)
+        L = (L + 1) // 2
+    return rows
+
+
+class EhemBatchDecoder:
+    """FrameDecoder for several streams at once (scheduling: EhemLockstep).  A round = the current level of every stream in flight: ONE
+    packed phase-1 forward over all their windows (in runs of whole steps under the encoder's bounds, `chunk_steps`), one CDF launch,
+    one pinned copy, ehem_phase2_prepare for the round on the side stream; then per step every stream's own range decoder takes its
+    window's even symbols, the even symbols of the step go up in one copy, ONE phase 2 runs on the step's slice of the round's phase-1
+    state with the plan of the step's lengths (the slice IS that plan's layout: the step's windows are adjacent in every stage), one CDF
+    launch and copy, and every stream decodes its odd symbols.  The decoded levels of all streams are expanded by one launch
+    (native.decode_expand_batch) that writes the next round's model inputs in round order.  The packed forward is batch-invariant bit
+    for bit, so every stream's CDF rows, symbols, codes and leaves are FrameDecoder's; per stream the bitstream order (window: evens,
+    odds) is untouched.  max_tokens / max_rows: the bounds of one phase-1 forward (the encoder's; tests lower them).  coder_threads > 1:
+    the range-decoder calls of a step (independent streams; ctypes releases the GIL) run on a pool of that many threads, 16 at most."""
+
+    def __init__(self, model, streams, device=None, profile=None, max_tokens=1_000_000, max_rows=None, coder_threads=CODER_THREADS):
+        self.model = model
+        self.profile = profile
+        self.slots = int(streams)
+        if not 1 <= self.slots <= 64:
+            raise native.ScpError("EhemBatchDecoder: 1 .. 64 streams expected")
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.context_size = model.cfg.model.context_size
+        self.max_tokens, self.max_rows = max_tokens, max_rows
+        self.stats = None             # set to {} to collect wall seconds per stage (a device synchronisation per stamp) + the two counters
+        self.rounds = self.steps = 0
+        self._plans = {}
+        self._pin = [None, None]
+        self._pin_po = None
+        self._pin_sym = None
+        self._side = None
+        self._pool = None
+        if min(int(coder_threads), self.slots) > 1:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(max_workers=min(int(coder_threads), self.slots, 16))
+        self.prepare_ahead = os.environ.get("SCP_DEC_PREP", "1") != "0"
+
+    _stamp = FrameDecoder._stamp
+    _t0 = FrameDecoder._t0
+    _cdf_to_host = FrameDecoder._cdf_to_host
+    _prepare = FrameDecoder._prepare
+
+    def _plan(self, lengths):
+        """The packed plan of a list of window lengths.  Kept are the lists that repeat: those of small windows only (the one-node and
+        few-node levels every tree starts with) and those of full windows only (the inner steps of the large levels)."""
+        from .models.packed import PackedPlan
+        key = tuple(lengths)
+        p = self._plans.get(key)
+        if p is None:
+            p = PackedPlan(list(key), device=self.device)
+            if max(key) <= 64 or min(key) == self.context_size:
+                if len(self._plans) >= 256:
+                    self._plans.clear()
+                self._plans[key] = p
+        return p
+
+    def _run_coders(self, decs, grp, rows):
+        """One range-decoder call per window of a step: decs[col].run(rows_of_that_window) for (col, rows) in order -> the symbols."""
+        if self._pool is None or len(grp) < 2:
+            return [decs[col].run(r) for (col, _), r in zip(grp, rows)]
+        return list(self._pool.map(lambda a: decs[a[0][0]].run(a[1]), zip(grp, rows)))
+
+    def _evens_to_device(self, evens, qps):
+        """The even symbols of a step's windows -> int64 device tensor [sum qps] in the cross layout (each window's rows padded to its x512
+        rows with zeros behind the real ones): one asynchronous copy out of a pinned buffer, whose previous contents were consumed - a
+        step's phase-2 rows are read back, with a synchronisation, before the next step gets here."""
+        Q = sum(qps)
+        if self._pin_po is None or self._pin_po.numel() < Q:
+            self._pin_po = torch.empty(max(Q, 8192), dtype=torch.int64, pin_memory=True)
+        h = self._pin_po[:Q].numpy()
+        q0 = 0
+        for even, qp in zip(evens, qps):
+            h[q0:q0 + even.shape[0]] = even
+            h[q0 + even.shape[0]:q0 + qp] = 0
+            q0 += qp
+        po = torch.empty(Q, dtype=torch.int64, device=self.device)
+        po.copy_(self._pin_po[:Q], non_blocking=True)
+        return po
+
+    def _decode_round(self, decs, steps, ctx, posn, sym, first):
+        """The windows of a round.  decs[col]: the column's range decoder; steps: EhemLockstep.layout's; ctx / posn: the round's inputs in
+        window order; the symbols of column col go to sym[first[col]:] (host int64)."""
+        from .models.packed import ehem_phase1_packed, ehem_phase2_packed, phase2_prep_window
+        cs, model = self.context_size, self.model
+        nst = len(model.swin_cross_transformer.layers)
+        t_row = 0
+        t = self._t0()
+        for k0, k1 in chunk_steps([[c for _, c in st] for st in steps], self.max_tokens, self.max_rows):
+            lengths = [c for st in steps[k0:k1] for _, c in st]
+            ntok = sum(lengths)
+            plan = self._plan(lengths)
+            prob1, st = ehem_phase1_packed(model, ctx[t_row:t_row + ntok], posn[t_row:t_row + ntok], plan)
+            t = self._stamp("phase1_model", t)
+            cdf1_dev = native.softmax_cdf(prob1.contiguous(), want_lohi=False, want_cdf=True)["cdf"]
+            ahead = self.prepare_ahead and max(lengths) > 1
+            cdf1, prep = self._cdf_to_host(cdf1_dev, (lambda: self._prepare(st, plan)) if ahead else None)
+            t = self._stamp("cdf_d2h", t)
+            e0 = q0 = 0
+            bases = [0] * nst
+            for k in range(k0, k1):
+                grp = steps[k]
+                nes = [(c + 1) // 2 for _, c in grp]
+                offs = np.cumsum([e0] + nes)
+                evens = self._run_coders(decs, grp, [cdf1[offs[i]:offs[i + 1]] for i in range(len(grp))])
+                e0 = int(offs[-1])
+                for (col, c), even in zip(grp, evens):
+                    r0 = first[col] + k * cs
+                    sym[r0:r0 + c:2] = even
+                t = self._stamp("range_decoder", t)
+                per = [_stage_rows(c, nst) for _, c in grp]
+                rows = [sum(p[s] for p in per) for s in range(nst)]
+                if max(c for _, c in grp) > 1:
+                    po = self._evens_to_device(evens, [p[0] for p in per])
+                    t = self._stamp("index_ops", t)
+                    pw = plan if k1 - k0 == 1 else self._plan([c for _, c in grp])       # a one-step run: the step's plan is the run's
+                    Q = rows[0]
+                    stw = dict(a1=st["a1"][q0:q0 + Q], a2=st["a2"][q0:q0 + Q], pre_occ=st["pre_occ"][q0:q0 + Q])
+                    pwin = None
+                    if prep is not None:
+                        if prep[1] is not None:
+                            torch.cuda.current_stream(self.device).wait_event(prep[1])
+                            prep = (prep[0], None)
+                        pwin = phase2_prep_window(prep[0], bases, rows)
+                    prob2 = ehem_phase2_packed(model, stw, pw, po, prep=pwin)
+                    t = self._stamp("phase2_model", t)
+                    cdf2, _ = self._cdf_to_host(native.softmax_cdf(prob2.contiguous(), want_lohi=False, want_cdf=True)["cdf"], slot=1)
+                    t = self._stamp("cdf_d2h", t)
+                    odd = [(col, c) for col, c in grp if c > 1]
+                    offs = np.cumsum([0] + [c // 2 for _, c in odd])
+                    for (col, c), o in zip(odd, self._run_coders(decs, odd, [cdf2[offs[i]:offs[i + 1]] for i in range(len(odd))])):
+                        r0 = first[col] + k * cs
+                        sym[r0 + 1:r0 + c:2] = o
+                    t = self._stamp("range_decoder", t)
+                q0 += rows[0]
+                bases = [b + r for b, r in zip(bases, rows)]
+                self.steps += 1
+            t_row += ntok
+
+    # ---- per-file facts
+    def _params(self, f, tree, L):
+        """(lv, clamp, mn, den) of the model inputs of level L of tree `tree` of job f (FrameDecoder._decode_tree's level_params)."""
+        j, d = self._jobs[f], self._depths[f][tree]
+        off = sum(self._depths[f][:tree])
+        mm = j["pos_mm"][off:off + d] if j["polar"] else None
+        return ehem_level_params(L, d, last_coded_level(d, mm, j["mullevel"], j["polar"]), mm, j["lidar_level"], j["mullevel"], j["polar"])
+
+    def _put_roots(self, ctx, posn, roots):
+        """roots: [(input row, file, tree)] - the root's context row and normalised origin, as FrameDecoder._decode_tree makes them."""
+        if not roots:
+            return
+        c = np.zeros((len(roots), 12), np.uint8)
+        p = np.zeros((len(roots), 3), np.float32)
+        for i, (_, f, tree) in enumerate(roots):
+            lv, _, mn, den = self._params(f, tree, 1)
+            c[i] = [0, 0, 255] * 3 + [lv, 1, 255]
+            p[i] = np.float32((0.0 - mn) / den) if self._jobs[f]["polar"] else np.float32(0.0 / den)
+        idx = torch.tensor([r for r, _, _ in roots], dtype=torch.int64, device=self.device)
+        ctx.index_copy_(0, idx, torch.from_numpy(c).to(self.device))
+        posn.index_copy_(0, idx, torch.from_numpy(p).to(self.device))
+
+    def _refill(self, sched, decs, codes):
+        for _, f in sched.refill():
+            decs[f], codes[f] = native.AcDecoder(self._jobs[f]["stream"]), []
+
+    def _upload_symbols(self, N, ends):
+        """The round's symbols (the first N words of the pinned buffer; behind them the last parent row of every segment) in one copy, one
+        scan of their child counts, the segment totals back -> (sym, cum, children per segment)."""
+        C = len(ends)
+        self._pin_sym[N:N + C] = torch.from_numpy(ends)
+        up = torch.empty(N + C, dtype=torch.int64, device=self.device)
+        up.copy_(self._pin_sym[:N + C], non_blocking=True)
+        sym = up[:N]
+        cum = torch.cumsum(native.popcount_table(self.device)[sym + 1], 0)
+        tot = cum[up[N:]].cpu().numpy()
+        return sym, cum, np.diff(tot, prepend=0)
+
+    def _segment_table(self, info, state, ninfo, nwb, first, cfirst):
+        """The table of native.decode_expand_batch for the decoded round `info` (state[col]: what EhemLockstep.advance said), given the next
+        round `ninfo` and its layout: a segment whose slot goes on with its tree gets its next level's scalars, coded rows and window
+        starts; one whose tree is complete only yields child state (the leaves)."""
+        ncol_of = {r[0]: i for i, r in enumerate(ninfo)}
+        seg = np.zeros(len(info), native.EXPAND_SEG)
+        wbk = np.full((nwb.shape[0], len(info)), -1, np.int64)
+        for col, (s, f, tree, L, n, _) in enumerate(info):
+            if state[col] == "level":
+                lvn, clamp, mn, den = self._params(f, tree, L + 1)
+                coded, polar = ninfo[ncol_of[s]][5], self._jobs[f]["polar"]
+                wbk[:, col] = nwb[:, ncol_of[s]]
+            else:
+                lvn, clamp, mn, den, coded, polar = 0, 255, 0.0, 1.0, 0, False
+            seg[col] = (first[col], n, cfirst[col], coded, L, self._depths[f][tree] - L, lvn, clamp, 1 if polar else 0, 0, mn, den)
+        return seg, wbk
+
+    def _next_parents(self, info, ninfo, nwb, cfirst, m, state_dev, roots_dev):
+        """The parents of the next round, slot-major: a slot that goes on takes its children where the launch put them, a slot at a root (a
+        new tree or file) the root row -> (pos, anc, octant), [(input row, file, tree)] of the roots with a coded row."""
+        col_of = {r[0]: i for i, r in enumerate(info)}
+        pieces, roots = [], []
+        for nc, (s, f, tree, L, n, rows) in enumerate(ninfo):
+            if L > 1:
+                pieces.append((int(cfirst[col_of[s]]), int(m[col_of[s]])))
+            else:
+                pieces.append(None)
+                if rows > 0:
+                    roots.append((int(nwb[0, nc]), f, tree))
+        if pieces and all(p is not None for p in pieces) and sum(p[1] for p in pieces) == state_dev[0].shape[0]:
+            return state_dev, roots                                  # every segment goes on: its children are the next parents as they lie
+        if not pieces:
+            return state_dev, roots
+        return tuple(torch.cat([a[p[0]:p[0] + p[1]] if p is not None else r for p in pieces]) for a, r in zip(state_dev, roots_dev)), roots
+
+    def decode(self, jobs):
+        """jobs: dicts(name, stream bytes, n_levels, pos_mm, polar, mullevel, lidar_level) -> per job the list FrameDecoder.decode returns:
+        (codes per level, leaf integers int64 [U, 3]) of every shell."""
+        from . import ops
+        dev, cs = self.device, self.context_size
+        self._jobs = jobs
+        self._depths = depths = [shell_depths(j["n_levels"], j["mullevel"]) for j in jobs]
+        sched = EhemLockstep(depths, [j["mullevel"] for j in jobs], self.slots, cs)
+        decs, codes, shells = [None] * len(jobs), [None] * len(jobs), [[] for _ in jobs]
+        results = [None] * len(jobs)
+        roots_dev = (torch.zeros((1, 3), dtype=torch.int32, device=dev), torch.tensor([[0, 0, 255] * 3], dtype=torch.uint8, device=dev),
+                     torch.ones(1, dtype=torch.uint8, device=dev))
+        with native.use_profile(self.profile), ops.frozen_weights():
+            t = self._t0()
+            self._refill(sched, decs, codes)
+            info = sched.round()
+            steps, wb = EhemLockstep.layout([r[5] for r in info], cs)
+            pos, anc, octant = (r.repeat(len(info), *([1] * (r.dim() - 1))) for r in roots_dev)
+            T = sum(r[5] for r in info)
+            ctx = torch.empty((T, 12), dtype=torch.uint8, device=dev)
+            posn = torch.empty((T, 3), dtype=torch.float32, device=dev)
+            self._put_roots(ctx, posn, [(int(wb[0, col]), r[1], r[2]) for col, r in enumerate(info) if r[5] > 0])
+            while info:
+                self.rounds += 1
+                ns = np.array([r[4] for r in info], np.int64)
+                first = np.cumsum(ns) - ns
+                N = int(ns.sum())
+                if self._pin_sym is None or self._pin_sym.numel() < N + len(info):
+                    self._pin_sym = torch.empty(max(N + len(info), 1 << 16), dtype=torch.int64, pin_memory=True)
+                buf = self._pin_sym[:N].numpy()
+                buf[:] = -1
+                t = self._stamp("tree_expansion", t)
+                if steps:
+                    self._decode_round([decs[r[1]] for r in info], steps, ctx, posn, buf, [int(x) for x in first])
+                t = self._t0()
+                sym, cum, m = self._upload_symbols(N, first + ns - 1)
+                cfirst = np.cumsum(m) - m
+                state = []
+                for col, (s, f, tree, L, n, _) in enumerate(info):
+                    if L < depths[f][tree] and m[col] == 0:
+                        raise native.ScpError(f"{jobs[f]['name']}: level {L} of a tree of {depths[f][tree]} levels decodes to no children: stream and "
+                                              "side information disagree")
+                    state.append(sched.advance(s, m[col]))
+                self._refill(sched, decs, codes)
+                ninfo = sched.round()
+                nsteps, nwb = EhemLockstep.layout([r[5] for r in ninfo], cs)
+                seg, wbk = self._segment_table(info, state, ninfo, nwb, first, cfirst)
+                occ8, cpos, canc, coct, ctx, posn = native.decode_expand_batch(sym, pos, anc, octant, cum, seg, cs, wbk, int(m.sum()),
+                                                                               sum(r[5] for r in ninfo))
+                for col, (s, f, tree, L, n, _) in enumerate(info):
+                    codes[f].append(occ8[first[col]:first[col] + n].clone())          # (a copy: the round's arrays are not kept alive)
+                    if state[col] != "level":
+                        shells[f].append((codes[f], cpos[cfirst[col]:cfirst[col] + m[col]].long()))
+                        codes[f] = []
+                    if state[col] == "file":
+                        results[f], decs[f], codes[f] = shells[f], None, None
+                (pos, anc, octant), roots = self._next_parents(info, ninfo, nwb, cfirst, m, (cpos, canc, coct), roots_dev)
+                self._put_roots(ctx, posn, roots)
+                info, steps = ninfo, nsteps
+            self._stamp("tree_expansion", t)
+        if self.stats is not None:
+            self.stats["rounds"], self.stats["steps"] = self.rounds, self.steps
+        return results
+
+
+def decode_files(binfiles, model, streams=1, lidar_level=None, data_type=None, mullevel=False, device=None, profile=None):
+    """Several EHEM stream files decoded `streams` at a time in lockstep (EhemBatchDecoder) -> the dicts decode_file returns, in the order
+    of `binfiles`, each with the bits the one-stream decoder gives (codes, leaves, points).  The streams share the model and `mullevel`;
+    they may differ in depth, coordinate system, data type and lidar level.  Every file's name side info and `.scp.json` is read and
+    checked, the numeric profile included, before anything is decoded."""
+    if not 1 <= int(streams) <= 64:
+        raise native.ScpError("decode_files: 1 .. 64 streams expected")
+    jobs = [_ehem_job(str(b), lidar_level, data_type, mullevel, profile) for b in binfiles]
+    for j in jobs:
+        if j["data_type"] == "obj" and not (j["side"] or {}).get("quant"):
+            raise _obj_without_quant(j["name"])                               # decode_file's refusal, before anything is decoded
+    if not jobs:
+        return []
+    dec = EhemBatchDecoder(model, min(int(streams), len(jobs)), device=device, profile=profile)
+    return [_ehem_result(j, shells) for j, shells in zip(jobs, dec.decode(jobs))]

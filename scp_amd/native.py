@@ -127,6 +127,7 @@ def lib():
         "scp_octattn_attention_rowinv_step": (C.c_int, [_vp, i64, _vp, _vp, i64, i64, i32, i32, _vp, _vp, i64, _vp, _vp, i64, _vp, _vp, i32, i32, i32,
                                                         _vp]),
         "scp_decode_expand_octattn": (C.c_int, [_vp, _vp, _vp, _vp, i64, i32, i32, i32, _vp, _vp, _vp, _vp, _vp]),
+        "scp_decode_expand_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, i64, _vp, i32, i32, _vp, i32, i64, i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "scp_split_weight_bf16": (C.c_int, [_vp, i32, i32, i32, i32, _vp, _vp, _vp]),
         "scp_linear_bf16x3": (C.c_int, [_vp, i64, _vp, _vp, i32, _vp, _vp, i64, _vp, i64, i32, i32, i32, i32, _vp]),
         "scp_split_weight_f16": (C.c_int, [_vp, i32, i32, i32, i32, _vp, _vp, _vp, _vp]),
@@ -518,9 +519,7 @@ def decode_expand(sym, pos, anc, octant, L, shift, lv_next, lv_clamp, polar, mn,
     sym int64 [n] (-1 = unknown), pos int32 [n,3], anc uint8 [n,9], octant uint8 [n] ->
     (occ8 uint8 [n], cpos int32 [m,3], canc uint8 [m,9], coct uint8 [m], cctx uint8 [m,12], cposn float32 [m,3]); one host sync (m)."""
     dev, n = sym.device, sym.shape[0]
-    tab = _POPC.get(dev)
-    if tab is None:
-        tab = _POPC[dev] = torch.tensor([bin(v).count("1") for v in range(256)], dtype=torch.int64, device=dev)
+    tab = popcount_table(dev)
     cum = torch.cumsum(tab[sym + 1], 0)
     m = int(cum[-1])
     occ8 = torch.empty(n, dtype=torch.uint8, device=dev)
@@ -536,6 +535,56 @@ def decode_expand(sym, pos, anc, octant, L, shift, lv_next, lv_clamp, polar, mn,
     _check(lib().scp_decode_expand(_dev(sym, torch.int64), cum.data_ptr(), _dev(pos, torch.int32), _dev(anc, torch.uint8), _dev(octant, torch.uint8), n,
                                    int(L), int(shift), int(lv_next), int(lv_clamp), 1 if polar else 0, float(mn), float(den), cpos.data_ptr(), canc.data_ptr(),
                                    coct.data_ptr(), cctx.data_ptr(), cposn.data_ptr(), occ8.data_ptr(), _stream()), "scp_decode_expand")
+    return occ8, cpos, canc, coct, cctx, cposn
+
+
+# include/scp.h: scp_expand_seg, as a numpy record (one row per segment of scp_decode_expand_batch)
+EXPAND_SEG = np.dtype([("first", np.int64), ("count", np.int64), ("cfirst", np.int64), ("coded", np.int64), ("L", np.int32), ("shift", np.int32),
+                       ("lv_next", np.int32), ("lv_clamp", np.int32), ("polar", np.int32), ("reserved", np.int32), ("mn", np.float64),
+                       ("den", np.float64)])
+
+
+def popcount_table(dev):
+    """int64 [256] on `dev`: the set bits of every occupancy code (cached)."""
+    tab = _POPC.get(dev)
+    if tab is None:
+        tab = _POPC[dev] = torch.tensor([bin(v).count("1") for v in range(256)], dtype=torch.int64, device=dev)
+    return tab
+
+
+def decode_expand_batch(sym, pos, anc, octant, cum, seg, cs, wbase, M, T):
+    """Lockstep decoder: the decoded levels of S <= 64 streams expanded in ONE launch (csrc/plan.hip: scp_decode_expand_batch).  The
+    parents of the streams lie segment after segment in sym int64 [n] (-1 = unknown), pos int32 [n,3], anc uint8 [n,9], octant uint8 [n];
+    cum int64 [n] = the inclusive scan of popcount(sym + 1) over the whole array; seg: EXPAND_SEG records [S] (host); wbase int64 [K,S]
+    (host): first input row of window k of segment s, -1 = none; M = children in all, T = input rows in all.  ->
+    (occ8 uint8 [n], cpos int32 [M,3], canc uint8 [M,9], coct uint8 [M] with segment s at rows cfirst[s].., cctx uint8 [T,12],
+    cposn float32 [T,3] with child c < coded[s] of segment s at row wbase[c // cs, s] + c % cs).  Asynchronous: the tables go up in one
+    copy out of pinned memory on the current stream, nothing is awaited."""
+    dev, n = sym.device, sym.shape[0]
+    seg = np.ascontiguousarray(seg, EXPAND_SEG)
+    wbase = np.ascontiguousarray(wbase, np.int64)
+    if wbase.ndim != 2 or wbase.shape[1] != seg.shape[0]:
+        raise ScpError("decode_expand_batch: wbase must be [K, S]")
+    S, K, M, T = int(seg.shape[0]), int(wbase.shape[0]), int(M), int(T)
+    if cum.shape[0] != n or cum.dtype != torch.int64:
+        raise ScpError("decode_expand_batch: cum must be the int64 scan of the parents")
+    cpos = torch.empty((M, 3), dtype=torch.int32, device=dev)
+    canc = torch.empty((M, 9), dtype=torch.uint8, device=dev)
+    coct = torch.empty(M, dtype=torch.uint8, device=dev)
+    cctx = torch.empty((T, 12), dtype=torch.uint8, device=dev)
+    cposn = torch.empty((T, 3), dtype=torch.float32, device=dev)
+    if M == 0 and n > 0:
+        # no parent has a child (every stream sits on a last level that holds only the dropped node): nothing to launch, as in decode_expand
+        return (sym + 1).clamp_(min=0).to(torch.uint8), cpos, canc, coct, cctx, cposn
+    occ8 = torch.empty(n, dtype=torch.uint8, device=dev)
+    host = torch.zeros((64 * EXPAND_SEG.itemsize + 8 * max(K * S, 1),), dtype=torch.uint8, pin_memory=True)
+    host[:seg.nbytes] = torch.from_numpy(seg.view(np.uint8))
+    host[64 * EXPAND_SEG.itemsize:64 * EXPAND_SEG.itemsize + wbase.nbytes] = torch.from_numpy(wbase.reshape(-1).view(np.uint8))
+    scratch = host.to(dev, non_blocking=True)           # (torch keeps the pinned block until the copy has run)
+    _check(lib().scp_decode_expand_batch(_dev(sym, torch.int64), cum.data_ptr(), _dev(pos, torch.int32), _dev(anc, torch.uint8), _dev(octant, torch.uint8),
+                                         n, seg.ctypes.data, S, int(cs), wbase.ctypes.data, K, M, T, scratch.data_ptr(), cpos.data_ptr(),
+                                         canc.data_ptr(), coct.data_ptr(), cctx.data_ptr(), cposn.data_ptr(), occ8.data_ptr(), _stream()),
+           "scp_decode_expand_batch")
     return occ8, cpos, canc, coct, cctx, cposn
 
 
@@ -1522,9 +1571,7 @@ def decode_expand_octattn(sym, ctx, apos, L, depth):
     scp_decode_expand_octattn).  sym int64 [n] (-1 = no children), ctx uint8 [n,12], apos int32 [n,4,3] (the parents' context rows and
     their four integer origins) -> (occ8 uint8 [n], cctx uint8 [m,12], capos int32 [m,4,3], cpos float32 [m,4,3]); one host sync (m)."""
     dev, n = sym.device, sym.shape[0]
-    tab = _POPC.get(dev)
-    if tab is None:
-        tab = _POPC[dev] = torch.tensor([bin(v).count("1") for v in range(256)], dtype=torch.int64, device=dev)
+    tab = popcount_table(dev)
     cum = torch.cumsum(tab[sym + 1], 0)
     m = int(cum[-1])
     occ8 = torch.empty(n, dtype=torch.uint8, device=dev)
