@@ -407,6 +407,32 @@ SCP_API int scp_softmax_cdf(const float *logits, int64_t ld, int64_t n, int32_t 
 SCP_API int scp_pmf_cdf(const float *pmf, int64_t n, int32_t nsym, const uint8_t *sym, uint32_t *lohi,
                 uint16_t *cdf_full, void *stream);
 
+/* Rate report (csrc/rate.hip; additive, no new ABI version): where a stream's bits go.  For every row of the coding-order logits table
+ *   ideal_bits = (m - x[sym] + log(sum_j exp(x[j] - m))) / ln 2   the model's cross-entropy in bits (models/ehem.py:198-210: `train_loss` is its
+ *                                                                 mean per node); m = the row maximum, every term float64 from the float32 logits
+ *   table_bits = 16 - log2(w), w = (hi ? hi : 65536) - lo          what the 16-bit table of scp_softmax_cdf charges for the symbol
+ *   top1       = (x[sym] == m)                                     a tie with the maximum is a hit
+ * summed over nseg segments of consecutive rows: seg_off int64 [nseg + 1] (DEVICE), non-decreasing, seg_off[0] = 0, seg_off[nseg] = n
+ * (offsets are clamped to [0, n]; a segment may be empty).  A row with w < 1 (no table of this library has one), with sym >= nsym or with
+ * a non-finite cross-entropy is counted in bad_rows, contributes 0 to both sums and is written as 0 to row_ideal / row_table; it still
+ * counts in rows, and in top1 when its symbol holds the maximum.  No inf / NaN is ever written.
+ * logits [n][nsym] with row stride ld >= nsym floats, 2 <= nsym <= 256.  With ld == 256 and a 16-byte aligned base the rows are read with
+ * 16-byte loads, ALL 256 floats of every row: the last row's columns nsym .. 255 must then be readable memory too (as for scp_softmax_cdf;
+ * the encoders' tables are [n][256]).  sym uint8 [n];
+ * lohi uint32 [n] as scp_softmax_cdf writes it; out [nseg]; row_ideal / row_table float64 [n], optional (NULL).  workspace: device memory,
+ * 8-byte aligned, scp_rate_workspace_bytes(n, nseg) bytes.  n == 0: SCP_OK, every segment zero (the row pointers may then be NULL).
+ * Summation order is fixed - a row's sum depends on nsym alone, a segment's on its length alone - and there are no floating-point atomics:
+ * a segment's sums are bit-identical from run to run, wherever the segment lies in the table, and for any ld. */
+typedef struct scp_rate_seg {
+    int64_t rows;
+    double ideal_bits, table_bits;
+    int64_t top1, bad_rows;
+} scp_rate_seg;
+SCP_API int64_t scp_rate_workspace_bytes(int64_t n, int32_t nseg);   /* bytes, or SCP_EINVAL for a negative argument */
+SCP_API int scp_rate_segments(const float *logits, int64_t ld, int64_t n, int32_t nsym, const uint8_t *sym, const uint32_t *lohi,
+                              const int64_t *seg_off, int32_t nseg, scp_rate_seg *out, double *row_ideal, double *row_table,
+                              void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Range coder (host, serial) - replaces numpyAc/backend/numpyAc_backend.cpp
  *   encode_cdf :327-334 / encode :245-323  ->  scp_ac_encode_cdf, scp_ac_encode_lohi

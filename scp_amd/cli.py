@@ -9,11 +9,15 @@ same stdout block per frame, same summary file.  Differences, all additive:
   * `--test_files` accepts a glob, a directory or a list (the reference's `glob.glob(list)` cannot work, SURVEY B-3).
   * `--metrics`: chamfer distance and D1 PSNR of every frame, computed on the device (scp_amd/metrics.py; the reference
     shells out to pc_error and a CPU KD-tree for these) - they enter the per-frame block and the all-reduced summary.
+  * `--rate_report`: where every frame's bits go - the model's cross-entropy (ideal bits), the cost of the coder's 16-bit tables and the
+    coded size, per octree level (EHEM: per phase), computed on the device (csrc/rate.hip): one more line per frame and a
+    `<stream>.rate.json` next to every stream.  The streams themselves do not change.
   * `--normals estimate|DIR` (with `--metrics`, EHEM): the D2 (point-to-plane) PSNR as well, on normals estimated on the device or
     read from the `<DIR>/<sequence>/<frame>.ply` files `gene_normals.py` writes; one more line per frame, `PSNR_D2:` in the summary.
 """
 import argparse
 import glob
+import json
 import os
 import time
 from pathlib import Path
@@ -80,6 +84,10 @@ def get_args(argv=None, mullevel=False):
     p.add_argument("--decodable", action="store_true",
                    help="OctAttention only: code under the decodable numeric profile (octattn/1d) so that decode.py can rebuild the stream; "
                         "EHEM streams are decodable already")
+    # (absent from the namespace unless given, like the fields hand-made namespaces leave out: read it with getattr(args, "rate_report", False))
+    p.add_argument("--rate_report", action="store_true", default=argparse.SUPPRESS,
+                   help="per frame: ideal (cross-entropy), coded-table and coded bits per point on one more line, and <stream>.rate.json next to "
+                        "the stream with the same figures per octree level (EHEM: per phase); the streams do not change")
     p.add_argument("--host_transform", action="store_true",
                    help="strict identity with the reference from the frame on: the coordinate transform + quantiser run in numpy float32 on the "
                         "host exactly as data_preprocess.py:42-70 does (the device transform is more accurate, hence not bit-identical); "
@@ -250,6 +258,7 @@ def main(argv=None, mullevel=False):
     cfg = load_cfg(args.ckpt_path, args.model)
     name = cfg.model.class_name
     refuse_unsupported(args, name, mullevel)
+    rate_report = getattr(args, "rate_report", False)
     cls = OctAttention if name == "OctAttention" else EHEM
     if args.random_weights is not None or not args.ckpt_path:
         from .weights import fill_weights
@@ -272,10 +281,10 @@ def main(argv=None, mullevel=False):
         mul = mullevel and args.spher and not obj       # encode_dataset_mullevel.py:76: the three-shell form exists for --spher
         enc = OctAttnFrameEncoder(model, args.type, args.lidar_level, spher=args.spher and not obj, cylin=args.cylin and not obj, device=dev,
                                   mullevel=mul, level_wise=args.level_wise and mullevel, named=mullevel,
-                                  host_transform=True if args.host_transform else None, decodable=args.decodable)
+                                  host_transform=True if args.host_transform else None, decodable=args.decodable, rate=rate_report)
     else:
         enc = FrameEncoder(model, args.type, args.lidar_level, spher=args.spher, cylin=args.cylin, mullevel=mullevel, device=dev,
-                           host_transform=True if args.host_transform else None)
+                           host_transform=True if args.host_transform else None, rate=rate_report)
 
     mine = D.shard(files, rank, world)
     # fast path: frames are enqueued with encode_async (stage G on a side stream, two model lanes, range coder on a worker thread)
@@ -287,6 +296,7 @@ def main(argv=None, mullevel=False):
     reader = Prefetch(mine, post=host_ints)
     pending = []
     sums = [0.0, 0.0, 0.0, 0.0, 0.0] + ([0.0] if args.normals else [])      # --normals: one more number in the reduced summary
+    rate_sums = [0.0, 0.0, 0.0, 0]            # --rate_report: this rank's own frames (the reduced summary stays as it is)
     last_done = [time.time()]
 
     def stem_of(cur):
@@ -318,6 +328,13 @@ def main(argv=None, mullevel=False):
             if "psnr_d2" in dist:
                 print("PSNR (D2)                   :", dist["psnr_d2"])
                 sums[5] += dist["psnr_d2"]
+        if rate_report:
+            rate = res["rate"]
+            print("bpp ideal / table / coded   :", rate["bpp_ideal"], rate["bpp_table"], res["bpp"])
+            with open(outfile[:-len(".bin")] + ".rate.json", "w") as f:
+                json.dump(dict(rate, model=name, profile=enc.profile_string(), lidar_level=args.lidar_level, bits=res["bits"],
+                               n_points=res["n_points"], n_nodes=res["n_nodes"]), f, indent=1)
+            rate_sums[0] += rate["bpp_ideal"]; rate_sums[1] += rate["bpp_table"]; rate_sums[2] += res["bpp"]; rate_sums[3] += 1
         sums[0] += res["bpp"]; sums[1] += dist["psnr"] if dist else 0.0; sums[2] += dist["chamfer"] if dist else 0.0
         sums[3] += elapsed; sums[4] += 1
 
@@ -379,6 +396,8 @@ def main(argv=None, mullevel=False):
         print("bpp:", m["bpp"])
         if args.normals:
             print("PSNR_D2:", m["psnr_d2"])
+        if rate_report and world == 1 and rate_sums[3]:
+            print("bpp ideal / table / coded (mean):", *[v / rate_sums[3] for v in rate_sums[:3]])
         if combine and args.type in ("kitti", "ford"):
             tag = "mul" if mullevel else "same"
             out = (f"{tag} {args.lidar_level} {args.test_files} {args.ckpt_path}\nsample number: {m['count']}\ntimes: {m['time']}\n"

@@ -11,6 +11,7 @@ This is the hot path of encode.py:85-160 (compress_ehem) / encode_mullevel.py:88
 Per-window softmax, the [N,255] PMF table on the host, the int64 [N,4,6] records and the per-level Python loops of
 the reference do not exist here.  The returned dict carries the same scalars the reference prints.
 """
+import math
 import time
 from concurrent.futures import ThreadPoolExecutor
 
@@ -143,14 +144,70 @@ def _upload_ints(hq, device):
     return qs
 
 
-def _result(stream, meta, times, debug=None):
+def _result(stream, meta, times, debug=None, rate=None):
     """The dict every entry point of both encoders returns: the coded stream and its size, the frame's `meta` fields (what the reference
-    prints, what its file names and the side-info file carry), the wall times; `_debug` (device tensors) from the synchronous calls only."""
+    prints, what its file names and the side-info file carry), the wall times; `_debug` (device tensors) from the synchronous calls only.
+    rate: (host scp_rate_seg records, the frame's levels in `_rate_layout` form) of an encoder made with rate=True -> the `rate` entry."""
     bits = 8 * len(stream)
     res = dict(bytes=stream, bits=bits, bpp=bits / meta["n_points"], times=times, **meta)
     if debug is not None:
         res["_debug"] = debug
+    if rate is not None:
+        res["rate"] = _rate_report(rate[0], rate[1], bits, meta["n_points"])
     return res
+
+
+def _rate_layout(level_sizes, context_size=None):
+    """The segments of a coding-order table the rate report sums over (native.rate_segments), from level sizes alone (host bookkeeping,
+    the windows of EncodePlan): -> (the n_seg + 1 row offsets, per level its segment indices).  context_size None: one segment per level
+    (plain BFS coding order, OctAttention) - ([index],).  EHEM: two per window of context_size rows, in coding order the window's first
+    (c + 1) // 2 rows (phase 1: the first siblings) and the rest (phase 2: the second siblings, predicted through the cross-attention
+    encoder) - (phase-1 indices, phase-2 indices); a window of one row has an empty phase 2, a level of no rows no segment."""
+    off, levels, row = [0], [], 0
+    for n in level_sizes:
+        if context_size is None:
+            levels.append(([len(off) - 1],))
+            off.append(row + n)
+        else:
+            p1, p2 = [], []
+            for i in range(0, n, context_size):
+                c = min(context_size, n - i)
+                p1.append(len(off) - 1)
+                off.append(row + i + (c + 1) // 2)
+                p2.append(len(off) - 1)
+                off.append(row + i + c)
+            levels.append((p1, p2))
+        row += n
+    return off, levels
+
+
+def _rate_sum(raw, idx):
+    """Segments `idx` of the host records (numpy int64 [S,5]: rows, ideal_bits, table_bits, top1, bad_rows - the two sums as float64 bit
+    patterns) added up: math.fsum, i.e. correctly rounded and therefore the same whatever else the launch held."""
+    f = raw.view(np.float64)
+    return dict(nodes=int(raw[idx, 0].sum()), ideal_bits=math.fsum(f[idx, 1]), table_bits=math.fsum(f[idx, 2]), top1=int(raw[idx, 3].sum()),
+                bad_rows=int(raw[idx, 4].sum()))
+
+
+def _rate_report(raw, levels, bits, n_points):
+    """The `rate` entry of a result dict ("Rate report"): per level of `level_sizes` nodes / ideal_bits / table_bits / top1
+    (EHEM: also under phase1 / phase2), the frame's totals, bits per point and per node, and what the range coder spent beyond its table."""
+    out_levels, everything = [], []
+    for parts in levels:
+        idx = [i for p in parts for i in p]
+        everything += idx
+        entry = _rate_sum(raw, idx)
+        entry.pop("bad_rows")
+        if len(parts) == 2:
+            for name, p in zip(("phase1", "phase2"), parts):
+                entry[name] = _rate_sum(raw, p)
+                entry[name].pop("bad_rows")
+        out_levels.append(entry)
+    total = _rate_sum(raw, everything)
+    nodes = total["nodes"]
+    return dict(levels=out_levels, ideal_bits=total["ideal_bits"], table_bits=total["table_bits"], bad_rows=total["bad_rows"],
+                bpp_ideal=total["ideal_bits"] / n_points, bpp_table=total["table_bits"] / n_points,
+                bits_per_node_ideal=total["ideal_bits"] / max(nodes, 1), coder_overhead_bits=bits - total["table_bits"])
 
 
 class _CoderPipeline:
@@ -181,9 +238,12 @@ class _CoderPipeline:
         main.wait_stream(caller)
         return main
 
-    def submit(self, main, lohi, fills0, cuts=None):
-        """lohi: the frame's pairs, enqueued on `main` (the last thing of its model part).  -> future of the coded stream, or - cuts: row
-        bounds of the frames of a batch - of the list of every frame's own stream.  fills0: native.CACHE_FILLS before the frame began."""
+    def submit(self, main, lohi, fills0, cuts=None, rate=None):
+        """lohi: the frame's pairs, enqueued on `main` (the last thing of its model part).  -> (future of the coded stream, or - cuts: row
+        bounds of the frames of a batch - of the list of every frame's own stream; None).  fills0: native.CACHE_FILLS before the frame began.
+        rate: the device records of the frame's rate report (native.rate_segments, enqueued on `main` behind the pairs): they ride to a pinned
+        host tensor on the copy stream next to the pairs - no wait on this thread - and that tensor takes the place of the None; it is
+        complete once the future is."""
         done = torch.cuda.Event()
         done.record(main)
         if native.CACHE_FILLS != fills0:               # device-side caches were built during this call (first frames only):
@@ -193,6 +253,11 @@ class _CoderPipeline:
             self.copy_stream.wait_event(done)
             host.copy_(lohi, non_blocking=True)
             lohi.record_stream(self.copy_stream)
+            rate_host = None
+            if rate is not None:
+                rate_host = torch.empty(rate.shape, dtype=rate.dtype, pin_memory=True)
+                rate_host.copy_(rate, non_blocking=True)
+                rate.record_stream(self.copy_stream)
             copied = torch.cuda.Event(blocking=True)      # the coder thread SLEEPS until the pairs have landed (a default event spins a core)
             copied.record()
 
@@ -203,7 +268,7 @@ class _CoderPipeline:
                 return native.ac_encode_lohi(h)
             return [native.ac_encode_lohi(h[a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
 
-        return self.pool.submit(work)
+        return self.pool.submit(work), rate_host
 
 
 class _FrontEnd:
@@ -211,8 +276,9 @@ class _FrontEnd:
     device quantiser, and the lazily created coding pipeline of the asynchronous calls."""
     LANES_ENV = None                      # the environment variable that sets the number of lanes (read at the first asynchronous call)
 
-    def __init__(self, model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform):
+    def __init__(self, model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate=False):
         self.model = model
+        self.rate = bool(rate)                # every result dict gains `rate` (one more read of the logits table per frame; the stream's bytes stay)
         # strict-identity switch (CLI --host_transform, SCP_XFORM=numpy): the float -> integer step of the reference on the host
         # (numpy float32 arctan2 / arccos, data_preprocess.py:42-70) instead of the device transform, whose float64 atan2 / acos is
         # more accurate and therefore gives other integers for a few points per frame (DESIGN.md 2.1).  Everything after the
@@ -271,16 +337,28 @@ class _FrontEnd:
             self._pipe = _CoderPipeline(self.device, self.LANES_ENV)
         return self._pipe
 
+    RATE_PHASES = False                   # EHEM: the report's segments follow the two-phase coding order of the windows
+
+    def _rate_launch(self, table, sym_coded, lohi, level_sizes):
+        """rate=True: the rate kernels on the current stream, right behind the CDF launch that wrote `lohi` -> (device records and what
+        their launches use - to be held until they have run -, the levels' segment lists); (None, None) when the report is off."""
+        if not self.rate:
+            return None, None
+        off, levels = _rate_layout(level_sizes, self.context_size if self.RATE_PHASES else None)
+        r = native.rate_segments(table, sym_coded, lohi, off)
+        return (r["raw"], r["keep"]), levels
+
 
 class FrameEncoder(_FrontEnd):
     LANES_ENV = "SCP_LANES"
+    RATE_PHASES = True
 
     def __init__(self, model, data_type=KITTI, lidar_level=12, spher=True, cylin=False, mullevel=False, max_batch=8,
-                 device=None, packed=True, max_tokens=1_000_000, host_transform=None, profile=None):
+                 device=None, packed=True, max_tokens=1_000_000, host_transform=None, profile=None, rate=False):
         if mullevel and not (spher or cylin):
             # encode_dataset_ehem_mullevel.py:97-186 has a cylindrical and a spherical branch only
             raise native.ScpError("--mullevel needs --spher or --cylin (the reference has no Cartesian multi-level path)")
-        super().__init__(model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform)
+        super().__init__(model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate)
         self.profile = profile          # native.NumericProfile of THIS encoder (None: the process default); current around every launch
         self.packed = packed            # one packed forward for all windows (default) vs one forward per group of equal windows
         self.max_tokens = max_tokens
@@ -500,7 +578,9 @@ class FrameEncoder(_FrontEnd):
         with torch.cuda.stream(main):
             table = self.logits_in_coding_order(front["pre"], front["plan"])
             lohi = native.softmax_cdf(table, front["sym_coded"])["lohi"]
-        return dict(future=self._pipeline().submit(main, lohi, fills0, cuts), t0=t0, front=front, keep=(table, lohi))
+            rate, levels = self._rate_launch(table, front["sym_coded"], lohi, front["plan"].level_sizes)
+        future, rate_host = self._pipeline().submit(main, lohi, fills0, cuts, rate[0] if rate else None)
+        return dict(future=future, t0=t0, front=front, keep=(table, lohi, rate), rate=(rate_host, levels))
 
     def encode_async(self, xyz, ints=None, front=None):
         """Like encode(), but the front part runs on the front stream, the model part on the next lane, and the D2H copy of the
@@ -576,12 +656,19 @@ class FrameEncoder(_FrontEnd):
 
     def finish_batch(self, h):
         metas = h["front"]["metas"]
-        return [_result(stream, self._meta(m, m["n_nodes"]), dict(total=(time.perf_counter() - h["t0"]) / len(metas)))
-                for stream, m in zip(h["future"].result(), metas)]
+        streams = h["future"].result()
+        rates, (rate_host, levels) = [None] * len(metas), h["rate"]
+        if rate_host is not None:              # the batch's levels are the frames' level lists one after the other
+            cuts = np.concatenate(([0], np.cumsum([len(m["level_sizes"]) for m in metas])))
+            rates = [(rate_host.numpy(), levels[a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
+        return [_result(stream, self._meta(m, m["n_nodes"]), dict(total=(time.perf_counter() - h["t0"]) / len(metas)), rate=r)
+                for stream, m, r in zip(streams, metas, rates)]
 
     def finish(self, h):
         stream = h["future"].result()
-        return _result(stream, self._meta(h["front"]["pre"], h["front"]["plan"].n_rows), dict(total=time.perf_counter() - h["t0"]))
+        rate_host, levels = h["rate"]
+        return _result(stream, self._meta(h["front"]["pre"], h["front"]["plan"].n_rows), dict(total=time.perf_counter() - h["t0"]),
+                       rate=None if rate_host is None else (rate_host.numpy(), levels))
 
     def _encode_pre(self, pre, t0, timing):
         if timing:
@@ -593,12 +680,14 @@ class FrameEncoder(_FrontEnd):
         if timing:
             torch.cuda.synchronize()
         t2 = time.perf_counter()
-        lohi = native.softmax_cdf(table, sym_coded)["lohi"].cpu().numpy()
+        lohi_dev = native.softmax_cdf(table, sym_coded)["lohi"]
+        rate, levels = self._rate_launch(table, sym_coded, lohi_dev, plan.level_sizes)
+        lohi = lohi_dev.cpu().numpy()
         t3 = time.perf_counter()
         stream = native.ac_encode_lohi(lohi)
         t4 = time.perf_counter()
         return _result(stream, self._meta(pre, plan.n_rows), dict(geom=t1 - t0, model=t2 - t1, cdf=t3 - t2, coder=t4 - t3, total=t4 - t0),
-                       debug=dict(table=table, sym_coded=sym_coded, pre=pre))
+                       debug=dict(table=table, sym_coded=sym_coded, pre=pre), rate=rate and (rate[0].cpu().numpy(), levels))
 
     def outfile(self, base, res):
         """encode.py:140-144 file name."""
@@ -623,7 +712,7 @@ class OctAttnFrameEncoder(_FrontEnd):
     LANES_ENV = "SCP_LANES_OCTATTN"
 
     def __init__(self, model, data_type=KITTI, lidar_level=12, spher=True, cylin=False, max_batch=128, device=None, mullevel=False,
-                 level_wise=False, named=False, host_transform=None, decodable=False):
+                 level_wise=False, named=False, host_transform=None, decodable=False, rate=False):
         # decodable=True: the octattn/1d numeric profile (models/oct_attention.py) - every PMF row a function of its own window's rows
         # 0..t, so OctAttnFrameDecoder can reproduce it node by node; the default (octattn/1) keeps the round-6 bits
         self.decodable = bool(decodable)
@@ -632,7 +721,7 @@ class OctAttnFrameEncoder(_FrontEnd):
         if mullevel and (cylin or not spher):
             # encode_dataset_mullevel.py:76-86: the three-shell records exist for --spher only
             raise native.ScpError("OctAttention multi-level encoding needs --spher (encode_dataset_mullevel.py:76)")
-        super().__init__(model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform)
+        super().__init__(model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate)
         self.level_wise = level_wise
         self.named = named or mullevel        # encode_mullevel.py's file-name scheme (also for its single-shell Cartesian input)
 
@@ -794,10 +883,12 @@ class OctAttnFrameEncoder(_FrontEnd):
         z_off = float(quant[0]["offset"][2]) if (quant and self.cylin) else 0.0
         meta = dict(n_nodes=N, n_points=n_points, bin_num=bin_num, z_offset=z_off, quant=quant, n_levels=len(chunks), pos_mm=np.zeros((0, 2)),
                     level_sizes=[c[2] for c in chunks], depth=int(self.geom.info[0].depth), sequential=bool(sequential))
+        rate, levels = self._rate_launch(table, sym, lohi, meta["level_sizes"])
         if defer:
-            return lohi, meta, (table, sym, chunks)
+            return lohi, meta, (table, sym, chunks), (rate, levels)
         stream = native.ac_encode_lohi(lohi.cpu().numpy())
-        return _result(stream, meta, dict(total=time.perf_counter() - t0), debug=dict(table=table, sym_coded=sym))
+        return _result(stream, meta, dict(total=time.perf_counter() - t0), debug=dict(table=table, sym_coded=sym),
+                       rate=rate and (rate[0].cpu().numpy(), levels))
 
     def encode_async(self, xyz):
         """Like encode(), but stage G runs on the front stream, the model part on the next lane, and the D2H copy of the (c_low, c_high)
@@ -821,14 +912,16 @@ class OctAttnFrameEncoder(_FrontEnd):
             ready.record()
         main.wait_event(ready)
         with torch.cuda.stream(main):
-            lohi, meta, keep = self.encode_ints(q, bin_num, xyz_dev.shape[0], t0, defer=True, front=front, quant=self.quant_info())
+            lohi, meta, keep, (rate, levels) = self.encode_ints(q, bin_num, xyz_dev.shape[0], t0, defer=True, front=front, quant=self.quant_info())
         # (the handle keeps what the front stream allocated - the frame, its integers, the context sequences - and the table referenced
         # until finish(): see FrameEncoder._model_async)
-        return dict(future=pipe.submit(main, lohi, fills0), meta=meta, t0=t0, keep=(keep, lohi, q, xyz_dev))
+        future, rate_host = pipe.submit(main, lohi, fills0, rate=rate[0] if rate else None)
+        return dict(future=future, meta=meta, t0=t0, keep=(keep, lohi, q, xyz_dev, rate), rate=(rate_host, levels))
 
     def finish(self, h):
         stream = h["future"].result()
-        return _result(stream, h["meta"], dict(total=time.perf_counter() - h["t0"]))
+        rate_host, levels = h["rate"]
+        return _result(stream, h["meta"], dict(total=time.perf_counter() - h["t0"]), rate=None if rate_host is None else (rate_host.numpy(), levels))
 
     def outfile(self, base, res):
         """encode.py:24 (`<base>.bin`) / encode_mullevel.py:68-72 (`<base>[_spher|_cylin]_<chunks>_<bin_num>_0.bin`)."""

@@ -148,6 +148,8 @@ def lib():
         "scp_linear_f32": (C.c_int, [_vp, i64, _vp, _vp, _vp, i64, i32, i32, i32, i32, _vp]),
         "scp_softmax_cdf": (C.c_int, [_vp, i64, i64, i32, _vp, _vp, _vp, _vp, _vp]),
         "scp_pmf_cdf": (C.c_int, [_vp, i64, i32, _vp, _vp, _vp, _vp]),
+        "scp_rate_workspace_bytes": (C.c_int64, [i64, i32]),
+        "scp_rate_segments": (C.c_int, [_vp, i64, i64, i32, _vp, _vp, _vp, i32, _vp, _vp, _vp, _vp, i64, _vp]),
         "scp_ac_encode_cdf": (C.c_int, [_vp, _vp, i64, i32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "scp_ac_encode_lohi": (C.c_int, [_vp, i64, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "scp_ac_dec_new": (C.c_int, [C.POINTER(_vp), _vp, C.c_size_t, i32]),
@@ -203,7 +205,7 @@ def _opt(t):
 # ------------------------------------------------------------------------------------------------- launch brackets (scp_debug.h)
 PROF_TAGS = {1: "post_attn", 2: "ln_linear", 3: "attention", 4: "knn_feat", 5: "knn_pos", 6: "gemm_split", 7: "edge_mlp", 8: "merge",
              9: "edge_gather", 10: "cdf", 11: "gemm_f32", 12: "gemm_rows", 13: "split_rows", 14: "layernorm", 15: "oa_attention", 16: "geom",
-             17: "other", 18: "mlp3"}
+             17: "other", 18: "mlp3", 19: "rate"}
 
 
 class launch_profile:
@@ -1629,6 +1631,41 @@ def pmf_cdf(pmf, sym=None, want_cdf=False):
     rc = lib().scp_pmf_cdf(_dev(pmf, torch.float32), n, nsym, _opt(sym), _opt(lohi), _opt(cdf), _stream())
     _check(rc, "scp_pmf_cdf")
     return dict(lohi=lohi, cdf=cdf)
+
+
+RATE_FIELDS = ("rows", "ideal_bits", "table_bits", "top1", "bad_rows")     # include/scp.h: scp_rate_seg, five 8-byte fields
+
+
+def rate_segments(logits, sym, lohi, seg_off, want_rows=False):
+    """Rate report of a coding-order logits table (csrc/rate.hip: scp_rate_segments).  logits cuda f32 [n,nsym] (row stride allowed), sym
+    uint8 [n], lohi int32 [n] as softmax_cdf returns it; seg_off: the n_seg + 1 row offsets of the segments - a device int64 tensor, or a
+    host sequence (then uploaded out of pinned memory on the current stream: nothing is awaited).  -> dict of device tensors per segment:
+    rows, top1, bad_rows int64 [S], ideal_bits, table_bits float64 [S] (views of `raw` int64 [S,5], the scp_rate_seg records: one copy
+    brings them all to the host); with want_rows also row_ideal, row_table float64 [n]; `keep`: what the launches use (workspace,
+    offsets) - hold it until they have run."""
+    n, nsym = logits.shape
+    if logits.stride(1) != 1:
+        raise ScpError("rate_segments: unit column stride expected")
+    dev = logits.device
+    if not isinstance(seg_off, torch.Tensor):
+        host = torch.from_numpy(np.ascontiguousarray(seg_off, np.int64))
+        seg_off = (host.pin_memory() if torch.cuda.is_available() else host).to(dev, non_blocking=True)
+    S = int(seg_off.shape[0]) - 1
+    if S < 0 or sym.shape[0] != n or lohi.shape[0] != n:
+        raise ScpError("rate_segments: one symbol and one pair per row, and at least one offset, expected")
+    raw = torch.empty((S, len(RATE_FIELDS)), dtype=torch.int64, device=dev)
+    ws_bytes = int(lib().scp_rate_workspace_bytes(n, S))
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    ri = torch.empty(n, dtype=torch.float64, device=dev) if want_rows else None
+    rt = torch.empty(n, dtype=torch.float64, device=dev) if want_rows else None
+    ld = int(logits.stride(0)) if n > 1 else max(int(logits.stride(0)), nsym)      # (the stride of a single row says nothing)
+    rc = lib().scp_rate_segments(logits.data_ptr(), ld, n, nsym, _dev(sym, torch.uint8),
+                                 _dev(lohi), _dev(seg_off, torch.int64), S, raw.data_ptr(), _opt(ri), _opt(rt), ws.data_ptr(), ws_bytes, _stream())
+    _check(rc, "scp_rate_segments")
+    out = dict(raw=raw, keep=(ws, seg_off), row_ideal=ri, row_table=rt)
+    for k, name in enumerate(RATE_FIELDS):
+        out[name] = raw[:, k].view(torch.float64) if name.endswith("_bits") else raw[:, k]
+    return out
 
 
 # ------------------------------------------------------------------------------------------------- range coder (host)
