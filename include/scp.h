@@ -44,7 +44,9 @@ extern "C" {
  *        kernel that applies it; scp_swin_post_attn expects fc1 scaled by scp_gelu_prescale() and fc2 by its inverse.
  *        (additive, no new version: scp_decode_expand, scp_linear_split_f16_max, scp_row_scale_from_max, scp_octattn_attention_f16x3_vmax;
  *        round 6: scp_linear_split_hier2, scp_mlp3_rows; scp_octattn_attention_rowinv, scp_decode_expand_octattn, scp_octattn_attention_rowinv_step, scp_decode_expand_batch - existing entry points keep their bits, the EHEM model's numeric profile moved to ehem/6
- *        because models/packed.py now calls the two new ones; D2 PSNR: scp_estimate_normals_f64, scp_nn_tieset_f64.) */
+ *        because models/packed.py now calls the two new ones; D2 PSNR: scp_estimate_normals_f64, scp_nn_tieset_f64;
+ *        rate report: scp_rate_segments; distortion report: scp_nn_error_split_f64, scp_dist_segments_f64 - additive like the others, so
+ *        SCP_ABI_VERSION and native.ABI_VERSION stay together at 220.) */
 #define SCP_ABI_VERSION 220
 SCP_API int scp_version(void);
 SCP_API int scp_last_hip_error(void);
@@ -490,6 +492,57 @@ SCP_API int scp_estimate_normals_f64(const double *xyz, int64_t n, double radius
                                      int32_t *count, int32_t *idx, void *stream);
 SCP_API int scp_nn_tieset_f64(int32_t mode, const double *q, int64_t nq, const double *p, int64_t np, const double *dmin, const double *nrm,
                               double *out, void *stream);
+
+/* Distortion report (csrc/distreport.hip; additive, no new ABI version; host side: scp_amd/metrics.py distortion_report): where a frame's
+ * error goes - per range ring and per caller-given group (the encoder: per rho shell), split along the sensor's spherical axes.
+ * A = the query cloud [na][3], B = the searched cloud [nb][3], float64 DEVICE pointers, finite coordinates, 1 .. 2^30 points each;
+ * view = the sensor position, 3 HOST doubles.
+ *
+ * scp_nn_error_split_f64, per query i:
+ *   neighbour  d2(i,j) = (dx*dx + dy*dy) + dz*dz, dx = a_i.x - b_j.x ..., the arithmetic and rounding of scp_nn_sqdist_f64;
+ *              d2_out[i] = min_j d2(i,j) and idx_out[i] = j*(i) = the LOWEST j whose d2(i,j) equals that minimum bit for bit.  Both come
+ *              from integer atomicMin reductions, so neither depends on how the launch splits B or on the order tiles are visited in.
+ *   split      e = b_j* - a_i.  With (x,y,z) = a_i - view, s2 = x*x + y*y, s = sqrt(s2), rho2 = s2 + z*z, rho = sqrt(rho2):
+ *              r^ = (x,y,z)/rho, phi^ = (-y,x,0)/s, theta^ = (xz, yz, -s2)/(rho s) (growing polar angle arccos(z/rho));
+ *              comp_out[i] = (e.r^, e.phi^, e.theta^), accurate to a few ulp of |e|.  s == 0 (on the sensor's axis, or at the sensor):
+ *              no frame - an AXIS point: comp_out[i] = 0 and SCP_DIST_FLAG_AXIS in flag_out[i].
+ *   bin        edges_sq = n_rings HOST doubles, the SQUARES of the ring edges 0 = E_0 < E_1 < ... (finite, strictly increasing; the last
+ *              ring is open-ended; 1 <= n_rings <= SCP_DIST_MAX_RINGS).  ring(i) = the largest r with rho2 >= edges_sq[r]: decided on
+ *              rho2, no sqrt takes part, a point exactly on an edge belongs to the upper ring.  group int32 [na] (DEVICE; NULL: all 0),
+ *              0 <= group[i] < n_groups; bin_out[i] = group[i] * n_rings + ring(i); n_groups * n_rings <= SCP_DIST_MAX_BINS.
+ *              A group value outside [0, n_groups) is CLAMPED in the kernel and the row flagged SCP_DIST_FLAG_GROUP_CLAMPED, so no bin is
+ *              ever out of range (scp_amd/native.py checks the range before the launch and refuses).
+ *   A query no pair of which reproduces the minimum (only non-finite coordinates do that) gets idx -1, d2 0, components 0 and
+ *   SCP_DIST_FLAG_NO_NEIGHBOUR; nothing is read through its index.
+ * Every argument is checked before any launch: a NULL pointer (group excepted), na / nb outside 1 .. 2^30, n_groups < 1, n_rings outside
+ * 1 .. SCP_DIST_MAX_RINGS, edges that do not start at 0 or do not strictly increase, more than SCP_DIST_MAX_BINS bins or a non-finite
+ * view return SCP_EINVAL.
+ *
+ * scp_dist_segments_f64: one scp_dist_seg per bin from the per-query values above.  The rows of bin k are order[seg_off[k]] ..
+ * order[seg_off[k+1] - 1] (order int64 [n], DEVICE: a STABLE sort of the bins, so that a bin's rows come in index order; NULL: the rows
+ * lie in bin order already; seg_off int64 [n_bins + 1], DEVICE, non-decreasing; offsets are clamped to [0, n] and an order entry outside
+ * [0, n) is skipped).  Summation order is part of the contract: thread t of the bin's one workgroup adds rows t, t + 1024, .. of the bin
+ * in that order, then a fixed binary tree runs over the 1024 partial sums - a bin's sums are a function of that bin's rows in index
+ * order and of nothing else (not of the other bins, of n_bins or of the launch), the same bits in every run; no floating-point atomics.
+ *   rows, axis_rows   all rows of the bin / its axis points (which count in rows, sum_sq, max_sq and hist and add nothing to the other sums)
+ *   sum_sq = sum d2, sum_r2 = sum e_r^2, sum_phi2 = sum e_phi^2, sum_theta2 = sum e_theta^2, sum_r = sum e_r;  max_sq = max d2 (0: empty bin)
+ *   hist[0] = rows with d2 == 0; hist[k] = rows with k == clamp(floor(log2 d2) + 41, 1, 63), read from the exponent bits: bucket k holds
+ *   2^(k-41) <= d2 < 2^(k-40), both tails absorbed.
+ * n outside 1 .. 2^30, n_bins outside 1 .. SCP_DIST_MAX_BINS or a NULL pointer (order excepted): SCP_EINVAL, nothing launched. */
+#define SCP_DIST_MAX_RINGS 64
+#define SCP_DIST_MAX_BINS 4096
+#define SCP_DIST_MAX_POINTS (1ll << 30)
+enum { SCP_DIST_FLAG_AXIS = 1, SCP_DIST_FLAG_GROUP_CLAMPED = 2, SCP_DIST_FLAG_NO_NEIGHBOUR = 4 };
+typedef struct scp_dist_seg {
+    int64_t rows, axis_rows;
+    double sum_sq, sum_r2, sum_phi2, sum_theta2, sum_r, max_sq;
+    int64_t hist[64];
+} scp_dist_seg;
+SCP_API int scp_nn_error_split_f64(const double *a, int64_t na, const double *b, int64_t nb, const double *view, const double *edges_sq,
+                                   int32_t n_rings, const int32_t *group /* NULL ok */, int32_t n_groups, int32_t *idx_out, double *d2_out,
+                                   double *comp_out /* [na][3] */, int32_t *bin_out, uint8_t *flag_out, void *stream);
+SCP_API int scp_dist_segments_f64(const double *d2, const double *comp, const uint8_t *flag, const int64_t *order /* NULL ok */, int64_t n,
+                                  const int64_t *seg_off, int32_t n_bins, scp_dist_seg *out, void *stream);
 
 /* Input stage of the packed EHEM forward: embeddings of dgcnn.py:121-128 fused with the packed layout's input gather.
  * ctx u8 [T][12] = 4 x (level, octant, occ) (scp_geom_context_ehem), pos f32 [T][3], inmap i64 [rows] (== n_tokens: pad token);

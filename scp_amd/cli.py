@@ -12,6 +12,10 @@ same stdout block per frame, same summary file.  Differences, all additive:
   * `--rate_report`: where every frame's bits go - the model's cross-entropy (ideal bits), the cost of the coder's 16-bit tables and the
     coded size, per octree level (EHEM: per phase), computed on the device (csrc/rate.hip): one more line per frame and a
     `<stream>.rate.json` next to every stream.  The streams themselves do not change.
+  * `--distortion_report [EDGES]` (EHEM): where every frame's D1 error goes - per range ring (EDGES: comma-separated ring edges starting at
+    0, by default 0,5,10,15,20,30,40,60,80 m for KITTI and the same in millimetres for Ford) and per rho shell, split along the sensor's
+    r / phi / theta axes, computed on the device (csrc/distreport.hip): one more line per frame and a `<stream>.dist.json` next to every
+    stream.  The streams themselves do not change.
   * `--normals estimate|DIR` (with `--metrics`, EHEM): the D2 (point-to-plane) PSNR as well, on normals estimated on the device or
     read from the `<DIR>/<sequence>/<frame>.ply` files `gene_normals.py` writes; one more line per frame, `PSNR_D2:` in the summary.
 """
@@ -59,6 +63,21 @@ def load_cfg(ckpt_path, model_name=None):
     return Cfg(model=model, data=dict(extra_pos=False), train=dict(type="kitti", dropout=0.0))
 
 
+def parse_edges(text):
+    """`--distortion_report 0,5,10`: the ring edges as a tuple of floats (native.dist_edges states what a valid list is)."""
+    try:
+        vals = [float(v) for v in text.split(",")]
+    except ValueError:
+        raise native.ScpError(f"--distortion_report: ring edges are comma-separated numbers starting at 0, got {text!r}")
+    return native.dist_edges(vals)
+
+
+def distortion_request(args):
+    """(wanted, edges) of --distortion_report: (False, None) without the flag, (True, None) for the data type's default edges."""
+    v = getattr(args, "distortion_report", None)
+    return (v is not None and v is not False), (None if v is None or isinstance(v, bool) else tuple(v))
+
+
 def get_args(argv=None, mullevel=False):
     p = argparse.ArgumentParser()
     p.add_argument("--ckpt_path", type=str, default="", help="example: outputs/obj/2023-04-28/10-43-45/ckpt/epoch=7-step=64088.ckpt")
@@ -88,6 +107,12 @@ def get_args(argv=None, mullevel=False):
     p.add_argument("--rate_report", action="store_true", default=argparse.SUPPRESS,
                    help="per frame: ideal (cross-entropy), coded-table and coded bits per point on one more line, and <stream>.rate.json next to "
                         "the stream with the same figures per octree level (EHEM: per phase); the streams do not change")
+    # (absent from the namespace unless given, like --rate_report: read it with distortion_request(args))
+    p.add_argument("--distortion_report", nargs="?", const=True, type=parse_edges, default=argparse.SUPPRESS, metavar="EDGES",
+                   help="per frame (EHEM): the D1 error per range ring and rho shell, split along r / phi / theta, on one more line and in "
+                        "<stream>.dist.json next to the stream (the line: MSE and shares of the direction with the larger MSE, as D1's mseF takes it, "
+                        "and the largest error of both directions); EDGES = comma-separated ring edges from 0 (default: 0,5,10,15,20,30,40,60,80 m "
+                        "for kitti, x 1000 for ford); the streams do not change")
     p.add_argument("--host_transform", action="store_true",
                    help="strict identity with the reference from the frame on: the coordinate transform + quantiser run in numpy float32 on the "
                         "host exactly as data_preprocess.py:42-70 does (the device transform is more accurate, hence not bit-identical); "
@@ -136,6 +161,18 @@ def refuse_unsupported(args, name, mullevel):
         raise native.ScpError("--metrics is available for the EHEM encoders only")
     if getattr(args, "normals", None) and (name == "OctAttention" or not args.metrics):
         raise native.ScpError("--normals adds the D2 PSNR to --metrics, which the EHEM encoders have: give --metrics as well, with an EHEM model")
+    want_dist, dist_edges = distortion_request(args)
+    if want_dist:
+        if name == "OctAttention":
+            raise native.ScpError("--distortion_report is available for the EHEM encoders only (like --metrics: the OctAttention encoders "
+                                  "keep no reconstructed cloud)")
+        if args.type == "obj":
+            raise native.ScpError("--distortion_report splits the error in the frame of a LiDAR sensor at the origin: --type obj has none")
+        if args.preproc_path:
+            raise native.ScpError("--distortion_report with --preproc_path: no geometry of the frame is built there, only its records are coded")
+        if dist_edges is None:
+            from . import metrics
+            metrics.default_edges(args.type)
     if args.type == "obj" and (args.spher or args.cylin or mullevel and name != "OctAttention"):
         raise native.ScpError("--type obj is Cartesian and single-level in the reference (proc_pc defaults); drop --spher/--cylin/mullevel")
     if args.sequential and name != "OctAttention":
@@ -259,6 +296,7 @@ def main(argv=None, mullevel=False):
     name = cfg.model.class_name
     refuse_unsupported(args, name, mullevel)
     rate_report = getattr(args, "rate_report", False)
+    want_dist, dist_edges = distortion_request(args)
     cls = OctAttention if name == "OctAttention" else EHEM
     if args.random_weights is not None or not args.ckpt_path:
         from .weights import fill_weights
@@ -288,9 +326,9 @@ def main(argv=None, mullevel=False):
 
     mine = D.shard(files, rank, world)
     # fast path: frames are enqueued with encode_async (stage G on a side stream, two model lanes, range coder on a worker thread)
-    # and finished three frames later - what bench.py measures.  Flows that need the frame's octree after the encode (--metrics),
+    # and finished three frames later - what bench.py measures.  Flows that need the frame's octree after the encode (--metrics, --distortion_report),
     # come from record files, or run the one-window-per-node mode stay on the synchronous call.
-    pipelined = not (args.preproc_path or args.metrics or args.sequential or obj)
+    pipelined = not (args.preproc_path or args.metrics or want_dist or args.sequential or obj)
     DEPTH = 3
     host_ints = enc.host_ints if (pipelined and name != "OctAttention" and enc.host_transform) else None
     reader = Prefetch(mine, post=host_ints)
@@ -303,7 +341,7 @@ def main(argv=None, mullevel=False):
         return (cur.split("/")[-2] + Path(cur).stem) if (args.type == "kitti" and name != "OctAttention" and "/" in cur.rstrip("/")
                                                           and len(cur.split("/")) >= 2) else Path(cur).stem
 
-    def report(cur, res, t_submit, dist=None):
+    def report(cur, res, t_submit, dist=None, drep=None):
         now = time.time()
         elapsed = now - max(last_done[0], t_submit)      # wall time this frame added to the run (frames overlap in the pipeline)
         last_done[0] = now
@@ -335,6 +373,12 @@ def main(argv=None, mullevel=False):
                 json.dump(dict(rate, model=name, profile=enc.profile_string(), lidar_level=args.lidar_level, bits=res["bits"],
                                n_points=res["n_points"], n_nodes=res["n_nodes"]), f, indent=1)
             rate_sums[0] += rate["bpp_ideal"]; rate_sums[1] += rate["bpp_table"]; rate_sums[2] += res["bpp"]; rate_sums[3] += 1
+        if drep:
+            worse = max((drep["a_to_b"]["total"], drep["b_to_a"]["total"]), key=lambda e: e["mse"])     # the direction D1's mseF takes
+            share = [worse[k] / worse["mse"] if worse["mse"] > 0 else 0.0 for k in ("mse_r", "mse_phi", "mse_theta")]
+            print("D1 mse, r/phi/theta, max    :", worse["mse"], *share, max(drep["a_to_b"]["total"]["max"], drep["b_to_a"]["total"]["max"]))
+            with open(outfile[:-len(".bin")] + ".dist.json", "w") as f:
+                json.dump(dict(drep, lidar_level=args.lidar_level, type=args.type, n_points=res["n_points"]), f, indent=1)
         sums[0] += res["bpp"]; sums[1] += dist["psnr"] if dist else 0.0; sums[2] += dist["chamfer"] if dist else 0.0
         sums[3] += elapsed; sums[4] += 1
 
@@ -367,7 +411,7 @@ def main(argv=None, mullevel=False):
                 c0, h0, ts = pending.pop(0)
                 report(c0, enc.finish(h0), ts)
             continue
-        dist = None
+        dist = drep = None
         if args.preproc_path:
             # encode_dataset_ehem.py:149-157 / ..._mullevel.py:147-155: records + meta written by the test-set generator
             pp = args.preproc_path + ((cur.split("/")[-2] + Path(cur).stem) if args.type == "kitti" else Path(cur).stem)
@@ -382,10 +426,13 @@ def main(argv=None, mullevel=False):
             res = enc.encode(xyz, sequential=args.sequential)
         else:
             res = enc.encode(xyz)
-            if args.metrics:
+            if args.metrics or want_dist:
                 x_dev = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], np.float32)).to(dev)
+            if args.metrics:
                 dist = enc.distortion(x_dev, normals=frame_normals(args.normals, cur, x_dev) if args.normals else None)
-        report(cur, res, t0, dist)
+            if want_dist:
+                drep = enc.distortion_report(x_dev, dist_edges)
+        report(cur, res, t0, dist, drep)
     for c0, h0, ts in pending:
         report(c0, enc.finish(h0), ts)
     total = D.reduce_summary(sums, dev)

@@ -394,6 +394,27 @@ class FrameEncoder(_FrontEnd):
         first = self._infos[0]
         return qs, first.bin_num, (first.offset[2] if self.cylin else 0.0)
 
+    def _reconstructed(self, infos=None):
+        """The de-quantised leaves of the octree of the last `encode` / `preprocess` call, one float64 [U_s,3] device tensor per shell."""
+        from . import metrics
+        pts = []
+        for s, info in enumerate(infos or self._infos):   # infos: per shell, anything with .qs[3] and .offset[3] (tests: the oracle's)
+            pts.append(metrics.dequantize(self.geom.leaves(s), info.qs, info.offset, spher=self.spher, cylin=self.cylin,
+                                          f32=not self.mullevel).double())
+        return pts
+
+    def distortion_report(self, xyz_dev, edges=None, infos=None):
+        """Where the D1 error of the frame just encoded goes (metrics.distortion_report on the cloud `distortion` measures): per range
+        ring of `edges` (None: metrics.default_edges of the data type; other types must give edges) and, for the reconstructed points, per
+        rho shell - `b_to_a["groups"][g]` holds exactly the leaves of shell g.  Sensor at the origin.  The dict gains `shell_leaves`."""
+        from . import metrics
+        edges = metrics.default_edges(self.data_type) if edges is None else edges
+        pts = self._reconstructed(infos)
+        group = torch.cat([torch.full((p.shape[0],), g, dtype=torch.int32, device=p.device) for g, p in enumerate(pts)])
+        rep = metrics.distortion_report(xyz_dev[:, :3], torch.cat(pts), edges, quant_group=group, n_groups=len(pts))
+        rep["shell_leaves"] = [int(p.shape[0]) for p in pts]
+        return rep
+
     def distortion(self, xyz_dev, infos=None, normals=None):
         """Chamfer distance and D1 PSNR of the frame just encoded (the octree of the last `encode` / `preprocess` call) against
         its input cloud, on the device - what the reference gets from distChamfer + the pc_error tool
@@ -401,11 +422,7 @@ class FrameEncoder(_FrontEnd):
         per input point: metrics.estimate_normals or a gene_normals.py file) the dict gains the D2 (point-to-plane) PSNR `psnr_d2` and its
         two directions `mse_ab_d2`, `mse_ba_d2`."""
         from . import metrics
-        pts = []
-        for s, info in enumerate(infos or self._infos):   # infos: per shell, anything with .qs[3] and .offset[3] (tests: the oracle's)
-            pts.append(metrics.dequantize(self.geom.leaves(s), info.qs, info.offset, spher=self.spher, cylin=self.cylin,
-                                          f32=not self.mullevel).double())
-        quant, peak = torch.cat(pts), metrics.PEAK.get(self.data_type, 1.0)
+        quant, peak = torch.cat(self._reconstructed(infos)), metrics.PEAK.get(self.data_type, 1.0)
         d = metrics.chamfer_psnr(xyz_dev, quant, peak)
         if normals is not None:
             p2 = metrics.d2_psnr(xyz_dev, normals, quant, peak)

@@ -18,9 +18,13 @@ points of A are merged as for D1 and take the mean of their normals; the tool's 
 not identified (a probe printed 0.919601 / 1.98458, which none of keep-all / mean / first / last / sum / normalised mean gives).
 The normals are not open3d's bit for bit: the neighbour sets agree except at exact distance ties, but the covariance is the centred
 two-pass one and the eigenvector comes from Jacobi sweeps - D2 on estimated normals is this project's number, D2 on given normals the tool's.
+
+`distortion_report` = where the D1 error goes (csrc/distreport.hip; no counterpart in the reference): the nearest-neighbour error of both
+directions per range ring and, for the reconstructed cloud, per rho shell, split along the sensor's (r, phi, theta) axes.
 """
 import math
 
+import numpy as np
 import torch
 
 from . import native
@@ -90,6 +94,85 @@ def d2_psnr(pc, normals, quant, peak, dropdups=True):
     mse = max(m_ab, m_ba)
     psnr = 10.0 * math.log10(3.0 * peak * peak / mse) if mse > 0 else float("inf")
     return dict(mse_ab=m_ab, mse_ba=m_ba, psnr_d2=psnr)
+
+
+DIST_SUMS = ("sum_sq", "sum_r2", "sum_phi2", "sum_theta2", "sum_r")
+DEFAULT_EDGES = {"kitti": (0.0, 5.0, 10.0, 15.0, 20.0, 30.0, 40.0, 60.0, 80.0)}          # metres; Ford counts millimetres
+DEFAULT_EDGES["ford"] = tuple(1000.0 * e for e in DEFAULT_EDGES["kitti"])
+
+
+def default_edges(data_type):
+    """The ring edges the report uses when none are given: KITTI 0, 5, 10, 15, 20, 30, 40, 60, 80 m, Ford the same in its millimetres."""
+    if data_type not in DEFAULT_EDGES:
+        raise native.ScpError(f"distortion report: no default ring edges for --type {data_type} (its unit of length is the file's own): "
+                              "give edges, e.g. --distortion_report 0,0.5,1,2")
+    return DEFAULT_EDGES[data_type]
+
+
+def _dist_entry(rows, axis_rows, sums, max_sq, hist):
+    """One entry of the report from raw sums (plain Python numbers).  mse = sum_sq / rows; mse_r, mse_phi, mse_theta = the component sums
+    over the same rows, so they add up to mse less what the axis points (which have no frame) carry; bias_r = sum_r / (rows - axis_rows);
+    max = sqrt(max_sq).  An entry without rows has zeros there."""
+    e = dict(rows=int(rows), axis_rows=int(axis_rows), max_sq=float(max_sq), hist=[int(h) for h in hist])
+    e.update({k: float(v) for k, v in zip(DIST_SUMS, sums)})
+    n, framed = e["rows"], e["rows"] - e["axis_rows"]
+    e["mse"] = e["sum_sq"] / n if n else 0.0
+    e["mse_r"] = e["sum_r2"] / n if n else 0.0
+    e["mse_phi"] = e["sum_phi2"] / n if n else 0.0
+    e["mse_theta"] = e["sum_theta2"] / n if n else 0.0
+    e["bias_r"] = e["sum_r"] / framed if framed else 0.0
+    e["max"] = math.sqrt(e["max_sq"])
+    return e
+
+
+def dist_entries(raw):
+    """scp_dist_seg records on the host (numpy int64 [n_bins, 72], native.dist_segments(...)["raw"].cpu().numpy()) -> one entry per bin."""
+    rec = native.dist_record_views(np.ascontiguousarray(raw, np.int64))
+    return [_dist_entry(rec["rows"][k], rec["axis_rows"][k], [rec[name][k] for name in DIST_SUMS], rec["max_sq"][k], rec["hist"][k])
+            for k in range(raw.shape[0])]
+
+
+def dist_total(entries):
+    """The entry of several bins together: counts and histograms add, the maximum is the largest, every sum is math.fsum over the bins."""
+    hist = [sum(e["hist"][k] for e in entries) for k in range(native.DIST_HIST)]
+    return _dist_entry(sum(e["rows"] for e in entries), sum(e["axis_rows"] for e in entries),
+                       [math.fsum(e[name] for e in entries) for name in DIST_SUMS], max([e["max_sq"] for e in entries] + [0.0]), hist)
+
+
+def distortion_dict(edges, raw_ab, raw_ba, n_groups=1):
+    """The report from the two directions' records on the host (no device needed): raw_ab int64 [R, 72] (pc -> quant, one bin per ring),
+    raw_ba int64 [n_groups * R, 72] (quant -> pc, bin = group * R + ring), R = len(edges).  Plain Python throughout (json.dumps takes it)."""
+    edges = list(native.dist_edges(edges))
+    R = len(edges)
+    if raw_ab.shape[0] != R or raw_ba.shape[0] != n_groups * R:
+        raise native.ScpError(f"distortion report: {raw_ab.shape[0]} and {raw_ba.shape[0]} records for {R} rings and {n_groups} groups")
+    ab, ba = dist_entries(raw_ab), dist_entries(raw_ba)
+    return dict(edges=edges, a_to_b=dict(rings=ab, total=dist_total(ab)),
+                b_to_a=dict(groups=[ba[g * R:(g + 1) * R] for g in range(n_groups)], total=dist_total(ba)))
+
+
+def _dist_direction(a, b, edges, group, n_groups, view):
+    s = native.nn_error_split(a, b, edges, group, n_groups, view)
+    return native.dist_segments(s["d2"], s["comp"], s["flag"], s["bin"], n_groups * len(edges))["raw"]
+
+
+def distortion_report(pc, quant, edges, quant_group=None, n_groups=1, view=(0.0, 0.0, 0.0)):
+    """Where the D1 error of `quant` [U,3] against `pc` [P,3] goes (device tensors, compared in float64), both directions:
+        a_to_b  every point of pc against its nearest point of quant, binned by the ORIGINAL point's range ring:   a_to_b["rings"][r]
+        b_to_a  every point of quant against its nearest point of pc, binned by (quant_group, ring of the RECONSTRUCTED point):
+                b_to_a["groups"][g][r]   (quant_group: device int32 [U], 0 <= g < n_groups - the encoder passes the rho shell; None: one group)
+    and a_to_b["total"], b_to_a["total"].  Ring r holds edges[r] <= rho < edges[r+1] as seen from `view`, the last ring is open-ended.
+    Every entry holds the raw sums of include/scp.h's scp_dist_seg (rows, axis_rows, sum_sq, sum_r2, sum_phi2, sum_theta2, sum_r, max_sq,
+    hist[64]) and mse, mse_r, mse_phi, mse_theta, bias_r, max derived from them (_dist_entry); the totals' sums are math.fsum over the
+    bins.  The nearest neighbour is the lowest index among equals and the sums run in a fixed order, so the report is the same bits in
+    every run.  No duplicate merging is done: a_to_b["total"]["sum_sq"] / P is the mse_ab of chamfer_psnr(..., dropdups=False).
+    Returns plain Python (one device -> host copy per direction)."""
+    a = pc.to(torch.float64).contiguous()
+    b = quant.to(torch.float64).contiguous()
+    edges = native.dist_edges(edges)
+    raw_ab = _dist_direction(a, b, edges, None, 1, view)
+    raw_ba = _dist_direction(b, a, edges, quant_group, n_groups, view)
+    return distortion_dict(edges, raw_ab.cpu().numpy(), raw_ba.cpu().numpy(), n_groups)
 
 
 def dequantize(leaves, qs, offset, spher=False, cylin=False, f32=False):

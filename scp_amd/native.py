@@ -150,6 +150,8 @@ def lib():
         "scp_pmf_cdf": (C.c_int, [_vp, i64, i32, _vp, _vp, _vp, _vp]),
         "scp_rate_workspace_bytes": (C.c_int64, [i64, i32]),
         "scp_rate_segments": (C.c_int, [_vp, i64, i64, i32, _vp, _vp, _vp, i32, _vp, _vp, _vp, _vp, i64, _vp]),
+        "scp_nn_error_split_f64": (C.c_int, [_vp, i64, _vp, i64, _vp, _vp, i32, _vp, i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "scp_dist_segments_f64": (C.c_int, [_vp, _vp, _vp, _vp, i64, _vp, i32, _vp, _vp]),
         "scp_ac_encode_cdf": (C.c_int, [_vp, _vp, i64, i32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "scp_ac_encode_lohi": (C.c_int, [_vp, i64, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "scp_ac_dec_new": (C.c_int, [C.POINTER(_vp), _vp, C.c_size_t, i32]),
@@ -1665,6 +1667,99 @@ def rate_segments(logits, sym, lohi, seg_off, want_rows=False):
     out = dict(raw=raw, keep=(ws, seg_off), row_ideal=ri, row_table=rt)
     for k, name in enumerate(RATE_FIELDS):
         out[name] = raw[:, k].view(torch.float64) if name.endswith("_bits") else raw[:, k]
+    return out
+
+
+DIST_MAX_RINGS, DIST_MAX_BINS = 64, 4096                                   # include/scp.h: SCP_DIST_MAX_*
+DIST_FLAG_AXIS, DIST_FLAG_GROUP_CLAMPED, DIST_FLAG_NO_NEIGHBOUR = 1, 2, 4  # include/scp.h: SCP_DIST_FLAG_*
+# include/scp.h: scp_dist_seg, eight 8-byte fields and the 64 buckets of the histogram
+DIST_FIELDS = ("rows", "axis_rows", "sum_sq", "sum_r2", "sum_phi2", "sum_theta2", "sum_r", "max_sq")
+DIST_HIST = 64
+
+
+def dist_edges(edges):
+    """The ring edges of a distortion report as a tuple of floats: 0 = E_0 < E_1 < ..., finite, at most DIST_MAX_RINGS.  Host only."""
+    try:
+        e = tuple(float(v) for v in edges)
+    except (TypeError, ValueError):
+        raise ScpError(f"distortion report: ring edges are a list of numbers, got {edges!r}")
+    if not e or e[0] != 0.0 or len(e) > DIST_MAX_RINGS or any(not (b > a) for a, b in zip(e, e[1:])) or not all(v * v < float("inf") for v in e):
+        raise ScpError(f"distortion report: ring edges must start at 0, increase strictly, be finite and number at most {DIST_MAX_RINGS}, got {e}")
+    return e
+
+
+def nn_error_split(a, b, edges, group=None, n_groups=1, view=(0.0, 0.0, 0.0)):
+    """scp_nn_error_split_f64 (csrc/distreport.hip).  a [na,3], b [nb,3] device tensors (compared in float64); edges: host list 0 = E_0 <
+    E_1 < ..; group int32 [na] device tensor with 0 <= group < n_groups (None: all 0); view: the sensor, three host numbers.  -> dict of
+    device tensors: idx int32 [na] (the LOWEST index among the nearest points of b), d2 float64 [na], comp float64 [na,3] (e_r, e_phi,
+    e_theta of e = b[idx] - a), bin int32 [na] (group * len(edges) + ring), axis bool [na] (no local frame: on the sensor's axis), flag
+    uint8 [na] (the DIST_FLAG_* bits).  Everything is checked before the launch; a group value out of range is refused here (one read-back
+    of the group's extremes), and the kernel would clamp and flag it."""
+    e = dist_edges(edges)
+    n_groups = int(n_groups)
+    if n_groups < 1 or n_groups * len(e) > DIST_MAX_BINS:
+        raise ScpError(f"nn_error_split: {n_groups} groups x {len(e)} rings: between 1 and {DIST_MAX_BINS} bins expected")
+    a, b = _dev_f64(a), _dev_f64(b)
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != 3 or b.shape[1] != 3 or a.shape[0] < 1 or b.shape[0] < 1:
+        raise ScpError(f"nn_error_split: clouds of shape [n,3] with n >= 1 expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    na = a.shape[0]
+    if group is not None:
+        if not group.is_cuda or group.dtype != torch.int32 or tuple(group.shape) != (na,):
+            raise ScpError(f"nn_error_split: group is a device int32 tensor with one entry per query ({na})")
+        group = group.contiguous()
+        lo, hi = int(group.min().item()), int(group.max().item())
+        if lo < 0 or hi >= n_groups:
+            raise ScpError(f"nn_error_split: group values {lo} .. {hi} outside 0 .. {n_groups - 1}")
+    view = tuple(float(c) for c in view)
+    if len(view) != 3 or not all(abs(c) < float("inf") for c in view):
+        raise ScpError(f"nn_error_split: view is the sensor position, three finite numbers, got {view}")
+    v = (C.c_double * 3)(*view)
+    esq = (C.c_double * len(e))(*[c * c for c in e])
+    dev = a.device
+    idx = torch.empty((na,), dtype=torch.int32, device=dev)
+    d2 = torch.empty((na,), dtype=torch.float64, device=dev)
+    comp = torch.empty((na, 3), dtype=torch.float64, device=dev)
+    bin_ = torch.empty((na,), dtype=torch.int32, device=dev)
+    flag = torch.empty((na,), dtype=torch.uint8, device=dev)
+    _check(lib().scp_nn_error_split_f64(a.data_ptr(), na, b.data_ptr(), b.shape[0], C.cast(v, _vp), C.cast(esq, _vp), len(e),
+                                        None if group is None else group.data_ptr(), n_groups, idx.data_ptr(), d2.data_ptr(), comp.data_ptr(),
+                                        bin_.data_ptr(), flag.data_ptr(), _stream()), "scp_nn_error_split_f64")
+    return dict(idx=idx, d2=d2, comp=comp, bin=bin_, axis=(flag & DIST_FLAG_AXIS) != 0, flag=flag)
+
+
+def dist_segments(d2, comp, flag, bins, n_bins):
+    """scp_dist_segments_f64: one record per bin 0 .. n_bins - 1 from the per-query tensors of nn_error_split (`flag`: its uint8 flags;
+    `bins`: its int32 bins, in any order - a stable sort brings every bin's rows together in index order, which the summation order
+    contract needs).  -> dict of device tensors, all views of `raw` int64 [n_bins, 72] (the scp_dist_seg records: one copy brings them all
+    to the host): rows, axis_rows int64 [n_bins]; sum_sq, sum_r2, sum_phi2, sum_theta2, sum_r, max_sq float64 [n_bins]; hist int64
+    [n_bins, 64].  A bin without rows is all zeros; a row whose bin lies outside 0 .. n_bins - 1 belongs to no record."""
+    n_bins = int(n_bins)
+    if n_bins < 1 or n_bins > DIST_MAX_BINS:
+        raise ScpError(f"dist_segments: between 1 and {DIST_MAX_BINS} bins expected, got {n_bins}")
+    for t, dt, name in ((d2, torch.float64, "d2"), (comp, torch.float64, "comp"), (flag, torch.uint8, "flag"), (bins, torch.int32, "bins")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
+            raise ScpError(f"dist_segments: {name} is a device tensor of {dt} (there is no CPU path in the product)")
+    n = d2.shape[0]
+    if n < 1 or tuple(d2.shape) != (n,) or tuple(comp.shape) != (n, 3) or tuple(flag.shape) != (n,) or tuple(bins.shape) != (n,):
+        raise ScpError(f"dist_segments: d2 [n], comp [n,3], flag [n], bins [n] with n >= 1 expected, got {tuple(d2.shape)}, {tuple(comp.shape)}, "
+                       f"{tuple(flag.shape)}, {tuple(bins.shape)}")
+    d2, comp, flag = d2.contiguous(), comp.contiguous(), flag.contiguous()
+    ordered, order = torch.sort(bins, stable=True)
+    seg_off = torch.searchsorted(ordered, torch.arange(n_bins + 1, dtype=torch.int32, device=bins.device)).to(torch.int64).contiguous()
+    raw = torch.empty((n_bins, len(DIST_FIELDS) + DIST_HIST), dtype=torch.int64, device=d2.device)
+    _check(lib().scp_dist_segments_f64(d2.data_ptr(), comp.data_ptr(), flag.data_ptr(), order.data_ptr(), n, seg_off.data_ptr(), n_bins,
+                                       raw.data_ptr(), _stream()), "scp_dist_segments_f64")
+    return dict(dist_record_views(raw), raw=raw)
+
+
+def dist_record_views(raw):
+    """The fields of scp_dist_seg records held as int64 [n_bins, 72] (a torch tensor or a numpy array, device or host) -> dict of views."""
+    f64 = (lambda c: c.view(torch.float64)) if isinstance(raw, torch.Tensor) else (lambda c: c.view(np.float64))
+    out = {}
+    for k, name in enumerate(DIST_FIELDS):
+        col = raw[:, k]
+        out[name] = col if name in ("rows", "axis_rows") else f64(col)
+    out["hist"] = raw[:, len(DIST_FIELDS):]
     return out
 
 
