@@ -148,7 +148,29 @@ def _octattn_result(side, codes, leaves, stats):
     return dict(codes=[codes], leaves=[leaves], points=pts, spher=spher, cylin=cylin, stats=stats)
 
 
-class OctAttnFrameDecoder:
+class _Stamps:
+    """Wall seconds per stage, for all four decoders: `stats` is None (nothing is measured, no synchronisation) or a dict that collects
+    them (bench.py --decode), assignable from outside at any time; every stamp then costs a device synchronisation."""
+    stats = None
+
+    def _t0(self):
+        if self.stats is None:
+            return 0.0
+        import time
+        torch.cuda.synchronize()
+        return time.perf_counter()
+
+    def _stamp(self, key, t0):
+        if self.stats is None:
+            return t0
+        import time
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        self.stats[key] = self.stats.get(key, 0.0) + (t - t0)
+        return t
+
+
+class OctAttnFrameDecoder(_Stamps):
     """The inverse of OctAttnFrameEncoder(decodable=True).  The octree is regenerated breadth first; a level's children, their context
     rows (occ, level, octant) x (ggp, gp, p, self) and positions come from one launch (native.decode_expand_octattn) once the level is
     decoded.  Node by node (the window rule of `octattn_window_of`; with `level_wise` every level is its own chunk): the unknown pass of
@@ -161,17 +183,7 @@ class OctAttnFrameDecoder:
         self.level_wise = bool(level_wise)
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.context_size = model.cfg.model.context_size
-        self.stats = None             # set to {} to collect wall seconds per stage (a device synchronisation per stamp)
         self._pin = torch.empty(256, dtype=torch.int16, pin_memory=True)
-
-    def _stamp(self, key, t0):
-        if self.stats is None:
-            return t0
-        import time
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        self.stats[key] = self.stats.get(key, 0.0) + (t - t0)
-        return t
 
     def decode(self, stream, n_nodes):
         """-> (occupancy codes uint8 [n_nodes] in BFS order, leaf integer coordinates int64 [U, 3])."""
@@ -312,7 +324,7 @@ class OctAttnLockstep:
         self.file[slot] = None
 
 
-class OctAttnBatchDecoder:
+class OctAttnBatchDecoder(_Stamps):
     """OctAttnFrameDecoder for several streams at once.  Slot s of an OctAttnBatchStepper holds the window of one stream; in one step
     every active slot decodes exactly one node: one `unknown` over the active slots, one CDF launch on [B, 255], ONE pinned
     device-to-host copy of the B CDF rows and one stream synchronisation, B range-decoder calls (each stream has its own decoder),
@@ -327,12 +339,9 @@ class OctAttnBatchDecoder:
         self.slots = int(streams)
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.context_size = model.cfg.model.context_size
-        self.stats = None             # set to {} to collect wall seconds per stage (a device synchronisation per stamp)
         self.steps = 0
         self._pin = torch.empty((self.slots, 256), dtype=torch.int16, pin_memory=True)
         self._pin_sym = torch.empty((self.slots,), dtype=torch.uint8, pin_memory=True)
-
-    _stamp = OctAttnFrameDecoder._stamp
 
     def decode(self, jobs):
         """jobs: dicts(name, stream bytes, n_nodes, depth, level_wise) -> [(codes uint8 [n_nodes] in BFS order, leaves int64 [U, 3])] in
@@ -518,52 +527,90 @@ def ehem_level_params(L, depth, last_coded, pos_mm, lidar_level, mullevel, polar
     return lv, (lidar_level if last else 255), 0.0, float(2 ** depth)
 
 
-class FrameDecoder:
-    def __init__(self, model, lidar_level=12, mullevel=False, polar=True, device=None, profile=None):
+def window_lengths(rows, cs):
+    """The windows of a level with `rows` coded nodes."""
+    return [min(cs, rows - i) for i in range(0, rows, cs)]
+
+
+def chunk_steps(steps, max_tokens=1_000_000, max_rows=None):
+    """Cut a round (steps[k] = the window lengths of step k) into the runs of WHOLE steps that one phase-1 forward takes:
+    [(first step, one past the last)].  A run holds at most `max_tokens` real tokens and `max_rows` rows of the padded layout
+    (encoder.MAX_PACKED_ROWS: the bounds of the encoder's own packed forwards, encoder.chunk_windows); a step is never split - one step of
+    64 slots x 8192 tokens fits both bounds, and a step that did not would go alone."""
+    if max_rows is None:
+        from .encoder import MAX_PACKED_ROWS as max_rows
+    out, i = [], 0
+    while i < len(steps):
+        j, tok, rows = i, 0, 0
+        while j < len(steps):
+            t = sum(steps[j])
+            r = sum(-(-(c + (c & 1)) // 512) * 512 for c in steps[j])
+            if j > i and (tok + t > max_tokens or rows + r > max_rows):
+                break
+            tok += t
+            rows += r
+            j += 1
+        out.append((i, j))
+        i = j
+    return out
+
+
+def _stage_rows(c, nst):
+    """Rows of a window of c nodes in every cross stage (models/packed.py: StageLayout - every stage pads a window to x512 rows)."""
+    rows, L = [], (c + (c & 1)) // 2
+    for _ in range(nst):
+        rows.append(-(-L // 512) * 512)
+        L = (L + 1) // 2
+    return rows
+
+
+class _EhemRounds(_Stamps):
+    """What both EHEM decoders do alike with the windows of a ROUND - one level of one stream (FrameDecoder) or the current level of every
+    stream in flight (EhemBatchDecoder), as `steps`: steps[k] = [(column, window length)], window k of every column that has one.  The
+    even-node logits of a window depend on ancestors only (ehem.py:92-115), so phase 1 runs ONCE over all windows of the round as a packed
+    forward (in runs of whole steps under the encoder's bounds, `chunk_steps`) - bit-identical to one-window launches (every kernel is
+    per-row / per-window deterministic: tests/test_gpu_e2e.py::test_full_frame_packed_forward_is_batch_invariant) and 10 - 50 x better at
+    filling the GPU - with one CDF launch, one pinned copy and ehem_phase2_prepare on the side stream while the copy travels.  Phase 2
+    needs the decoded even symbols and every bitstream interleaves its windows (evens, odds, evens, ...), so it runs step by step on the
+    step's slice of the run's phase-1 state, with the plan of the step's lengths (the slice IS that plan's layout: the windows of a step
+    are adjacent in every stage).  All state is per instance: several decoders may run on threads, each on its own stream."""
+
+    def __init__(self, model, device=None, profile=None, max_tokens=1_000_000, max_rows=None, coder_threads=1):
         self.model = model
         self.profile = profile        # native.NumericProfile: must be the one the stream was coded under (None: process default)
-        self.lidar_level = lidar_level
-        self.mullevel = mullevel
-        self.polar = polar            # spherical / cylindrical: positions normalised with the .dat (min, max) pairs
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.context_size = model.cfg.model.context_size
-        self.stats = None             # set to {} to collect wall seconds per stage (adds a device synchronisation per stamp: bench.py --decode)
-        self._plans = {}              # one-window plans by window length (index maps depend on the length only): built once, reused
+        self.max_tokens, self.max_rows = max_tokens, max_rows        # the bounds of one phase-1 forward (the encoder's; tests lower them)
+        self.steps = 0
+        self._plans = {}              # packed plans by their window lengths (`_plan`)
         self._pin = [None, None]      # pinned staging of the CDF rows (grown on demand)
-        self._pin_po = None           # pinned staging of a window's even symbols on their way up
+        self._pin_po = None           # pinned staging of a step's even symbols on their way up
         self._side = None             # side stream of ehem_phase2_prepare (created on first use, on the decoding thread's device)
+        self._pool = None             # range-decoder threads for the windows of a step (independent streams; ctypes releases the GIL)
+        if int(coder_threads) > 1:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(max_workers=min(int(coder_threads), 16))
         self.prepare_ahead = os.environ.get("SCP_DEC_PREP", "1") != "0"       # A/B switch: 0 = everything of phase 2 after the even symbols
 
-    def _stamp(self, key, t0):
-        if self.stats is None:
-            return t0
-        import time
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        self.stats[key] = self.stats.get(key, 0.0) + (t - t0)
-        return t
-
-    def _t0(self):
-        if self.stats is None:
-            return 0.0
-        import time
-        torch.cuda.synchronize()
-        return time.perf_counter()
-
-    def _plan1(self, c):
-        """The packed plan of ONE window of c nodes (cached: a frame has 55 windows of 8192 nodes and the plan is a function of c alone)."""
+    def _plan(self, lengths):
+        """The packed plan of a list of window lengths (index maps depend on the lengths only).  Kept are the lists that repeat: ONE window
+        of any length (every window's phase 2 in a one-stream level, and a frame decoded again has the same tail windows), small windows
+        only (the one-node and few-node levels every tree starts with) and full windows only (the inner steps of the large levels)."""
         from .models.packed import PackedPlan
-        p = self._plans.get(c)
+        key = tuple(lengths)
+        p = self._plans.get(key)
         if p is None:
-            if len(self._plans) > 64:
-                self._plans.clear()
-            p = self._plans[c] = PackedPlan([c], device=self.device)
+            p = PackedPlan(list(key), device=self.device)
+            if len(key) == 1 or max(key) <= 64 or min(key) == self.context_size:
+                if len(self._plans) >= 256:
+                    self._plans.clear()
+                self._plans[key] = p
         return p
 
     def _cdf_to_host(self, cdf_dev, then=None, slot=0):
         """int16 CDF rows -> numpy, through a pinned buffer with an asynchronous copy: `then()` (launches for the side stream) runs on the host while
-        the GPU finishes phase 1 and the copy; returns (rows, then's result).  The rows are a view of pinned buffer `slot` (0: a level's phase-1 rows,
-        1: a window's phase-2 rows): consumed before the slot's next use."""
+        the GPU finishes phase 1 and the copy; returns (rows, then's result).  The rows are a view of pinned buffer `slot` (0: a run's phase-1 rows,
+        1: a step's phase-2 rows): consumed before the slot's next use."""
         n = cdf_dev.numel()
         if self._pin[slot] is None or self._pin[slot].numel() < n:
             self._pin[slot] = torch.empty(max(n, 1 << 20), dtype=torch.int16, pin_memory=True)
@@ -591,106 +638,122 @@ class FrameDecoder:
             done.record(self._side)
         return prep, done
 
-    def _even_to_device(self, even, qp):
-        """The decoded even symbols of a window (int16 numpy [ne]) -> int64 device tensor [qp] in the cross layout (zeros behind the real rows):
-        one asynchronous copy out of a pinned buffer.  (The buffer's previous contents were consumed: a window's phase-2 rows are read back,
-        with a synchronisation, before the next window gets here.)"""
-        if self._pin_po is None or self._pin_po.numel() < qp:
-            self._pin_po = torch.empty(max(qp, 8192), dtype=torch.int64, pin_memory=True)
-        h = self._pin_po[:qp].numpy()
-        h[:even.shape[0]] = even
-        h[even.shape[0]:] = 0
-        po = torch.empty(qp, dtype=torch.int64, device=self.device)
-        po.copy_(self._pin_po[:qp], non_blocking=True)
+    def _run_coders(self, decs, grp, rows):
+        """One range-decoder call per window of a step: decs[col].run(rows_of_that_window) for (col, rows) in order -> the symbols."""
+        if self._pool is None or len(grp) < 2:
+            return [decs[col].run(r) for (col, _), r in zip(grp, rows)]
+        return list(self._pool.map(lambda a: decs[a[0][0]].run(a[1]), zip(grp, rows)))
+
+    def _evens_to_device(self, evens, qps):
+        """The even symbols of a step's windows -> int64 device tensor [sum qps] in the cross layout (each window's rows padded to its x512
+        rows with zeros behind the real ones): one asynchronous copy out of a pinned buffer, whose previous contents were consumed - a
+        step's phase-2 rows are read back, with a synchronisation, before the next step gets here."""
+        Q = sum(qps)
+        if self._pin_po is None or self._pin_po.numel() < Q:
+            self._pin_po = torch.empty(max(Q, 8192), dtype=torch.int64, pin_memory=True)
+        h = self._pin_po[:Q].numpy()
+        q0 = 0
+        for even, qp in zip(evens, qps):
+            h[q0:q0 + even.shape[0]] = even
+            h[q0 + even.shape[0]:q0 + qp] = 0
+            q0 += qp
+        po = torch.empty(Q, dtype=torch.int64, device=self.device)
+        po.copy_(self._pin_po[:Q], non_blocking=True)
         return po
 
-    def _decode_window(self, dec, ctx, pos, sym):
-        """ctx uint8 [c,12] (own occupancy = 255 placeholder), pos f32 [c,3]; the symbols go to sym[:c] (host int64).
-        Runs the SAME packed kernels as the encoder (a one-window plan): encoder and decoder must produce bit-identical
-        integer CDFs, and every kernel on the path is deterministic per row / per window, independent of the batch."""
-        from .models.packed import PackedPlan, ehem_phase1_packed, ehem_phase2_packed
-        c = ctx.shape[0]
+    def _step_rows(self, st, prep, run):
+        """The rows of every step of a run (its steps' [(column, window length)]) in the run's phase-1 state `st` and preparation `prep`
+        (or None) -> per step (state, preparation or None, cross-layout rows of every window).  Views only, cut while the CDF rows travel
+        and the host has nothing else to do; a step of one-node windows is stepped over like any other.  A one-step run IS its step."""
+        from .models.packed import phase2_prep_window
+        nst = len(self.model.swin_cross_transformer.layers)
+        out, bases = [], [0] * nst                                              # first row of the current step in every cross stage
+        for grp in run:
+            per = [_stage_rows(c, nst) for _, c in grp]
+            rows = [sum(r) for r in zip(*per)]
+            if len(run) == 1:
+                out.append((st, prep, [p[0] for p in per]))
+                continue
+            q0, q1 = bases[0], bases[0] + rows[0]
+            out.append((dict(a1=st["a1"][q0:q1], a2=st["a2"][q0:q1], pre_occ=st["pre_occ"][q0:q1]),
+                        None if prep is None else phase2_prep_window(prep, bases, rows), [p[0] for p in per]))
+            bases = [b + r for b, r in zip(bases, rows)]
+        return out
+
+    def _decode_round(self, decs, steps, ctx, posn, sym, first):
+        """The windows of a round.  decs[col]: the column's range decoder; steps: EhemLockstep.layout's; ctx uint8 [T, 12] (own occupancy =
+        255 placeholder) / posn f32 [T, 3]: the round's inputs in window order; the symbols of column col go to sym[first[col]:] (host
+        int64: they stay on the host until the round is complete, a step sends only its even symbols up).  Runs the SAME packed kernels as
+        the encoder: encoder and decoder must produce bit-identical integer CDFs.  A window of one node has no phase 2."""
+        from itertools import accumulate
+        from .models.packed import ehem_phase1_packed, ehem_phase2_packed
+        cs, model = self.context_size, self.model
+        t_row = 0
         t = self._t0()
-        plan = self._plan1(c)
-        prob1, st = ehem_phase1_packed(self.model, ctx, pos, plan)
-        t = self._stamp("phase1_model", t)
-        cdf_dev = native.softmax_cdf(prob1.contiguous(), want_lohi=False, want_cdf=True)["cdf"]
-        cdf, prep = self._cdf_to_host(cdf_dev, (lambda: self._prepare(st, plan)) if (c > 1 and self.prepare_ahead) else None)
-        t = self._stamp("cdf_d2h", t)
-        even = dec.run(cdf)
-        t = self._stamp("range_decoder", t)
-        sym[0:c:2] = even
-        if c > 1:
-            po = self._even_to_device(even, plan.d["a1map"].shape[0])   # one window: its real rows are the first rows of the cross layout
-            t = self._stamp("index_ops", t)
-            if prep is not None:
-                torch.cuda.current_stream(self.device).wait_event(prep[1])
-            prob2 = ehem_phase2_packed(self.model, st, plan, po, prep=None if prep is None else prep[0])
-            t = self._stamp("phase2_model", t)
-            cdf, _ = self._cdf_to_host(native.softmax_cdf(prob2.contiguous(), want_lohi=False, want_cdf=True)["cdf"], slot=1)
+        for k0, k1 in chunk_steps([[c for _, c in st] for st in steps], self.max_tokens, self.max_rows):
+            lengths = [c for st in steps[k0:k1] for _, c in st]
+            ntok = sum(lengths)
+            plan = self._plan(lengths)
+            prob1, st = ehem_phase1_packed(model, ctx[t_row:t_row + ntok], posn[t_row:t_row + ntok], plan)
+            t = self._stamp("phase1_model", t)
+            cdf1_dev = native.softmax_cdf(prob1.contiguous(), want_lohi=False, want_cdf=True)["cdf"]
+            # the run's query stream + pre_attn_mlp: one packed pass over all windows, launched while the CDF rows travel
+            ahead = self.prepare_ahead and max(lengths) > 1
+
+            def then():
+                prep, done = self._prepare(st, plan) if ahead else (None, None)
+                return done, self._step_rows(st, prep, steps[k0:k1])
+
+            cdf1, (done, views) = self._cdf_to_host(cdf1_dev, then)
             t = self._stamp("cdf_d2h", t)
-            sym[1:c:2] = dec.run(cdf)
-            t = self._stamp("range_decoder", t)
+            e0 = 0
+            for k, (stw, pwin, qps) in zip(range(k0, k1), views):
+                grp = steps[k]
+                ends = list(accumulate(((c + 1) // 2 for _, c in grp), initial=e0))
+                evens = self._run_coders(decs, grp, [cdf1[a:b] for a, b in zip(ends, ends[1:])])
+                e0 = ends[-1]
+                for (col, c), even in zip(grp, evens):
+                    r0 = first[col] + k * cs
+                    sym[r0:r0 + c:2] = even
+                t = self._stamp("range_decoder", t)
+                if max(c for _, c in grp) > 1:
+                    po = self._evens_to_device(evens, qps)
+                    t = self._stamp("index_ops", t)
+                    pw = plan if k1 - k0 == 1 else self._plan([c for _, c in grp])       # a one-step run: the step's plan is the run's
+                    if done is not None:
+                        torch.cuda.current_stream(self.device).wait_event(done)
+                        done = None
+                    prob2 = ehem_phase2_packed(model, stw, pw, po, prep=pwin)
+                    t = self._stamp("phase2_model", t)
+                    cdf2, _ = self._cdf_to_host(native.softmax_cdf(prob2.contiguous(), want_lohi=False, want_cdf=True)["cdf"], slot=1)
+                    t = self._stamp("cdf_d2h", t)
+                    odd = [(col, c) for col, c in grp if c > 1]
+                    ends = list(accumulate((c // 2 for _, c in odd), initial=0))
+                    for (col, c), o in zip(odd, self._run_coders(decs, odd, [cdf2[a:b] for a, b in zip(ends, ends[1:])])):
+                        r0 = first[col] + k * cs
+                        sym[r0 + 1:r0 + c:2] = o
+                    t = self._stamp("range_decoder", t)
+                self.steps += 1
+            t_row += ntok
+
+
+class FrameDecoder(_EhemRounds):
+    """One stream: the tree driver (`_decode_tree`, native.decode_expand) over the round engine, a level = a round of one column.  A
+    phase-1 forward takes the engine's default bounds (1 000 000 tokens, encoder.MAX_PACKED_ROWS padded rows); a level holds at most as
+    many nodes as the frame has points (about 120 000), so no level of a supported frame reaches them and every level is one run."""
+
+    def __init__(self, model, lidar_level=12, mullevel=False, polar=True, device=None, profile=None):
+        super().__init__(model, device=device, profile=profile)
+        self.lidar_level = lidar_level
+        self.mullevel = mullevel
+        self.polar = polar            # spherical / cylindrical: positions normalised with the .dat (min, max) pairs
 
     def _decode_level(self, dec, ctx, pos, n_total):
         """All windows of one level -> int64 device tensor [n_total]: the symbols of the ctx.shape[0] coded nodes, -1 behind them (the dropped last
-        node of a multi-level shell).  The even-node logits of a window depend on ancestors only (ehem.py:92-115), so phase 1 runs
-        ONCE for the whole level as a packed forward - bit-identical to one-window launches (every kernel is per-row / per-window
-        deterministic: tests/test_gpu_e2e.py::test_full_frame_packed_forward_is_batch_invariant) and 10 - 50 x better at filling the
-        GPU; phase 2 needs the window's decoded even symbols and the bitstream interleaves the windows (evens, odds, evens, ...),
-        so it runs window by window on that window's slice of the phase-1 state (a one-window plan has exactly that layout).
-        The decoded symbols stay on the host until the level is complete (one copy); a window sends only its even symbols up."""
-        from .models.packed import PackedPlan, ehem_phase1_packed, ehem_phase2_packed, phase2_prep_window
-        cs = self.context_size
-        n = ctx.shape[0]
+        node of a multi-level shell).  ctx uint8 [n, 12], pos f32 [n, 3]."""
         sym = np.full(n_total, -1, np.int64)
-        lengths = [min(cs, n - i) for i in range(0, n, cs)]
-        if len(lengths) == 1:
-            self._decode_window(dec, ctx, pos, sym)
-            return torch.from_numpy(sym).to(self.device)
-        t = self._t0()
-        plan = PackedPlan(lengths, device=self.device)
-        prob1, st = ehem_phase1_packed(self.model, ctx, pos, plan)
-        t = self._stamp("phase1_model", t)
-        cdf1_dev = native.softmax_cdf(prob1.contiguous(), want_lohi=False, want_cdf=True)["cdf"]
-        # the level's query stream + pre_attn_mlp: one packed pass over all windows, launched while the CDF rows travel
-        cdf1, prep = self._cdf_to_host(cdf1_dev, (lambda: self._prepare(st, plan)) if self.prepare_ahead else None)
-        t = self._stamp("cdf_d2h", t)
-        row0 = e0 = q0 = 0
-        nst = len(self.model.swin_cross_transformer.layers)
-        bases = [0] * nst                                                       # first row of the current window in every cross stage
-        for c in lengths:
-            ne = (c + 1) // 2
-            qp = -(-((c + (c & 1)) // 2) // 512) * 512                     # cross-layout rows of this window (padded to 512)
-            rows, L = [], (c + (c & 1)) // 2                                    # (models/packed.py: StageLayout - every stage pads a window to x512 rows)
-            for _ in range(nst):
-                rows.append(-(-L // 512) * 512)
-                L = (L + 1) // 2
-            even = dec.run(cdf1[e0:e0 + ne])
-            t = self._stamp("range_decoder", t)
-            sym[row0:row0 + c:2] = even
-            if c > 1:
-                pw = self._plan1(c)
-                stw = dict(a1=st["a1"][q0:q0 + qp], a2=st["a2"][q0:q0 + qp],
-                           pre_occ=st["pre_occ"][q0:q0 + qp])
-                po = self._even_to_device(even, qp)
-                t = self._stamp("index_ops", t)
-                pwin = None
-                if prep is not None:
-                    if prep[1] is not None:
-                        torch.cuda.current_stream(self.device).wait_event(prep[1])
-                        prep = (prep[0], None)
-                    pwin = phase2_prep_window(prep[0], bases, rows)
-                prob2 = ehem_phase2_packed(self.model, stw, pw, po, prep=pwin)
-                t = self._stamp("phase2_model", t)
-                cdf, _ = self._cdf_to_host(native.softmax_cdf(prob2.contiguous(), want_lohi=False, want_cdf=True)["cdf"], slot=1)
-                t = self._stamp("cdf_d2h", t)
-                sym[row0 + 1:row0 + c:2] = dec.run(cdf)
-                t = self._stamp("range_decoder", t)
-            row0 += c
-            e0 += ne
-            q0 += qp
-            bases = [b + r for b, r in zip(bases, rows)]
+        steps = [[(0, c)] for c in window_lengths(ctx.shape[0], self.context_size)]
+        self._decode_round([dec], steps, ctx, pos, sym, [0])
         return torch.from_numpy(sym).to(self.device)
 
     def _decode_tree(self, dec, depth, pos_mm):
@@ -745,34 +808,6 @@ class FrameDecoder:
 
 
 # ------------------------------------------------------------------------------------------------ several EHEM streams in lockstep
-def window_lengths(rows, cs):
-    """The windows of a level with `rows` coded nodes (FrameDecoder._decode_level)."""
-    return [min(cs, rows - i) for i in range(0, rows, cs)]
-
-
-def chunk_steps(steps, max_tokens=1_000_000, max_rows=None):
-    """Cut a round (steps[k] = the window lengths of step k) into the runs of WHOLE steps that one phase-1 forward takes:
-    [(first step, one past the last)].  A run holds at most `max_tokens` real tokens and `max_rows` rows of the padded layout
-    (encoder.MAX_PACKED_ROWS: the bounds of the encoder's own packed forwards, encoder.chunk_windows); a step is never split - one step of
-    64 slots x 8192 tokens fits both bounds, and a step that did not would go alone."""
-    if max_rows is None:
-        from .encoder import MAX_PACKED_ROWS as max_rows
-    out, i = [], 0
-    while i < len(steps):
-        j, tok, rows = i, 0, 0
-        while j < len(steps):
-            t = sum(steps[j])
-            r = sum(-(-(c + (c & 1)) // 512) * 512 for c in steps[j])
-            if j > i and (tok + t > max_tokens or rows + r > max_rows):
-                break
-            tok += t
-            rows += r
-            j += 1
-        out.append((i, j))
-        i = j
-    return out
-
-
 class EhemLockstep:
     """The host bookkeeping of the lockstep EHEM decoder, free of any device state (tests drive it with made-up level sizes).  `slots`
     slots each hold one file's position: tree (of the file's 1 or 3), level L of the tree's depth, node count n of the level.  A ROUND
@@ -857,149 +892,23 @@ class EhemLockstep:
 CODER_THREADS = int(os.environ.get("SCP_DEC_CODER_THREADS", "1"))
 
 
-def _stage_rows(c, nst):
-    """Rows of a window of c nodes in every cross stage (models/packed.py: StageLayout - every stage pads a window to x512 rows)."""
-    rows, L = [], (c + (c & 1)) // 2
-    for _ in range(nst):
-        rows.append(-(-L // 512) * 512)
-        L = (L + 1) // 2
-    return rows
-
-
-class EhemBatchDecoder:
-    """FrameDecoder for several streams at once (scheduling: EhemLockstep).  A round = the current level of every stream in flight: ONE
-    packed phase-1 forward over all their windows (in runs of whole steps under the encoder's bounds, `chunk_steps`), one CDF launch,
-    one pinned copy, ehem_phase2_prepare for the round on the side stream; then per step every stream's own range decoder takes its
-    window's even symbols, the even symbols of the step go up in one copy, ONE phase 2 runs on the step's slice of the round's phase-1
-    state with the plan of the step's lengths (the slice IS that plan's layout: the step's windows are adjacent in every stage), one CDF
-    launch and copy, and every stream decodes its odd symbols.  The decoded levels of all streams are expanded by one launch
+class EhemBatchDecoder(_EhemRounds):
+    """FrameDecoder for several streams at once: the lockstep driver (scheduling: EhemLockstep) over the round engine.  A round = the
+    current level of every stream in flight, a column each; per step every stream's own range decoder takes its window's even symbols,
+    ONE phase 2 serves the step, and every stream decodes its odd symbols.  The decoded levels of all streams are expanded by one launch
     (native.decode_expand_batch) that writes the next round's model inputs in round order.  The packed forward is batch-invariant bit
     for bit, so every stream's CDF rows, symbols, codes and leaves are FrameDecoder's; per stream the bitstream order (window: evens,
     odds) is untouched.  max_tokens / max_rows: the bounds of one phase-1 forward (the encoder's; tests lower them).  coder_threads > 1:
-    the range-decoder calls of a step (independent streams; ctypes releases the GIL) run on a pool of that many threads, 16 at most."""
+    the range-decoder calls of a step run on a pool of that many threads, 16 at most.  `stats` also gets the counters `rounds`, `steps`."""
 
     def __init__(self, model, streams, device=None, profile=None, max_tokens=1_000_000, max_rows=None, coder_threads=CODER_THREADS):
-        self.model = model
-        self.profile = profile
         self.slots = int(streams)
         if not 1 <= self.slots <= 64:
             raise native.ScpError("EhemBatchDecoder: 1 .. 64 streams expected")
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        self.context_size = model.cfg.model.context_size
-        self.max_tokens, self.max_rows = max_tokens, max_rows
-        self.stats = None             # set to {} to collect wall seconds per stage (a device synchronisation per stamp) + the two counters
-        self.rounds = self.steps = 0
-        self._plans = {}
-        self._pin = [None, None]
-        self._pin_po = None
-        self._pin_sym = None
-        self._side = None
-        self._pool = None
-        if min(int(coder_threads), self.slots) > 1:
-            from concurrent.futures import ThreadPoolExecutor
-            self._pool = ThreadPoolExecutor(max_workers=min(int(coder_threads), self.slots, 16))
-        self.prepare_ahead = os.environ.get("SCP_DEC_PREP", "1") != "0"
-
-    _stamp = FrameDecoder._stamp
-    _t0 = FrameDecoder._t0
-    _cdf_to_host = FrameDecoder._cdf_to_host
-    _prepare = FrameDecoder._prepare
-
-    def _plan(self, lengths):
-        """The packed plan of a list of window lengths.  Kept are the lists that repeat: those of small windows only (the one-node and
-        few-node levels every tree starts with) and those of full windows only (the inner steps of the large levels)."""
-        from .models.packed import PackedPlan
-        key = tuple(lengths)
-        p = self._plans.get(key)
-        if p is None:
-            p = PackedPlan(list(key), device=self.device)
-            if max(key) <= 64 or min(key) == self.context_size:
-                if len(self._plans) >= 256:
-                    self._plans.clear()
-                self._plans[key] = p
-        return p
-
-    def _run_coders(self, decs, grp, rows):
-        """One range-decoder call per window of a step: decs[col].run(rows_of_that_window) for (col, rows) in order -> the symbols."""
-        if self._pool is None or len(grp) < 2:
-            return [decs[col].run(r) for (col, _), r in zip(grp, rows)]
-        return list(self._pool.map(lambda a: decs[a[0][0]].run(a[1]), zip(grp, rows)))
-
-    def _evens_to_device(self, evens, qps):
-        """The even symbols of a step's windows -> int64 device tensor [sum qps] in the cross layout (each window's rows padded to its x512
-        rows with zeros behind the real ones): one asynchronous copy out of a pinned buffer, whose previous contents were consumed - a
-        step's phase-2 rows are read back, with a synchronisation, before the next step gets here."""
-        Q = sum(qps)
-        if self._pin_po is None or self._pin_po.numel() < Q:
-            self._pin_po = torch.empty(max(Q, 8192), dtype=torch.int64, pin_memory=True)
-        h = self._pin_po[:Q].numpy()
-        q0 = 0
-        for even, qp in zip(evens, qps):
-            h[q0:q0 + even.shape[0]] = even
-            h[q0 + even.shape[0]:q0 + qp] = 0
-            q0 += qp
-        po = torch.empty(Q, dtype=torch.int64, device=self.device)
-        po.copy_(self._pin_po[:Q], non_blocking=True)
-        return po
-
-    def _decode_round(self, decs, steps, ctx, posn, sym, first):
-        """The windows of a round.  decs[col]: the column's range decoder; steps: EhemLockstep.layout's; ctx / posn: the round's inputs in
-        window order; the symbols of column col go to sym[first[col]:] (host int64)."""
-        from .models.packed import ehem_phase1_packed, ehem_phase2_packed, phase2_prep_window
-        cs, model = self.context_size, self.model
-        nst = len(model.swin_cross_transformer.layers)
-        t_row = 0
-        t = self._t0()
-        for k0, k1 in chunk_steps([[c for _, c in st] for st in steps], self.max_tokens, self.max_rows):
-            lengths = [c for st in steps[k0:k1] for _, c in st]
-            ntok = sum(lengths)
-            plan = self._plan(lengths)
-            prob1, st = ehem_phase1_packed(model, ctx[t_row:t_row + ntok], posn[t_row:t_row + ntok], plan)
-            t = self._stamp("phase1_model", t)
-            cdf1_dev = native.softmax_cdf(prob1.contiguous(), want_lohi=False, want_cdf=True)["cdf"]
-            ahead = self.prepare_ahead and max(lengths) > 1
-            cdf1, prep = self._cdf_to_host(cdf1_dev, (lambda: self._prepare(st, plan)) if ahead else None)
-            t = self._stamp("cdf_d2h", t)
-            e0 = q0 = 0
-            bases = [0] * nst
-            for k in range(k0, k1):
-                grp = steps[k]
-                nes = [(c + 1) // 2 for _, c in grp]
-                offs = np.cumsum([e0] + nes)
-                evens = self._run_coders(decs, grp, [cdf1[offs[i]:offs[i + 1]] for i in range(len(grp))])
-                e0 = int(offs[-1])
-                for (col, c), even in zip(grp, evens):
-                    r0 = first[col] + k * cs
-                    sym[r0:r0 + c:2] = even
-                t = self._stamp("range_decoder", t)
-                per = [_stage_rows(c, nst) for _, c in grp]
-                rows = [sum(p[s] for p in per) for s in range(nst)]
-                if max(c for _, c in grp) > 1:
-                    po = self._evens_to_device(evens, [p[0] for p in per])
-                    t = self._stamp("index_ops", t)
-                    pw = plan if k1 - k0 == 1 else self._plan([c for _, c in grp])       # a one-step run: the step's plan is the run's
-                    Q = rows[0]
-                    stw = dict(a1=st["a1"][q0:q0 + Q], a2=st["a2"][q0:q0 + Q], pre_occ=st["pre_occ"][q0:q0 + Q])
-                    pwin = None
-                    if prep is not None:
-                        if prep[1] is not None:
-                            torch.cuda.current_stream(self.device).wait_event(prep[1])
-                            prep = (prep[0], None)
-                        pwin = phase2_prep_window(prep[0], bases, rows)
-                    prob2 = ehem_phase2_packed(model, stw, pw, po, prep=pwin)
-                    t = self._stamp("phase2_model", t)
-                    cdf2, _ = self._cdf_to_host(native.softmax_cdf(prob2.contiguous(), want_lohi=False, want_cdf=True)["cdf"], slot=1)
-                    t = self._stamp("cdf_d2h", t)
-                    odd = [(col, c) for col, c in grp if c > 1]
-                    offs = np.cumsum([0] + [c // 2 for _, c in odd])
-                    for (col, c), o in zip(odd, self._run_coders(decs, odd, [cdf2[offs[i]:offs[i + 1]] for i in range(len(odd))])):
-                        r0 = first[col] + k * cs
-                        sym[r0 + 1:r0 + c:2] = o
-                    t = self._stamp("range_decoder", t)
-                q0 += rows[0]
-                bases = [b + r for b, r in zip(bases, rows)]
-                self.steps += 1
-            t_row += ntok
+        super().__init__(model, device=device, profile=profile, max_tokens=max_tokens, max_rows=max_rows,
+                         coder_threads=min(int(coder_threads), self.slots))
+        self.rounds = 0
+        self._pin_sym = None          # pinned staging of a round's symbols on their way up (`_upload_symbols`)
 
     # ---- per-file facts
     def _params(self, f, tree, L):

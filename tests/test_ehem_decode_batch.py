@@ -18,7 +18,7 @@ _FILES = [
 
 
 def _one_stream(trees, drop, cs):
-    """The (tree, level, window, length) sequence of FrameDecoder._decode_tree / _decode_level for one file."""
+    """The (tree, level, window, length) sequence of FrameDecoder._decode_tree (levels) and decoder.window_lengths (windows) for one file."""
     out = []
     for t, sizes in enumerate(trees):
         depth = len(sizes)

@@ -331,6 +331,50 @@ def test_rounds_cut_into_several_phase1_runs_and_coder_threads(model1k, dev, tmp
     assert frames[0][1]["level_sizes"][-1] + frames[1][1]["level_sizes"][-1] > 2 * 3000
 
 
+_STAGES = ("tree_expansion", "phase1_model", "cdf_d2h", "range_decoder", "index_ops", "phase2_model")
+
+
+@pytest.mark.parametrize("points,tail", [(4097, (1025, 2049)), (4101, (1026, 2051)), (2, (1,))])
+def test_one_stream_tail_windows_of_one_two_and_three_nodes(model1k, dev, points, tail):
+    """Integer clouds on a line, context_size 1024: the last two levels end in a tail window of one node (1024 + 1, 2 x 1024 + 1: no phase
+    2 for it, yet its rows in the level's phase-1 state, the preparation and the CDF rows are stepped over) or of two and three nodes;
+    two points are one level of one node (no phase 2 at all).  FrameDecoder as constructed, without the preparation ahead and with stage
+    stamps, and EhemBatchDecoder on one slot, all decode to the encoder's occupancies and leaves."""
+    from scp_amd.decoder import EhemBatchDecoder, FrameDecoder
+    from scp_amd.encoder import FrameEncoder
+    q = np.zeros((points, 3), np.int32)
+    q[:, 0] = np.arange(points)
+    enc = FrameEncoder(model1k, "kitti", 12, spher=False, cylin=False, mullevel=False, device=dev)
+    res = enc.encode_ints([q], 0, 0.0, points)
+    assert tuple(res["level_sizes"][-len(tail):]) == tail, res["level_sizes"]
+    occ = enc.geom.nodes(("occ",))["occ"].long()
+    leaves = enc.geom.leaves(0).long()
+    assert occ.shape[0] == res["n_nodes"] == sum(res["level_sizes"])
+
+    def check(shells, what):
+        assert len(shells) == 1, what
+        codes, lv = shells[0]
+        assert torch.equal(torch.cat(codes).long(), occ), what
+        assert torch.equal(lv.long(), leaves), what
+
+    def one_stream(**attrs):
+        d = FrameDecoder(model1k, 12, mullevel=False, polar=False, device=dev)
+        for k, v in attrs.items():
+            setattr(d, k, v)
+        check(d.decode(res["bytes"], res["n_levels"], res["pos_mm"]), attrs)
+        return d
+
+    one_stream()
+    one_stream(prepare_ahead=False)
+    stats = one_stream(stats={}).stats
+    if points == 2:                                           # one node: nothing goes up, no phase 2
+        assert all(k in stats for k in _STAGES[:4]) and stats.get("phase2_model", 0) == 0, stats
+    else:
+        assert all(k in stats for k in _STAGES) and stats["phase2_model"] > 0, stats
+    job = dict(name="line", stream=res["bytes"], n_levels=res["n_levels"], pos_mm=res["pos_mm"], polar=False, mullevel=False, lidar_level=12)
+    check(EhemBatchDecoder(model1k, 1, device=dev).decode([job])[0], "lockstep, one slot")
+
+
 def test_a_stream_of_another_profile_is_refused_before_anything_is_decoded(model1k, dev, tmp_path):
     from scp_amd import native
     from scp_amd.decoder import SIDECAR, EhemBatchDecoder, decode_files

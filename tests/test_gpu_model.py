@@ -1858,7 +1858,7 @@ def test_phase2_prepared_ahead_has_the_bits_of_the_plain_phase2(dev, ehem):
     prep = ehem_phase2_prepare(ehem, st, plan)
     got = ehem_phase2_packed(ehem, st, plan, prep=prep)
     assert torch.equal(got, want)
-    # one window at a time on its rows of the level-wide state and of the level-wide preparation (what FrameDecoder._decode_level does);
+    # one window at a time on its rows of the level-wide state and of the level-wide preparation (what the decoders' round engine, decoder._EhemRounds._decode_round, does);
     # a preparation is consumed by the phase 2 that takes it (the blocks run in place on `pre`): a fresh one
     prep = ehem_phase2_prepare(ehem, st, plan)
     nst = len(ehem.swin_cross_transformer.layers)
