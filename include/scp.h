@@ -544,6 +544,60 @@ SCP_API int scp_nn_error_split_f64(const double *a, int64_t na, const double *b,
 SCP_API int scp_dist_segments_f64(const double *d2, const double *comp, const uint8_t *flag, const int64_t *order /* NULL ok */, int64_t n,
                                   const int64_t *seg_off, int32_t n_bins, scp_dist_seg *out, void *stream);
 
+/* Rate per range ring (csrc/ringrate.hip; additive, no new ABI version; host side: scp_amd/metrics.py ring_rate_dict, FrameEncoder.ring_rate):
+ * every leaf's share of its ancestors' bits, summed over the bins of the distortion report - so that "what does the 40 - 60 m ring cost,
+ * and what error does it buy" has an answer.  Definition, for one tree (one segment of a scp_geom build; nodes in BFS order, depth D):
+ *   leaves(i) = popcount(occ_i) for a node of level D, the sum over the node's children otherwise (the level-D total is n_leaves);
+ *   bits(i)   = what the caller says node i cost, two columns (ideal, table) - the encoder: row_ideal / row_table of the node's coded row
+ *               (scp_rate_segments), 0 for the node a drop_last segment leaves uncoded;
+ *   share(i)  = bits(i) / (double)leaves(i), one IEEE float64 division;
+ *   cost(p)   = ((share(a_1) + share(a_2)) + ..) + share(a_D), a_l = the ancestor of leaf p at level l: root first, float64, no fused
+ *               operation - a numpy loop reproduces it bit for bit;
+ *   leaf p    = in the order of scp_geom_emit_leaves: level-D node j owns the popcount(occ_j) consecutive leaves that start at the
+ *               exclusive prefix sum of the popcounts of the level-D nodes before it.
+ * The sum of cost over the leaves equals the sum of bits over the nodes up to rounding (every node's bits are handed out in leaves(i)
+ * equal parts).
+ *
+ * scp_rate_leaf_share: occ / level uint8, parent int32 (index into the concatenated table, -1 for a root), bits_ideal / bits_table
+ * float64, all DEVICE [total_nodes] - the columns of scp_geom_emit_nodes for all segments of a build; segs = nseg HOST rows of four
+ * int64 (node_base, n_nodes, depth, leaf_base) that tile the node table and the leaf table in this order (segment s owns the leaves
+ * leaf_base[s] .. leaf_base[s + 1] - 1, the last one up to total_leaves - 1; at least one node and one leaf each).  Outputs (DEVICE):
+ * leaves int64 [total_nodes]; cost_ideal, cost_table float64 [total_leaves], segment-major, Morton order inside a segment.  workspace:
+ * device memory, 8-byte aligned, scp_rate_leaf_share_workspace_bytes(total_nodes, nseg) bytes.
+ * Every argument is checked on the host before any launch: a NULL pointer, total_nodes / total_leaves outside 1 .. 2^30, nseg outside
+ * 1 .. SCP_MAX_SEGMENTS, a depth outside 1 .. SCP_MAX_DEPTH, a segment table that does not tile both tables, a workspace too small or
+ * misaligned: SCP_EINVAL.  The node table itself is then checked by a validation launch before any index in it is followed: per
+ * segment the first node is the only node of level 1 and has parent -1; levels lie in 1 .. depth and never fall along the table; a
+ * parent lies inside the segment, in front of its child, one level up; parents never fall along a level; no occ is 0; the level-D
+ * popcounts add up to the segment's leaf count.  A table that breaks a rule returns SCP_EINVAL (one small read-back: the call
+ * synchronises `stream` once); nothing is written through an index taken from it.
+ * Order: leaves by integer atomics, one launch per level bottom-up; cost one launch per level top-down, a node adding its share to its
+ * parent's finished sum.  All segments share the launches, whose number (2 * deepest tree + 1) depends on the depths alone.
+ *
+ * scp_ring_bins_f64: the bin of scp_nn_error_split_f64's bin_out for a cloud of its own - xyz float64 DEVICE [n][3], view / edges_sq /
+ * n_rings / group / n_groups exactly as there, the same expressions on the same operands (rho2 = (x*x + y*y) + z*z of xyz - view; ring =
+ * the largest r with rho2 >= edges_sq[r]; bin = group * n_rings + ring): integer for integer the same bins.  flag_out uint8 [n]
+ * (optional, NULL): SCP_DIST_FLAG_GROUP_CLAMPED where a group outside [0, n_groups) was clamped.  Argument checks as there.
+ *
+ * scp_share_segments_f64: one scp_share_seg per bin; rows, order, seg_off, clamping and the SUMMATION CONTRACT exactly as
+ * scp_dist_segments_f64 (thread t adds rows t, t + 1024, .. of the bin in that order, a fixed binary tree over the 1024 partial sums; no
+ * floating-point atomics; a bin's record depends on that bin's rows in index order and on nothing else).
+ *   leaves = rows of the bin; ideal_bits = sum cost_ideal; table_bits = sum cost_table; max_ideal_bits = max cost_ideal (0: empty bin)
+ * n outside 1 .. 2^30, n_bins outside 1 .. SCP_DIST_MAX_BINS or a NULL pointer (order excepted): SCP_EINVAL, nothing launched. */
+#define SCP_SHARE_MAX_NODES (1ll << 30)
+typedef struct scp_share_seg {
+    int64_t leaves;
+    double ideal_bits, table_bits, max_ideal_bits;
+} scp_share_seg;
+SCP_API int64_t scp_rate_leaf_share_workspace_bytes(int64_t total_nodes, int32_t nseg);   /* bytes, or SCP_EINVAL */
+SCP_API int scp_rate_leaf_share(const uint8_t *occ, const uint8_t *level, const int32_t *parent, int64_t total_nodes, const double *bits_ideal,
+                                const double *bits_table, const int64_t *segs /* HOST [nseg][4] */, int32_t nseg, int64_t total_leaves,
+                                int64_t *leaves, double *cost_ideal, double *cost_table, void *workspace, int64_t workspace_bytes, void *stream);
+SCP_API int scp_ring_bins_f64(const double *xyz, int64_t n, const double *view, const double *edges_sq, int32_t n_rings,
+                              const int32_t *group /* NULL ok */, int32_t n_groups, int32_t *bin_out, uint8_t *flag_out /* NULL ok */, void *stream);
+SCP_API int scp_share_segments_f64(const double *cost_ideal, const double *cost_table, const int64_t *order /* NULL ok */, int64_t n,
+                                   const int64_t *seg_off, int32_t n_bins, scp_share_seg *out, void *stream);
+
 /* Input stage of the packed EHEM forward: embeddings of dgcnn.py:121-128 fused with the packed layout's input gather.
  * ctx u8 [T][12] = 4 x (level, octant, occ) (scp_geom_context_ehem), pos f32 [T][3], inmap i64 [rows] (== n_tokens: pad token);
  * tables occ_enc [256][16], level_enc [*][4], octant_enc [*][4]; out x f32 [rows][80], pos_out f32 [rows][3], occ_self i64 [rows]. */

@@ -16,6 +16,10 @@ same stdout block per frame, same summary file.  Differences, all additive:
     0, by default 0,5,10,15,20,30,40,60,80 m for KITTI and the same in millimetres for Ford) and per rho shell, split along the sensor's
     r / phi / theta axes, computed on the device (csrc/distreport.hip): one more line per frame and a `<stream>.dist.json` next to every
     stream.  The streams themselves do not change.
+  * `--rate_rings [EDGES]` (EHEM): what every range ring costs - each node's ideal and coded-table bits handed to the points below it in
+    equal parts and summed per ring (same EDGES and defaults as `--distortion_report`) and rho shell, computed on the device
+    (csrc/ringrate.hip): one more line per frame (ideal bits per leaf of every ring) and a `<stream>.rings.json` next to every stream
+    (tools/rd_rings.py joins it with the `.dist.json`).  Implies the rate kernels; the streams themselves do not change.
   * `--normals estimate|DIR` (with `--metrics`, EHEM): the D2 (point-to-plane) PSNR as well, on normals estimated on the device or
     read from the `<DIR>/<sequence>/<frame>.ply` files `gene_normals.py` writes; one more line per frame, `PSNR_D2:` in the summary.
 """
@@ -63,18 +67,29 @@ def load_cfg(ckpt_path, model_name=None):
     return Cfg(model=model, data=dict(extra_pos=False), train=dict(type="kitti", dropout=0.0))
 
 
-def parse_edges(text):
+def parse_edges(text, flag="--distortion_report"):
     """`--distortion_report 0,5,10`: the ring edges as a tuple of floats (native.dist_edges states what a valid list is)."""
     try:
         vals = [float(v) for v in text.split(",")]
     except ValueError:
-        raise native.ScpError(f"--distortion_report: ring edges are comma-separated numbers starting at 0, got {text!r}")
+        raise native.ScpError(f"{flag}: ring edges are comma-separated numbers starting at 0, got {text!r}")
     return native.dist_edges(vals)
+
+
+def parse_ring_edges(text):
+    """`--rate_rings 0,5,10`: the same syntax as --distortion_report's."""
+    return parse_edges(text, "--rate_rings")
 
 
 def distortion_request(args):
     """(wanted, edges) of --distortion_report: (False, None) without the flag, (True, None) for the data type's default edges."""
     v = getattr(args, "distortion_report", None)
+    return (v is not None and v is not False), (None if v is None or isinstance(v, bool) else tuple(v))
+
+
+def rings_request(args):
+    """(wanted, edges) of --rate_rings, read like distortion_request."""
+    v = getattr(args, "rate_rings", None)
     return (v is not None and v is not False), (None if v is None or isinstance(v, bool) else tuple(v))
 
 
@@ -113,6 +128,11 @@ def get_args(argv=None, mullevel=False):
                         "<stream>.dist.json next to the stream (the line: MSE and shares of the direction with the larger MSE, as D1's mseF takes it, "
                         "and the largest error of both directions); EDGES = comma-separated ring edges from 0 (default: 0,5,10,15,20,30,40,60,80 m "
                         "for kitti, x 1000 for ford); the streams do not change")
+    # (absent from the namespace unless given: read it with rings_request(args))
+    p.add_argument("--rate_rings", nargs="?", const=True, type=parse_ring_edges, default=argparse.SUPPRESS, metavar="EDGES",
+                   help="per frame (EHEM): ideal bits per leaf of every range ring on one more line, and <stream>.rings.json next to the stream "
+                        "with ideal / coded-table bits and leaves per ring and rho shell (every node's bits shared equally among the points "
+                        "below it); EDGES as for --distortion_report, with the same defaults; implies the rate kernels; the streams do not change")
     p.add_argument("--host_transform", action="store_true",
                    help="strict identity with the reference from the frame on: the coordinate transform + quantiser run in numpy float32 on the "
                         "host exactly as data_preprocess.py:42-70 does (the device transform is more accurate, hence not bit-identical); "
@@ -171,6 +191,18 @@ def refuse_unsupported(args, name, mullevel):
         if args.preproc_path:
             raise native.ScpError("--distortion_report with --preproc_path: no geometry of the frame is built there, only its records are coded")
         if dist_edges is None:
+            from . import metrics
+            metrics.default_edges(args.type)
+    want_rings, ring_edges = rings_request(args)
+    if want_rings:
+        if name == "OctAttention":
+            raise native.ScpError("--rate_rings is available for the EHEM encoders only (like --distortion_report: the OctAttention encoders "
+                                  "keep no reconstructed cloud)")
+        if args.type == "obj":
+            raise native.ScpError("--rate_rings bins the points by their range from a LiDAR sensor at the origin: --type obj has none")
+        if args.preproc_path:
+            raise native.ScpError("--rate_rings with --preproc_path: no geometry of the frame is built there, only its records are coded")
+        if ring_edges is None:
             from . import metrics
             metrics.default_edges(args.type)
     if args.type == "obj" and (args.spher or args.cylin or mullevel and name != "OctAttention"):
@@ -297,6 +329,7 @@ def main(argv=None, mullevel=False):
     refuse_unsupported(args, name, mullevel)
     rate_report = getattr(args, "rate_report", False)
     want_dist, dist_edges = distortion_request(args)
+    want_rings, ring_edges = rings_request(args)
     cls = OctAttention if name == "OctAttention" else EHEM
     if args.random_weights is not None or not args.ckpt_path:
         from .weights import fill_weights
@@ -322,13 +355,14 @@ def main(argv=None, mullevel=False):
                                   host_transform=True if args.host_transform else None, decodable=args.decodable, rate=rate_report)
     else:
         enc = FrameEncoder(model, args.type, args.lidar_level, spher=args.spher, cylin=args.cylin, mullevel=mullevel, device=dev,
-                           host_transform=True if args.host_transform else None, rate=rate_report)
+                           host_transform=True if args.host_transform else None, rate=rate_report or want_rings, rate_rows=want_rings)
 
     mine = D.shard(files, rank, world)
     # fast path: frames are enqueued with encode_async (stage G on a side stream, two model lanes, range coder on a worker thread)
-    # and finished three frames later - what bench.py measures.  Flows that need the frame's octree after the encode (--metrics, --distortion_report),
+    # and finished three frames later - what bench.py measures.  Flows that need the frame's octree after the encode (--metrics, --distortion_report,
+    # --rate_rings),
     # come from record files, or run the one-window-per-node mode stay on the synchronous call.
-    pipelined = not (args.preproc_path or args.metrics or want_dist or args.sequential or obj)
+    pipelined = not (args.preproc_path or args.metrics or want_dist or want_rings or args.sequential or obj)
     DEPTH = 3
     host_ints = enc.host_ints if (pipelined and name != "OctAttention" and enc.host_transform) else None
     reader = Prefetch(mine, post=host_ints)
@@ -341,7 +375,7 @@ def main(argv=None, mullevel=False):
         return (cur.split("/")[-2] + Path(cur).stem) if (args.type == "kitti" and name != "OctAttention" and "/" in cur.rstrip("/")
                                                           and len(cur.split("/")) >= 2) else Path(cur).stem
 
-    def report(cur, res, t_submit, dist=None, drep=None):
+    def report(cur, res, t_submit, dist=None, drep=None, rrep=None):
         now = time.time()
         elapsed = now - max(last_done[0], t_submit)      # wall time this frame added to the run (frames overlap in the pipeline)
         last_done[0] = now
@@ -379,6 +413,10 @@ def main(argv=None, mullevel=False):
             print("D1 mse, r/phi/theta, max    :", worse["mse"], *share, max(drep["a_to_b"]["total"]["max"], drep["b_to_a"]["total"]["max"]))
             with open(outfile[:-len(".bin")] + ".dist.json", "w") as f:
                 json.dump(dict(drep, lidar_level=args.lidar_level, type=args.type, n_points=res["n_points"]), f, indent=1)
+        if rrep:
+            print("ideal bits per leaf by ring :", *[e["ideal_bits_per_leaf"] for e in rrep["rings"]])
+            with open(outfile[:-len(".bin")] + ".rings.json", "w") as f:
+                json.dump(dict(rrep, lidar_level=args.lidar_level, type=args.type, n_points=res["n_points"], bits=res["bits"]), f, indent=1)
         sums[0] += res["bpp"]; sums[1] += dist["psnr"] if dist else 0.0; sums[2] += dist["chamfer"] if dist else 0.0
         sums[3] += elapsed; sums[4] += 1
 
@@ -411,7 +449,7 @@ def main(argv=None, mullevel=False):
                 c0, h0, ts = pending.pop(0)
                 report(c0, enc.finish(h0), ts)
             continue
-        dist = drep = None
+        dist = drep = rrep = None
         if args.preproc_path:
             # encode_dataset_ehem.py:149-157 / ..._mullevel.py:147-155: records + meta written by the test-set generator
             pp = args.preproc_path + ((cur.split("/")[-2] + Path(cur).stem) if args.type == "kitti" else Path(cur).stem)
@@ -426,13 +464,15 @@ def main(argv=None, mullevel=False):
             res = enc.encode(xyz, sequential=args.sequential)
         else:
             res = enc.encode(xyz)
-            if args.metrics or want_dist:
+            if args.metrics or want_dist or want_rings:
                 x_dev = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], np.float32)).to(dev)
             if args.metrics:
                 dist = enc.distortion(x_dev, normals=frame_normals(args.normals, cur, x_dev) if args.normals else None)
             if want_dist:
                 drep = enc.distortion_report(x_dev, dist_edges)
-        report(cur, res, t0, dist, drep)
+            if want_rings:
+                rrep = enc.ring_rate(x_dev, ring_edges)
+        report(cur, res, t0, dist, drep, rrep)
     for c0, h0, ts in pending:
         report(c0, enc.finish(h0), ts)
     total = D.reduce_summary(sums, dev)

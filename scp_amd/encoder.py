@@ -276,9 +276,13 @@ class _FrontEnd:
     device quantiser, and the lazily created coding pipeline of the asynchronous calls."""
     LANES_ENV = None                      # the environment variable that sets the number of lanes (read at the first asynchronous call)
 
-    def __init__(self, model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate=False):
+    def __init__(self, model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate=False, rate_rows=False):
         self.model = model
         self.rate = bool(rate)                # every result dict gains `rate` (one more read of the logits table per frame; the stream's bytes stay)
+        # with rate: the synchronous calls keep the per-row bits of their last frame on the device (two float64 per coded row) for
+        # FrameEncoder.ring_rate; off, the rate kernels allocate and launch exactly what they did before the option existed
+        self.rate_rows = bool(rate_rows)
+        self._rate_rows = None                # (row_ideal, row_table, plan) of the last synchronous encode, while its geometry stands
         # strict-identity switch (CLI --host_transform, SCP_XFORM=numpy): the float -> integer step of the reference on the host
         # (numpy float32 arctan2 / arccos, data_preprocess.py:42-70) instead of the device transform, whose float64 atan2 / acos is
         # more accurate and therefore gives other integers for a few points per frame (DESIGN.md 2.1).  Everything after the
@@ -339,14 +343,15 @@ class _FrontEnd:
 
     RATE_PHASES = False                   # EHEM: the report's segments follow the two-phase coding order of the windows
 
-    def _rate_launch(self, table, sym_coded, lohi, level_sizes):
+    def _rate_launch(self, table, sym_coded, lohi, level_sizes, keep_rows=False):
         """rate=True: the rate kernels on the current stream, right behind the CDF launch that wrote `lohi` -> (device records and what
-        their launches use - to be held until they have run -, the levels' segment lists); (None, None) when the report is off."""
+        their launches use - to be held until they have run -, the levels' segment lists); (None, None) when the report is off.
+        keep_rows: also the per-row bits, as a third entry (row_ideal, row_table)."""
         if not self.rate:
             return None, None
         off, levels = _rate_layout(level_sizes, self.context_size if self.RATE_PHASES else None)
-        r = native.rate_segments(table, sym_coded, lohi, off)
-        return (r["raw"], r["keep"]), levels
+        r = native.rate_segments(table, sym_coded, lohi, off, want_rows=keep_rows)
+        return ((r["raw"], r["keep"], (r["row_ideal"], r["row_table"])) if keep_rows else (r["raw"], r["keep"])), levels
 
 
 class FrameEncoder(_FrontEnd):
@@ -354,11 +359,11 @@ class FrameEncoder(_FrontEnd):
     RATE_PHASES = True
 
     def __init__(self, model, data_type=KITTI, lidar_level=12, spher=True, cylin=False, mullevel=False, max_batch=8,
-                 device=None, packed=True, max_tokens=1_000_000, host_transform=None, profile=None, rate=False):
+                 device=None, packed=True, max_tokens=1_000_000, host_transform=None, profile=None, rate=False, rate_rows=False):
         if mullevel and not (spher or cylin):
             # encode_dataset_ehem_mullevel.py:97-186 has a cylindrical and a spherical branch only
             raise native.ScpError("--mullevel needs --spher or --cylin (the reference has no Cartesian multi-level path)")
-        super().__init__(model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate)
+        super().__init__(model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate, rate_rows)
         self.profile = profile          # native.NumericProfile of THIS encoder (None: the process default); current around every launch
         self.packed = packed            # one packed forward for all windows (default) vs one forward per group of equal windows
         self.max_tokens = max_tokens
@@ -415,6 +420,39 @@ class FrameEncoder(_FrontEnd):
         rep["shell_leaves"] = [int(p.shape[0]) for p in pts]
         return rep
 
+    def ring_rate(self, xyz_dev, edges=None, infos=None):
+        """What every range ring and rho shell of the frame just encoded costs ("Rate per ring"): every node's ideal and
+        coded-table bits are handed to the leaves below it in equal parts (csrc/ringrate.hip), and the leaves are summed over the bins of
+        `distortion_report` - the reconstructed point's ring of `edges` (None: metrics.default_edges) and its shell.  Callable after a
+        synchronous `encode` / `encode_ints` of an encoder made with rate=True and rate_rows=True, like `distortion_report`; the
+        asynchronous and batch calls rebuild the geometry before they finish and keep no rows.  -> plain Python: edges,
+        groups[shell][ring] (leaves, ideal_bits, table_bits, max_ideal_bits, ideal / table bits per leaf), rings[ring] (the shells
+        added with math.fsum, and `points`: the input points whose own range lies in the ring), total, shell_leaves."""
+        from . import metrics
+        if not (self.rate and self.rate_rows):
+            raise native.ScpError("ring_rate needs the per-row bits of the frame: make the encoder with rate=True and rate_rows=True (rate alone "
+                                  "keeps per-level sums only)")
+        if self._rate_rows is None:
+            raise native.ScpError("ring_rate: no frame to report on - call it after a synchronous encode / encode_ints (the asynchronous and "
+                                  "batch calls, and the record files of --preproc_path, leave no geometry and no rows behind)")
+        edges = native.dist_edges(metrics.default_edges(self.data_type) if edges is None else edges)
+        row_ideal, row_table, plan = self._rate_rows
+        g, dev = self.geom, self.device
+        nd = g.nodes(("occ", "level", "parent"))
+        # coding order -> frame-order row -> node: the rows of the segments lie back to back, a drop_last segment's last node has none
+        node_of_row = torch.cat([torch.arange(int(i.node_base), int(i.node_base) + g.rows(s), device=dev) for s, i in enumerate(g.info)])
+        bits_ideal, bits_table = native.node_bits(plan.coding_order_device(dev), node_of_row, row_ideal, row_table, g.total_nodes)
+        share = native.rate_leaf_share(nd["occ"], nd["level"], nd["parent"], bits_ideal, bits_table, native.share_table(g.info),
+                                       sum(int(i.n_leaves) for i in g.info))
+        pts = self._reconstructed(infos)
+        group = torch.cat([torch.full((p.shape[0],), k, dtype=torch.int32, device=p.device) for k, p in enumerate(pts)])
+        bins = native.ring_bins(torch.cat(pts), edges, group, len(pts))
+        raw = native.share_segments(share["cost_ideal"], share["cost_table"], bins, len(pts) * len(edges))["raw"]
+        points = torch.bincount(native.ring_bins(xyz_dev[:, :3], edges), minlength=len(edges))
+        rep = metrics.ring_rate_dict(edges, raw.cpu().numpy(), points.cpu().tolist(), len(pts))
+        rep["shell_leaves"] = [int(p.shape[0]) for p in pts]
+        return rep
+
     def distortion(self, xyz_dev, infos=None, normals=None):
         """Chamfer distance and D1 PSNR of the frame just encoded (the octree of the last `encode` / `preprocess` call) against
         its input cloud, on the device - what the reference gets from distChamfer + the pc_error tool
@@ -443,6 +481,7 @@ class FrameEncoder(_FrontEnd):
     def _tables(self, bin_num, z_offset, n_points):
         """ctx / pos / coded symbols of every segment of the geometry just built, one launch (scp_geom_context_ehem_all)."""
         pos_mode = native.POS_MINMAX_MUL if self.mullevel else (native.POS_POW2 if self.mode == native.CART else native.POS_MINMAX)
+        self._rate_rows = None           # a new geometry: the rows ring_rate would join it with are the previous frame's
         ctx, pos, sym_coded, mm = self.geom.context_ehem_all(pos_mode, self.lidar_level, self.context_size)
         sizes = []
         for s in range(len(self.geom.info)):
@@ -698,7 +737,9 @@ class FrameEncoder(_FrontEnd):
             torch.cuda.synchronize()
         t2 = time.perf_counter()
         lohi_dev = native.softmax_cdf(table, sym_coded)["lohi"]
-        rate, levels = self._rate_launch(table, sym_coded, lohi_dev, plan.level_sizes)
+        keep_rows = self.rate and self.rate_rows and pre.get("sym_coded") is not None      # (record files: no geometry to join the rows with)
+        rate, levels = self._rate_launch(table, sym_coded, lohi_dev, plan.level_sizes, keep_rows=keep_rows)
+        self._rate_rows = (*rate[2], plan) if keep_rows else None
         lohi = lohi_dev.cpu().numpy()
         t3 = time.perf_counter()
         stream = native.ac_encode_lohi(lohi)

@@ -175,6 +175,39 @@ def distortion_report(pc, quant, edges, quant_group=None, n_groups=1, view=(0.0,
     return distortion_dict(edges, raw_ab.cpu().numpy(), raw_ba.cpu().numpy(), n_groups)
 
 
+def _share_entry(leaves, ideal, table, mx):
+    """One entry of the rate-per-ring report from raw sums (plain Python numbers); an entry without leaves has zeros per leaf."""
+    n = int(leaves)
+    return dict(leaves=n, ideal_bits=float(ideal), table_bits=float(table), max_ideal_bits=float(mx),
+                ideal_bits_per_leaf=float(ideal) / n if n else 0.0, table_bits_per_leaf=float(table) / n if n else 0.0)
+
+
+def _share_total(entries):
+    """Several bins together: counts add, the maximum is the largest, both sums are math.fsum over the bins."""
+    return _share_entry(sum(e["leaves"] for e in entries), math.fsum(e["ideal_bits"] for e in entries),
+                        math.fsum(e["table_bits"] for e in entries), max([e["max_ideal_bits"] for e in entries] + [0.0]))
+
+
+def ring_rate_dict(edges, raw, points, n_groups=1):
+    """The rate-per-ring report from the scp_share_seg records on the host (no device needed): raw int64 [n_groups * R, 4] (bin = group *
+    R + ring, native.share_segments(...)["raw"].cpu().numpy()), points = the R counts of input points per ring, R = len(edges).  -> edges,
+    groups[g][r], rings[r] (the groups added, plus `points` and the bits per input point), total.  Plain Python (json.dumps takes it)."""
+    edges = list(native.dist_edges(edges))
+    R = len(edges)
+    raw = np.ascontiguousarray(raw, np.int64)
+    if raw.ndim != 2 or raw.shape != (n_groups * R, len(native.SHARE_FIELDS)) or len(points) != R:
+        raise native.ScpError(f"rate per ring: {raw.shape} records and {len(points)} point counts for {R} rings and {n_groups} groups")
+    rec = native.share_record_views(raw)
+    flat = [_share_entry(rec["leaves"][k], rec["ideal_bits"][k], rec["table_bits"][k], rec["max_ideal_bits"][k]) for k in range(n_groups * R)]
+    groups = [flat[g * R:(g + 1) * R] for g in range(n_groups)]
+
+    def with_points(e, n):
+        n = int(n)
+        return dict(e, points=n, ideal_bits_per_point=e["ideal_bits"] / n if n else 0.0, table_bits_per_point=e["table_bits"] / n if n else 0.0)
+    rings = [with_points(_share_total([g[r] for g in groups]), points[r]) for r in range(R)]
+    return dict(edges=edges, groups=groups, rings=rings, total=with_points(_share_total(flat), sum(int(n) for n in points)))
+
+
 def dequantize(leaves, qs, offset, spher=False, cylin=False, f32=False):
     """leaves int [U,3] (device) -> de-quantised Cartesian points [U,3]: `pt * qs + offset` in float64, then spher2cart /
     cylin2cart (data_preprocess.py:186-229).  f32=True: the same-level path rounds to float32 before the inverse transform

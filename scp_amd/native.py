@@ -152,6 +152,10 @@ def lib():
         "scp_rate_segments": (C.c_int, [_vp, i64, i64, i32, _vp, _vp, _vp, i32, _vp, _vp, _vp, _vp, i64, _vp]),
         "scp_nn_error_split_f64": (C.c_int, [_vp, i64, _vp, i64, _vp, _vp, i32, _vp, i32, _vp, _vp, _vp, _vp, _vp, _vp]),
         "scp_dist_segments_f64": (C.c_int, [_vp, _vp, _vp, _vp, i64, _vp, i32, _vp, _vp]),
+        "scp_rate_leaf_share_workspace_bytes": (C.c_int64, [i64, i32]),
+        "scp_rate_leaf_share": (C.c_int, [_vp, _vp, _vp, i64, _vp, _vp, _vp, i32, i64, _vp, _vp, _vp, _vp, i64, _vp]),
+        "scp_ring_bins_f64": (C.c_int, [_vp, i64, _vp, _vp, i32, _vp, i32, _vp, _vp, _vp]),
+        "scp_share_segments_f64": (C.c_int, [_vp, _vp, _vp, i64, _vp, i32, _vp, _vp]),
         "scp_ac_encode_cdf": (C.c_int, [_vp, _vp, i64, i32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "scp_ac_encode_lohi": (C.c_int, [_vp, i64, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "scp_ac_dec_new": (C.c_int, [C.POINTER(_vp), _vp, C.c_size_t, i32]),
@@ -1761,6 +1765,126 @@ def dist_record_views(raw):
         out[name] = col if name in ("rows", "axis_rows") else f64(col)
     out["hist"] = raw[:, len(DIST_FIELDS):]
     return out
+
+
+# ------------------------------------------------------------------------------------------------- rate per ring (csrc/ringrate.hip)
+SHARE_FIELDS = ("leaves", "ideal_bits", "table_bits", "max_ideal_bits")     # include/scp.h: scp_share_seg, four 8-byte fields
+MAX_SEGMENTS = 62                                                           # include/scp.h: SCP_MAX_SEGMENTS
+
+
+def share_table(infos):
+    """The per-segment table of rate_leaf_share from the SegmentInfo list of a Geom build (`Geom.info`): numpy int64 [S,4] = (node_base,
+    n_nodes, depth, leaf_base), the leaves of the segments back to back in segment order.  Host only."""
+    tab, leaf = np.zeros((len(infos), 4), np.int64), 0
+    for s, i in enumerate(infos):
+        tab[s] = (int(i.node_base), int(i.n_nodes), int(i.depth), leaf)
+        leaf += int(i.n_leaves)
+    return tab
+
+
+def node_bits(order, node_of_row, row_ideal, row_table, total_nodes):
+    """Per-row bits in CODING order -> per-node bits (index plumbing, torch): order int64 [R] = the frame-order row of every coded
+    position (EncodePlan.coding_order_device), node_of_row int64 [R] = the node of every frame-order row (a drop_last segment's last
+    node has no row), row_ideal / row_table float64 [R] (rate_segments(..., want_rows=True)).  -> (ideal, table) float64 [total_nodes],
+    0 for a node without a row."""
+    R = int(order.shape[0])
+    if tuple(node_of_row.shape) != (R,) or tuple(row_ideal.shape) != (R,) or tuple(row_table.shape) != (R,):
+        raise ScpError(f"node_bits: {R} coded positions, but {tuple(node_of_row.shape)} rows and {tuple(row_ideal.shape)} / {tuple(row_table.shape)} bits")
+    node = node_of_row[order]
+    ideal = torch.zeros(total_nodes, dtype=torch.float64, device=row_ideal.device)
+    table = torch.zeros(total_nodes, dtype=torch.float64, device=row_ideal.device)
+    ideal[node] = row_ideal
+    table[node] = row_table
+    return ideal, table
+
+
+def rate_leaf_share(occ, level, parent, bits_ideal, bits_table, segs, total_leaves):
+    """scp_rate_leaf_share: every leaf's share of its ancestors' bits (include/scp.h states the definition).  occ / level uint8, parent
+    int32, bits_ideal / bits_table float64: device tensors [N], the node columns of all segments of a build (Geom.nodes) and what every
+    node cost; segs: host int64 [S,4] (node_base, n_nodes, depth, leaf_base) - share_table(geom.info).  -> dict of device tensors: leaves
+    int64 [N], cost_ideal / cost_table float64 [total_leaves] (segment-major, the order of Geom.leaves inside a segment).  A table the
+    library's validation pass objects to raises ScpError (SCP_EINVAL); the call waits for the stream once."""
+    N = int(occ.shape[0])
+    for t, dt, name in ((occ, torch.uint8, "occ"), (level, torch.uint8, "level"), (parent, torch.int32, "parent"),
+                        (bits_ideal, torch.float64, "bits_ideal"), (bits_table, torch.float64, "bits_table")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != (N,):
+            raise ScpError(f"rate_leaf_share: {name} is a device tensor of {dt} with one entry per node ({N})")
+    segs = np.ascontiguousarray(segs, np.int64)
+    if segs.ndim != 2 or segs.shape[1] != 4:
+        raise ScpError(f"rate_leaf_share: the segment table is int64 [S,4] (node_base, n_nodes, depth, leaf_base), got {segs.shape}")
+    S, total_leaves = int(segs.shape[0]), int(total_leaves)
+    ws_bytes = int(lib().scp_rate_leaf_share_workspace_bytes(N, S))
+    if ws_bytes < 0:
+        raise ScpError(f"rate_leaf_share: {N} nodes in {S} segments: 1 .. 2^30 nodes in 1 .. {MAX_SEGMENTS} segments expected")
+    dev = occ.device
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    leaves = torch.empty(N, dtype=torch.int64, device=dev)
+    ci = torch.empty(max(total_leaves, 0), dtype=torch.float64, device=dev)
+    ct = torch.empty(max(total_leaves, 0), dtype=torch.float64, device=dev)
+    rc = lib().scp_rate_leaf_share(_dev(occ), _dev(level), _dev(parent), N, _dev(bits_ideal), _dev(bits_table), segs.ctypes.data, S, total_leaves,
+                                   leaves.data_ptr(), ci.data_ptr(), ct.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
+    _check(rc, "scp_rate_leaf_share")
+    return dict(leaves=leaves, cost_ideal=ci, cost_table=ct)
+
+
+def ring_bins(xyz, edges, group=None, n_groups=1, view=(0.0, 0.0, 0.0)):
+    """scp_ring_bins_f64: the (group, ring) bin of every point of a cloud [n,3] (device, compared in float64) - the bins nn_error_split
+    gives its queries, integer for integer; edges / group / n_groups / view as there.  -> device int32 [n]."""
+    e = dist_edges(edges)
+    n_groups = int(n_groups)
+    if n_groups < 1 or n_groups * len(e) > DIST_MAX_BINS:
+        raise ScpError(f"ring_bins: {n_groups} groups x {len(e)} rings: between 1 and {DIST_MAX_BINS} bins expected")
+    a = _dev_f64(xyz)
+    if a.dim() != 2 or a.shape[1] != 3 or a.shape[0] < 1:
+        raise ScpError(f"ring_bins: a cloud of shape [n,3] with n >= 1 expected, got {tuple(a.shape)}")
+    n = a.shape[0]
+    if group is not None:
+        if not group.is_cuda or group.dtype != torch.int32 or tuple(group.shape) != (n,):
+            raise ScpError(f"ring_bins: group is a device int32 tensor with one entry per point ({n})")
+        group = group.contiguous()
+        lo, hi = int(group.min().item()), int(group.max().item())
+        if lo < 0 or hi >= n_groups:
+            raise ScpError(f"ring_bins: group values {lo} .. {hi} outside 0 .. {n_groups - 1}")
+    view = tuple(float(c) for c in view)
+    if len(view) != 3 or not all(abs(c) < float("inf") for c in view):
+        raise ScpError(f"ring_bins: view is the sensor position, three finite numbers, got {view}")
+    v = (C.c_double * 3)(*view)
+    esq = (C.c_double * len(e))(*[c * c for c in e])
+    bin_ = torch.empty((n,), dtype=torch.int32, device=a.device)
+    _check(lib().scp_ring_bins_f64(a.data_ptr(), n, C.cast(v, _vp), C.cast(esq, _vp), len(e), None if group is None else group.data_ptr(), n_groups,
+                                   bin_.data_ptr(), None, _stream()), "scp_ring_bins_f64")
+    return bin_
+
+
+def share_segments(cost_ideal, cost_table, bins, n_bins):
+    """scp_share_segments_f64: one record per bin 0 .. n_bins - 1 from the leaf costs of rate_leaf_share and the leaves' bins (int32, any
+    order: a stable sort brings every bin's rows together in index order, which the summation contract needs).  -> dict of device tensors,
+    views of `raw` int64 [n_bins, 4] (the scp_share_seg records: one copy brings them all to the host): leaves int64, ideal_bits,
+    table_bits, max_ideal_bits float64 [n_bins].  A bin without rows is all zeros; a row whose bin lies outside 0 .. n_bins - 1 belongs to
+    no record."""
+    n_bins = int(n_bins)
+    if n_bins < 1 or n_bins > DIST_MAX_BINS:
+        raise ScpError(f"share_segments: between 1 and {DIST_MAX_BINS} bins expected, got {n_bins}")
+    for t, dt, name in ((cost_ideal, torch.float64, "cost_ideal"), (cost_table, torch.float64, "cost_table"), (bins, torch.int32, "bins")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
+            raise ScpError(f"share_segments: {name} is a device tensor of {dt} (there is no CPU path in the product)")
+    n = cost_ideal.shape[0]
+    if n < 1 or tuple(cost_ideal.shape) != (n,) or tuple(cost_table.shape) != (n,) or tuple(bins.shape) != (n,):
+        raise ScpError(f"share_segments: cost_ideal [n], cost_table [n], bins [n] with n >= 1 expected, got {tuple(cost_ideal.shape)}, "
+                       f"{tuple(cost_table.shape)}, {tuple(bins.shape)}")
+    cost_ideal, cost_table = cost_ideal.contiguous(), cost_table.contiguous()
+    ordered, order = torch.sort(bins, stable=True)
+    seg_off = torch.searchsorted(ordered, torch.arange(n_bins + 1, dtype=torch.int32, device=bins.device)).to(torch.int64).contiguous()
+    raw = torch.empty((n_bins, len(SHARE_FIELDS)), dtype=torch.int64, device=cost_ideal.device)
+    _check(lib().scp_share_segments_f64(cost_ideal.data_ptr(), cost_table.data_ptr(), order.data_ptr(), n, seg_off.data_ptr(), n_bins, raw.data_ptr(),
+                                        _stream()), "scp_share_segments_f64")
+    return dict(share_record_views(raw), raw=raw)
+
+
+def share_record_views(raw):
+    """The fields of scp_share_seg records held as int64 [n_bins, 4] (a torch tensor or a numpy array, device or host) -> dict of views."""
+    f64 = (lambda c: c.view(torch.float64)) if isinstance(raw, torch.Tensor) else (lambda c: c.view(np.float64))
+    return {name: (raw[:, k] if name == "leaves" else f64(raw[:, k])) for k, name in enumerate(SHARE_FIELDS)}
 
 
 # ------------------------------------------------------------------------------------------------- range coder (host)
