@@ -598,6 +598,36 @@ SCP_API int scp_ring_bins_f64(const double *xyz, int64_t n, const double *view, 
 SCP_API int scp_share_segments_f64(const double *cost_ideal, const double *cost_table, const int64_t *order /* NULL ok */, int64_t n,
                                    const int64_t *seg_off, int32_t n_bins, scp_share_seg *out, void *stream);
 
+/* Depth report (csrc/depthshare.hip; additive, no new ABI version; host side: scp_amd/metrics.py depth_dict, FrameEncoder.depth_report):
+ * what the first D - k levels of a tree cost, per leaf and per bin - an octree stream is progressive, its levels 1 .. D - k describe the
+ * cloud at cell size 2^k.  With leaves(i), share(i), the ancestors a_l and the leaf order of the rate per ring above:
+ *   cost_k(p) = ((share(a_1) + share(a_2)) + ..) + share(a_{D-k})   for 0 <= k < D: the operations of cost(p), the chain cut short;
+ *   cost_k(p) = +0.0                                                for k >= D.
+ * cost_0 is scp_rate_leaf_share's cost bit for bit; float64, no fused operation, no floating-point atomics.
+ *
+ * scp_rate_depth_share: the arguments of scp_rate_leaf_share plus max_drop (0 .. SCP_MAX_DEPTH).  Outputs (DEVICE): leaves int64
+ * [total_nodes]; cost_ideal, cost_table float64 [(max_drop + 1) * total_leaves], plane k (= cost_k of every leaf, in the leaf order of
+ * scp_rate_leaf_share) at offset k * total_leaves.  workspace: scp_rate_depth_share_workspace_bytes(total_nodes, nseg) bytes, 8-byte
+ * aligned device memory.  The host checks and the validation launch of scp_rate_leaf_share apply unchanged, and max_drop outside its
+ * range is refused with them: SCP_EINVAL, nothing written to an output (the call synchronises `stream` once).
+ * Order: leaves and the per-node sums as in scp_rate_leaf_share; then one launch in which every level-D node climbs up to max_drop
+ * parents and writes every plane of the leaves it owns.  All segments share the launches, whose number (2 * deepest tree + 2) depends
+ * on the depths alone - not on node counts, segment counts or max_drop.
+ *
+ * scp_share_segments_depth_f64: scp_share_segments_f64 on n_depths planes in one launch (depth on the second grid axis): plane d of
+ * cost_ideal / cost_table starts at d * plane_stride (>= n); order, seg_off, n, clamping and the SUMMATION CONTRACT exactly as there, the
+ * same for every plane.  out: scp_share_seg [n_depths][n_bins]; record [0][b] equals what scp_share_segments_f64 returns on plane 0,
+ * field for field.  n_depths outside 1 .. SCP_MAX_DEPTH + 1, plane_stride < n or > 2^30, or an argument scp_share_segments_f64
+ * refuses: SCP_EINVAL, nothing launched. */
+SCP_API int64_t scp_rate_depth_share_workspace_bytes(int64_t total_nodes, int32_t nseg);   /* bytes, or SCP_EINVAL */
+SCP_API int scp_rate_depth_share(const uint8_t *occ, const uint8_t *level, const int32_t *parent, int64_t total_nodes, const double *bits_ideal,
+                                 const double *bits_table, const int64_t *segs /* HOST [nseg][4] */, int32_t nseg, int64_t total_leaves,
+                                 int32_t max_drop, int64_t *leaves, double *cost_ideal, double *cost_table, void *workspace,
+                                 int64_t workspace_bytes, void *stream);
+SCP_API int scp_share_segments_depth_f64(const double *cost_ideal, const double *cost_table, const int64_t *order /* NULL ok */, int64_t n,
+                                         const int64_t *seg_off, int32_t n_bins, int32_t n_depths, int64_t plane_stride, scp_share_seg *out,
+                                         void *stream);
+
 /* Input stage of the packed EHEM forward: embeddings of dgcnn.py:121-128 fused with the packed layout's input gather.
  * ctx u8 [T][12] = 4 x (level, octant, occ) (scp_geom_context_ehem), pos f32 [T][3], inmap i64 [rows] (== n_tokens: pad token);
  * tables occ_enc [256][16], level_enc [*][4], octant_enc [*][4]; out x f32 [rows][80], pos_out f32 [rows][3], occ_self i64 [rows]. */

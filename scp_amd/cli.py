@@ -20,6 +20,11 @@ same stdout block per frame, same summary file.  Differences, all additive:
     equal parts and summed per ring (same EDGES and defaults as `--distortion_report`) and rho shell, computed on the device
     (csrc/ringrate.hip): one more line per frame (ideal bits per leaf of every ring) and a `<stream>.rings.json` next to every stream
     (tools/rd_rings.py joins it with the `.dist.json`).  Implies the rate kernels; the streams themselves do not change.
+  * `--depth_report [K[:EDGES]]` (EHEM): what every octree level costs and buys, from one encode - for every truncation depth k = 0 .. K
+    (default 4) the bits of levels 1 .. D - k per range ring and rho shell (csrc/depthshare.hip, on the bins of `--rate_rings`) and the D1
+    error of the cloud those levels describe (the cells of size 2^k, which `decode_ehem.py --lod k` writes): one more line per frame
+    (ideal bits per point and D1 PSNR for every k) and a `<stream>.depth.json` next to every stream (tools/rd_depth.py reads it).
+    Implies the rate kernels; the streams themselves do not change.
   * `--normals estimate|DIR` (with `--metrics`, EHEM): the D2 (point-to-plane) PSNR as well, on normals estimated on the device or
     read from the `<DIR>/<sequence>/<frame>.ply` files `gene_normals.py` writes; one more line per frame, `PSNR_D2:` in the summary.
 """
@@ -93,6 +98,29 @@ def rings_request(args):
     return (v is not None and v is not False), (None if v is None or isinstance(v, bool) else tuple(v))
 
 
+DEPTH_REPORT_DEFAULT = 4
+
+
+def parse_depth_report(text):
+    """`--depth_report 3` / `--depth_report 3:0,5,10`: (K, ring edges or None); the edges in --distortion_report's syntax."""
+    k, _, e = text.partition(":")
+    try:
+        drop = int(k) if k else DEPTH_REPORT_DEFAULT
+    except ValueError:
+        raise native.ScpError(f"--depth_report: K[:EDGES] with K the number of levels to drop (0 .. {native.MAX_DEPTH}), got {text!r}")
+    if not 0 <= drop <= native.MAX_DEPTH:
+        raise native.ScpError(f"--depth_report: K = {drop} outside 0 .. {native.MAX_DEPTH}")
+    return drop, (parse_edges(e, "--depth_report") if e else None)
+
+
+def depth_request(args):
+    """(wanted, K, edges) of --depth_report: (False, None, None) without the flag; the flag alone asks for K = 4 and the default edges."""
+    v = getattr(args, "depth_report", None)
+    if v is None or v is False:
+        return False, None, None
+    return (True, DEPTH_REPORT_DEFAULT, None) if v is True else (True, v[0], None if v[1] is None else tuple(v[1]))
+
+
 def get_args(argv=None, mullevel=False):
     p = argparse.ArgumentParser()
     p.add_argument("--ckpt_path", type=str, default="", help="example: outputs/obj/2023-04-28/10-43-45/ckpt/epoch=7-step=64088.ckpt")
@@ -133,6 +161,12 @@ def get_args(argv=None, mullevel=False):
                    help="per frame (EHEM): ideal bits per leaf of every range ring on one more line, and <stream>.rings.json next to the stream "
                         "with ideal / coded-table bits and leaves per ring and rho shell (every node's bits shared equally among the points "
                         "below it); EDGES as for --distortion_report, with the same defaults; implies the rate kernels; the streams do not change")
+    # (absent from the namespace unless given: read it with depth_request(args))
+    p.add_argument("--depth_report", nargs="?", const=True, type=parse_depth_report, default=argparse.SUPPRESS, metavar="K[:EDGES]",
+                   help="per frame (EHEM): for every truncation depth k = 0 .. K (default 4) the ideal bits per point of octree levels 1 .. D - k "
+                        "and the D1 PSNR of the cloud they describe on one more line, and <stream>.depth.json next to the stream with both per "
+                        "range ring and rho shell (what decode_ehem*.py --lod k would write); EDGES as for --rate_rings, with the same defaults; "
+                        "implies the rate kernels; the streams do not change")
     p.add_argument("--host_transform", action="store_true",
                    help="strict identity with the reference from the frame on: the coordinate transform + quantiser run in numpy float32 on the "
                         "host exactly as data_preprocess.py:42-70 does (the device transform is more accurate, hence not bit-identical); "
@@ -203,6 +237,18 @@ def refuse_unsupported(args, name, mullevel):
         if args.preproc_path:
             raise native.ScpError("--rate_rings with --preproc_path: no geometry of the frame is built there, only its records are coded")
         if ring_edges is None:
+            from . import metrics
+            metrics.default_edges(args.type)
+    want_depth, _, depth_edges = depth_request(args)
+    if want_depth:
+        if name == "OctAttention":
+            raise native.ScpError("--depth_report is available for the EHEM encoders only (like --rate_rings: the OctAttention encoders "
+                                  "keep no reconstructed cloud)")
+        if args.type == "obj":
+            raise native.ScpError("--depth_report bins the points by their range from a LiDAR sensor at the origin: --type obj has none")
+        if args.preproc_path:
+            raise native.ScpError("--depth_report with --preproc_path: no geometry of the frame is built there, only its records are coded")
+        if depth_edges is None:
             from . import metrics
             metrics.default_edges(args.type)
     if args.type == "obj" and (args.spher or args.cylin or mullevel and name != "OctAttention"):
@@ -330,6 +376,7 @@ def main(argv=None, mullevel=False):
     rate_report = getattr(args, "rate_report", False)
     want_dist, dist_edges = distortion_request(args)
     want_rings, ring_edges = rings_request(args)
+    want_depth, depth_drop, depth_edges = depth_request(args)
     cls = OctAttention if name == "OctAttention" else EHEM
     if args.random_weights is not None or not args.ckpt_path:
         from .weights import fill_weights
@@ -355,14 +402,15 @@ def main(argv=None, mullevel=False):
                                   host_transform=True if args.host_transform else None, decodable=args.decodable, rate=rate_report)
     else:
         enc = FrameEncoder(model, args.type, args.lidar_level, spher=args.spher, cylin=args.cylin, mullevel=mullevel, device=dev,
-                           host_transform=True if args.host_transform else None, rate=rate_report or want_rings, rate_rows=want_rings)
+                           host_transform=True if args.host_transform else None, rate=rate_report or want_rings or want_depth,
+                           rate_rows=want_rings or want_depth)
 
     mine = D.shard(files, rank, world)
     # fast path: frames are enqueued with encode_async (stage G on a side stream, two model lanes, range coder on a worker thread)
     # and finished three frames later - what bench.py measures.  Flows that need the frame's octree after the encode (--metrics, --distortion_report,
-    # --rate_rings),
+    # --rate_rings, --depth_report),
     # come from record files, or run the one-window-per-node mode stay on the synchronous call.
-    pipelined = not (args.preproc_path or args.metrics or want_dist or want_rings or args.sequential or obj)
+    pipelined = not (args.preproc_path or args.metrics or want_dist or want_rings or want_depth or args.sequential or obj)
     DEPTH = 3
     host_ints = enc.host_ints if (pipelined and name != "OctAttention" and enc.host_transform) else None
     reader = Prefetch(mine, post=host_ints)
@@ -375,7 +423,7 @@ def main(argv=None, mullevel=False):
         return (cur.split("/")[-2] + Path(cur).stem) if (args.type == "kitti" and name != "OctAttention" and "/" in cur.rstrip("/")
                                                           and len(cur.split("/")) >= 2) else Path(cur).stem
 
-    def report(cur, res, t_submit, dist=None, drep=None, rrep=None):
+    def report(cur, res, t_submit, dist=None, drep=None, rrep=None, lrep=None):
         now = time.time()
         elapsed = now - max(last_done[0], t_submit)      # wall time this frame added to the run (frames overlap in the pipeline)
         last_done[0] = now
@@ -417,6 +465,10 @@ def main(argv=None, mullevel=False):
             print("ideal bits per leaf by ring :", *[e["ideal_bits_per_leaf"] for e in rrep["rings"]])
             with open(outfile[:-len(".bin")] + ".rings.json", "w") as f:
                 json.dump(dict(rrep, lidar_level=args.lidar_level, type=args.type, n_points=res["n_points"], bits=res["bits"]), f, indent=1)
+        if lrep:
+            print("depth k: ideal bpp, D1 PSNR :", *[v for lv in lrep["levels"] for v in (lv["rate"]["total"]["ideal_bits_per_point"], lv["d1"]["psnr"])])
+            with open(outfile[:-len(".bin")] + ".depth.json", "w") as f:
+                json.dump(dict(lrep, lidar_level=args.lidar_level, type=args.type, n_points=res["n_points"], bits=res["bits"]), f, indent=1)
         sums[0] += res["bpp"]; sums[1] += dist["psnr"] if dist else 0.0; sums[2] += dist["chamfer"] if dist else 0.0
         sums[3] += elapsed; sums[4] += 1
 
@@ -449,7 +501,7 @@ def main(argv=None, mullevel=False):
                 c0, h0, ts = pending.pop(0)
                 report(c0, enc.finish(h0), ts)
             continue
-        dist = drep = rrep = None
+        dist = drep = rrep = lrep = None
         if args.preproc_path:
             # encode_dataset_ehem.py:149-157 / ..._mullevel.py:147-155: records + meta written by the test-set generator
             pp = args.preproc_path + ((cur.split("/")[-2] + Path(cur).stem) if args.type == "kitti" else Path(cur).stem)
@@ -464,7 +516,7 @@ def main(argv=None, mullevel=False):
             res = enc.encode(xyz, sequential=args.sequential)
         else:
             res = enc.encode(xyz)
-            if args.metrics or want_dist or want_rings:
+            if args.metrics or want_dist or want_rings or want_depth:
                 x_dev = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], np.float32)).to(dev)
             if args.metrics:
                 dist = enc.distortion(x_dev, normals=frame_normals(args.normals, cur, x_dev) if args.normals else None)
@@ -472,7 +524,9 @@ def main(argv=None, mullevel=False):
                 drep = enc.distortion_report(x_dev, dist_edges)
             if want_rings:
                 rrep = enc.ring_rate(x_dev, ring_edges)
-        report(cur, res, t0, dist, drep, rrep)
+            if want_depth:
+                lrep = enc.depth_report(x_dev, depth_drop, depth_edges)
+        report(cur, res, t0, dist, drep, rrep, lrep)
     for c0, h0, ts in pending:
         report(c0, enc.finish(h0), ts)
     total = D.reduce_summary(sums, dev)
@@ -511,6 +565,11 @@ def get_decode_args(argv=None):
     p.add_argument("--streams", type=_streams_arg, default=1,
                    help="decode this many files at a time in lockstep, one packed forward serving one level of each (1 .. 64; default 1: one "
                         "file after the other).  With more than one, the time printed per file is the total over the number of files")
+    p.add_argument("--lod", type=int, default=0, metavar="K",
+                   help="preview: stop every tree after its level D - K and write the centres of the cells of size 2^K those levels describe "
+                        "(what encode*.py --depth_report measures at k = K); 0 (default): the full decode.  A multi-level stream codes its "
+                        "shells one after the other, so the first two are decoded in full - the range decoder has to pass them - and only "
+                        "the last one stops early.  K <= the shallowest shell's depth - 1; not with --streams above 1")
     return p.parse_args(argv)
 
 
@@ -658,6 +717,11 @@ def decode_main(argv=None, mullevel=False):
     cfg = load_cfg(args.ckpt_path, "EHEM")
     if cfg.model.class_name != "EHEM":
         raise native.ScpError("decode_ehem*.py decode EHEM streams; OctAttention streams written with --decodable: decode.py")
+    if args.lod < 0:
+        raise native.ScpError(f"--lod {args.lod}: 0 (the full decode) or the number of levels to leave out expected")
+    if args.lod and args.streams > 1:
+        raise native.ScpError("--lod with --streams above 1: the lockstep decoder decodes every level of every stream; decode previews one "
+                              "file after the other (--streams 1)")
     if args.random_weights is not None or not args.ckpt_path:
         from .weights import fill_weights
         model = fill_weights(EHEM(cfg), args.random_weights or 0)
@@ -693,7 +757,7 @@ def decode_main(argv=None, mullevel=False):
             name, stem = find_stream(out_root, ori)            # the stem that matched, not string surgery on the stream name
             binfile = out_root + name
             t0 = time.time()
-            out = decode_file(binfile, model, args.lidar_level, args.type, mullevel, dev)
+            out = decode_file(binfile, model, args.lidar_level, args.type, mullevel, dev, lod=args.lod)
             torch.cuda.synchronize()
             t = time.time() - t0
         elapsed += t
@@ -708,6 +772,7 @@ def decode_main(argv=None, mullevel=False):
             for codes, c in zip(out["codes"], cands_npy):
                 want = np.load(c)[:, -1, 0]
                 got = codes.cpu().numpy()[:len(want)]
+                want = want[:len(got)] if args.lod else want          # --lod: the decoded levels only
                 assert np.array_equal(got.astype(np.int64), want), f"decoded occupancy differs from {c}"
             print("checked against", ", ".join(cands_npy))
         print("decode succeeded, time:", t)

@@ -472,9 +472,23 @@ def _obj_without_quant(binfile):
                            "(data_preprocess.py:31-37), which only the sidecar's `quant` entry records - it is missing here")
 
 
-def _ehem_result(job, shells):
-    """The decoded shells [(codes per level, leaf integers)] of a job -> the dict decode_file returns."""
+def check_lod(lod, depths):
+    """--lod K of a stream whose shells are `depths` levels deep: 0 .. the shallowest depth - 1, or refused with the reason."""
+    if isinstance(lod, bool) or not isinstance(lod, int) or not 0 <= lod <= min(depths) - 1:
+        raise native.ScpError(f"lod {lod!r} outside 0 .. {min(depths) - 1}: the shells of this stream are {list(depths)} levels deep and LOD K "
+                              "stops a tree after its level depth - K, of which there is at least one")
+    return lod
+
+
+def _ehem_result(job, shells, lod=0):
+    """The decoded shells [(codes per level, leaf integers)] of a job -> the dict decode_file returns.  lod = K >= 1: the shells carry
+    their LOD-K cell origins as a third entry; `points` are the cells' centres (metrics.lod_centres) through the same dequantiser, and
+    the dict gains lod, cells (per shell) and levels_decoded (the levels of all shells that were decoded)."""
     binfile, side, spher, cylin, data_type = job["name"], job["side"], job["spher"], job["cylin"], job["data_type"]
+    full = shells
+    if lod:
+        from . import metrics
+        shells = [(c, metrics.lod_centres(cells, lod)) for c, _, cells in full]
     # KITTI / Ford: the reference decoder's own rule (steps from the integer bin_num in float64, decode_ehem.py:237-249) - the cloud it
     # would write.  obj: there is no rule (the offset is the frame's per-axis minimum): the sidecar's `quant` entry, or nothing.
     quant = side.get("quant") if side is not None else None
@@ -485,19 +499,26 @@ def _ehem_result(job, shells):
         raise _obj_without_quant(binfile)
     else:
         pts = [dequantise_leaves(lv, q, b, job["z_offset"], spher, cylin, data_type) for (_, lv), q, b in zip(shells, job["qs"], job["bins"])]
-    return dict(codes=[torch.cat(c) for c, _ in shells], leaves=[lv for _, lv in shells], points=torch.cat(pts),
-                spher=spher, cylin=cylin, n_levels=job["n_levels"], bin_num=job["bin_num"], z_offset=job["z_offset"],
-                lidar_level=job["lidar_level"])
+    out = dict(codes=[torch.cat(c) for c, _ in shells], leaves=[lv for _, lv in shells], points=torch.cat(pts),
+               spher=spher, cylin=cylin, n_levels=job["n_levels"], bin_num=job["bin_num"], z_offset=job["z_offset"],
+               lidar_level=job["lidar_level"])
+    if lod:
+        out.update(leaves=[lv for _, lv, _ in full], lod=lod, cells=[cells for _, _, cells in full], levels_decoded=sum(len(c) for c, _, _ in full))
+    return out
 
 
-def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False, device=None, profile=None):
+def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False, device=None, profile=None, lod=0):
     """A stream file written by the encode CLIs -> dict(codes per shell, leaves per shell, points [U,3] float64 Cartesian).
     Side information exactly as the reference's decoders take it (`extract_info`); the `.scp.json` written next to the stream
     supplies what that cannot carry.  Without it the reference's own rules apply: lidar level = the level count (decode_ehem.py:218),
-    integer z offset, and - for the two outer shells - bin numbers extrapolated from the first shell's."""
+    integer z offset, and - for the two outer shells - bin numbers extrapolated from the first shell's.
+    lod = K >= 1 (at most the shallowest shell's depth - 1): a preview - the tree stops after level D - K and `points` holds the centres
+    of the cells of size 2^K those levels describe ("Depth report"); a multi-level stream decodes its first two shells in
+    full, since the range decoder has to pass them, and stops the last one early.  The dict gains lod, cells (int64 origins per shell)
+    and levels_decoded (over all shells: D - K for one tree); `leaves` holds None for the shell that stopped.  lod = 0 is the path without the option."""
     job = _ehem_job(binfile, lidar_level, data_type, mullevel, profile)
     dec = FrameDecoder(model, job["lidar_level"], mullevel=mullevel, polar=job["polar"], device=device, profile=profile)
-    return _ehem_result(job, dec.decode(job["stream"], job["n_levels"], job["pos_mm"]))
+    return _ehem_result(job, dec.decode(job["stream"], job["n_levels"], job["pos_mm"], lod), lod)
 
 
 def shell_depths(n_levels, mullevel):
@@ -756,8 +777,10 @@ class FrameDecoder(_EhemRounds):
         self._decode_round([dec], steps, ctx, pos, sym, [0])
         return torch.from_numpy(sym).to(self.device)
 
-    def _decode_tree(self, dec, depth, pos_mm):
-        """One octree: returns (codes per level as device uint8 tensors, leaf integer coordinates [U,3]).
+    def _decode_tree(self, dec, depth, pos_mm, lod=0, stop=False):
+        """One octree: returns (codes per level as device uint8 tensors, leaf integer coordinates [U,3]).  lod = K >= 1: a third entry,
+        the origins of the level-(depth - K + 1) nodes (int64 [C,3], leaf units, node order) - what the symbols of level depth - K name;
+        with `stop` the tree ends there (the levels below are not decoded, the leaves are None).
         Level state: pos int32 [n,3] node origins, anc uint8 [n,9] = (level, octant, symbol) of (ggp, gp, p) with pad = (0, 0, 255), octant uint8 [n];
         the children of a decoded level and the model inputs of the level they form come from one launch (native.decode_expand)."""
         dev = self.device
@@ -790,19 +813,27 @@ class FrameDecoder(_EhemRounds):
                 lvn, clamp, mn, den = level_params(L + 1)
             occ8, pos, anc, octant, ctx, posn = native.decode_expand(sym, pos, anc, octant, L, depth - L, lvn, clamp, self.polar and not last, mn, den)
             codes.append(occ8)
+            if lod and L == depth - lod:
+                cells = pos.long()
+                if stop:
+                    return codes, None, cells
             if last:
-                return codes, pos.long()
+                return (codes, pos.long(), cells) if lod else (codes, pos.long())
 
-    def decode(self, stream, n_levels, pos_mm):
+    def decode(self, stream, n_levels, pos_mm, lod=0):
         """stream: bytes; n_levels: total level count from the file name; pos_mm: [n_levels,2] array from the .dat file.
-        Returns list of (codes_per_level, leaf_points int64 [U,3]) - one entry per shell."""
+        Returns list of (codes_per_level, leaf_points int64 [U,3]) - one entry per shell.  lod = K >= 1 (at most the shallowest shell's
+        depth - 1): every entry gains the origins of the shell's LOD-K cells; the shells of a multi-level stream are coded one after the
+        other, so those before the last are decoded in full (the range decoder has to pass them) and only the last one stops after its
+        level depth - K, its leaves None."""
         dec = native.AcDecoder(stream)
         depths = shell_depths(n_levels, self.mullevel)
+        lod = check_lod(lod, depths)
         out, off = [], 0
         from . import ops
         with native.use_profile(self.profile), ops.frozen_weights():            # (the weights do not change inside a frame: validated once per frame)
-            for d in depths:
-                out.append(self._decode_tree(dec, d, pos_mm[off:off + d] if self.polar else None))
+            for k, d in enumerate(depths):
+                out.append(self._decode_tree(dec, d, pos_mm[off:off + d] if self.polar else None, lod, stop=lod > 0 and k == len(depths) - 1))
                 off += d
         return out
 

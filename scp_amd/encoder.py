@@ -420,6 +420,17 @@ class FrameEncoder(_FrontEnd):
         rep["shell_leaves"] = [int(p.shape[0]) for p in pts]
         return rep
 
+    def _share_args(self):
+        """The arguments of native.rate_leaf_share for the frame whose rows `_rate_rows` holds: the node columns of the geometry, what
+        every node cost (ideal, table), the segment table and the number of leaves."""
+        row_ideal, row_table, plan = self._rate_rows
+        g, dev = self.geom, self.device
+        nd = g.nodes(("occ", "level", "parent"))
+        # coding order -> frame-order row -> node: the rows of the segments lie back to back, a drop_last segment's last node has none
+        node_of_row = torch.cat([torch.arange(int(i.node_base), int(i.node_base) + g.rows(s), device=dev) for s, i in enumerate(g.info)])
+        bits_ideal, bits_table = native.node_bits(plan.coding_order_device(dev), node_of_row, row_ideal, row_table, g.total_nodes)
+        return (nd["occ"], nd["level"], nd["parent"], bits_ideal, bits_table, native.share_table(g.info), sum(int(i.n_leaves) for i in g.info))
+
     def ring_rate(self, xyz_dev, edges=None, infos=None):
         """What every range ring and rho shell of the frame just encoded costs ("Rate per ring"): every node's ideal and
         coded-table bits are handed to the leaves below it in equal parts (csrc/ringrate.hip), and the leaves are summed over the bins of
@@ -436,14 +447,7 @@ class FrameEncoder(_FrontEnd):
             raise native.ScpError("ring_rate: no frame to report on - call it after a synchronous encode / encode_ints (the asynchronous and "
                                   "batch calls, and the record files of --preproc_path, leave no geometry and no rows behind)")
         edges = native.dist_edges(metrics.default_edges(self.data_type) if edges is None else edges)
-        row_ideal, row_table, plan = self._rate_rows
-        g, dev = self.geom, self.device
-        nd = g.nodes(("occ", "level", "parent"))
-        # coding order -> frame-order row -> node: the rows of the segments lie back to back, a drop_last segment's last node has none
-        node_of_row = torch.cat([torch.arange(int(i.node_base), int(i.node_base) + g.rows(s), device=dev) for s, i in enumerate(g.info)])
-        bits_ideal, bits_table = native.node_bits(plan.coding_order_device(dev), node_of_row, row_ideal, row_table, g.total_nodes)
-        share = native.rate_leaf_share(nd["occ"], nd["level"], nd["parent"], bits_ideal, bits_table, native.share_table(g.info),
-                                       sum(int(i.n_leaves) for i in g.info))
+        share = native.rate_leaf_share(*self._share_args())
         pts = self._reconstructed(infos)
         group = torch.cat([torch.full((p.shape[0],), k, dtype=torch.int32, device=p.device) for k, p in enumerate(pts)])
         bins = native.ring_bins(torch.cat(pts), edges, group, len(pts))
@@ -452,6 +456,66 @@ class FrameEncoder(_FrontEnd):
         rep = metrics.ring_rate_dict(edges, raw.cpu().numpy(), points.cpu().tolist(), len(pts))
         rep["shell_leaves"] = [int(p.shape[0]) for p in pts]
         return rep
+
+    def lod_cells(self, k):
+        """The cells of LOD k of the geometry just built, per shell: device int32 [C_s,3] origins in leaf units, in node (Morton) order -
+        the leaves for k = 0, the nodes of level D_s - k + 1 for 1 <= k <= D_s - 1 ("Depth report").  The node origins are
+        checked against `(leaf >> k) << k` of the shell's leaves."""
+        g = self.geom
+        if k == 0:
+            return [g.leaves(s) for s in range(len(g.info))]
+        nd = g.nodes(("level", "pos"))
+        cells = []
+        for s, i in enumerate(g.info):
+            if not 1 <= k <= int(i.depth) - 1:
+                raise native.ScpError(f"lod_cells: LOD {k} of a shell of depth {int(i.depth)}: 0 .. {int(i.depth) - 1} expected")
+            sl = slice(int(i.node_base), int(i.node_base + i.n_nodes))
+            c = nd["pos"][sl][nd["level"][sl] == int(i.depth) - k + 1].contiguous()
+            want = torch.unique_consecutive(torch.bitwise_left_shift(torch.bitwise_right_shift(g.leaves(s), k), k), dim=0)
+            if c.shape != want.shape or not torch.equal(c, want):
+                raise native.ScpError(f"lod_cells: the origins of shell {s}'s level-{int(i.depth) - k + 1} nodes are not (leaf >> {k}) << {k} of its leaves")
+            cells.append(c)
+        return cells
+
+    def depth_report(self, xyz_dev, max_drop=4, edges=None, infos=None):
+        """What every octree level of the frame just encoded costs and buys ("Depth report"): for every truncation depth
+        k = 0 .. max_drop the bits of levels 1 .. D - k per range ring and rho shell (csrc/depthshare.hip: `ring_rate` with every leaf's
+        chain of ancestors cut k levels short, on ring_rate's bins - those of the FINEST reconstructed leaf, so that the columns of
+        different k compare) and the D1 error of the cloud those levels describe: the centres of the level-(D - k + 1) nodes, through the
+        encoder's own dequantiser.  Callable where `ring_rate` is.  max_drop: 0 .. the shallowest shell's depth - 1.  -> plain Python:
+        edges, shell_leaves, shell_depths, levels[k] = dict(drop, cells per shell, rate = the ring_rate form on plane k, distortion =
+        metrics.distortion_report of the LOD-k points against the input with groups = shells, d1 = metrics.chamfer_psnr of the same
+        pair)."""
+        from . import metrics
+        if not (self.rate and self.rate_rows):
+            raise native.ScpError("depth_report needs the per-row bits of the frame: make the encoder with rate=True and rate_rows=True (rate "
+                                  "alone keeps per-level sums only)")
+        if self._rate_rows is None:
+            raise native.ScpError("depth_report: no frame to report on - call it after a synchronous encode / encode_ints (the asynchronous and "
+                                  "batch calls, and the record files of --preproc_path, leave no geometry and no rows behind)")
+        depths = [int(i.depth) for i in self.geom.info]
+        if isinstance(max_drop, bool) or not isinstance(max_drop, int) or not 0 <= max_drop <= min(depths) - 1:
+            raise native.ScpError(f"depth_report: max_drop {max_drop!r} outside 0 .. {min(depths) - 1}: the shells of this frame are {depths} levels "
+                                  "deep and a tree keeps at least its root level")
+        edges = native.dist_edges(metrics.default_edges(self.data_type) if edges is None else edges)
+        share = native.rate_depth_share(*self._share_args(), max_drop)
+        infos = infos or self._infos
+        pts = self._reconstructed(infos)
+        S = len(pts)
+        group = torch.cat([torch.full((p.shape[0],), g, dtype=torch.int32, device=p.device) for g, p in enumerate(pts)])
+        bins = native.ring_bins(torch.cat(pts), edges, group, S)
+        raw = native.share_segments_depth(share["cost_ideal"], share["cost_table"], bins, S * len(edges))["raw"].cpu().numpy()
+        points = torch.bincount(native.ring_bins(xyz_dev[:, :3], edges), minlength=len(edges)).cpu().tolist()
+        peak, cells, dist, d1 = metrics.PEAK.get(self.data_type, 1.0), [], [], []
+        for k in range(max_drop + 1):
+            ck = self.lod_cells(k)
+            pk = [metrics.dequantize(metrics.lod_centres(c, k), info.qs, info.offset, spher=self.spher, cylin=self.cylin,
+                                     f32=not self.mullevel).double() for c, info in zip(ck, infos)]
+            gk = torch.cat([torch.full((p.shape[0],), g, dtype=torch.int32, device=p.device) for g, p in enumerate(pk)])
+            cells.append([int(c.shape[0]) for c in ck])
+            dist.append(metrics.distortion_report(xyz_dev[:, :3], torch.cat(pk), edges, quant_group=gk, n_groups=S))
+            d1.append(metrics.chamfer_psnr(xyz_dev[:, :3], torch.cat(pk), peak))
+        return metrics.depth_dict(edges, raw, points, S, cells, dist, d1, [int(p.shape[0]) for p in pts], depths)
 
     def distortion(self, xyz_dev, infos=None, normals=None):
         """Chamfer distance and D1 PSNR of the frame just encoded (the octree of the last `encode` / `preprocess` call) against

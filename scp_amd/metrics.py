@@ -208,6 +208,38 @@ def ring_rate_dict(edges, raw, points, n_groups=1):
     return dict(edges=edges, groups=groups, rings=rings, total=with_points(_share_total(flat), sum(int(n) for n in points)))
 
 
+def lod_centres(cells_or_leaves, k):
+    """The centres of the LOD-k cells ("Depth report") of integer leaves or cell origins [n,3] (a device or host torch
+    tensor, or a numpy array): origin = (x >> k) << k per axis, centre = origin + (2^k - 1) / 2 in leaf units -> float64 [n,3], exact
+    (half-integers).  One row per input row: leaves of one cell give the same centre.  k = 0: the leaves themselves."""
+    k = int(k)
+    if k < 0 or k > native.MAX_DEPTH:
+        raise native.ScpError(f"lod_centres: k = {k} outside 0 .. {native.MAX_DEPTH}")
+    half = (2 ** k - 1) / 2.0
+    if isinstance(cells_or_leaves, torch.Tensor):
+        x = cells_or_leaves.to(torch.int64)
+        return (torch.bitwise_left_shift(torch.bitwise_right_shift(x, k), k)).to(torch.float64) + half
+    x = np.asarray(cells_or_leaves).astype(np.int64)
+    return ((x >> k) << k).astype(np.float64) + half
+
+
+def depth_dict(edges, raw, points, n_groups, cells, distortion, d1, shell_leaves, shell_depths):
+    """The depth report from its raw parts on the host (no device needed): raw int64 [K + 1, n_groups * R, 4] = the scp_share_seg records
+    of planes k = 0 .. K (native.share_segments_depth(...)["raw"].cpu().numpy()), points = the R counts of input points per ring, and per
+    k: cells (one count per shell), distortion (a metrics.distortion_report dict), d1 (a metrics.chamfer_psnr dict).  -> edges,
+    shell_leaves, shell_depths, levels[k] = dict(drop, cells, rate = ring_rate_dict on plane k, distortion, d1).  Plain Python."""
+    edges = list(native.dist_edges(edges))
+    raw = np.ascontiguousarray(raw, np.int64)
+    K1 = len(cells)
+    if raw.ndim != 3 or raw.shape[0] != K1 or len(distortion) != K1 or len(d1) != K1 or K1 < 1:
+        raise native.ScpError(f"depth report: {raw.shape} records, {len(distortion)} distortion reports and {len(d1)} PSNRs for {K1} depths")
+    if len(shell_leaves) != n_groups or len(shell_depths) != n_groups or any(len(c) != n_groups for c in cells):
+        raise native.ScpError(f"depth report: {len(shell_leaves)} leaf counts, {len(shell_depths)} depths and cell counts {cells} for {n_groups} shells")
+    levels = [dict(drop=k, cells=[int(c) for c in cells[k]], rate=ring_rate_dict(edges, raw[k], points, n_groups), distortion=distortion[k],
+                   d1={name: float(v) for name, v in d1[k].items()}) for k in range(K1)]
+    return dict(edges=edges, shell_leaves=[int(n) for n in shell_leaves], shell_depths=[int(d) for d in shell_depths], levels=levels)
+
+
 def dequantize(leaves, qs, offset, spher=False, cylin=False, f32=False):
     """leaves int [U,3] (device) -> de-quantised Cartesian points [U,3]: `pt * qs + offset` in float64, then spher2cart /
     cylin2cart (data_preprocess.py:186-229).  f32=True: the same-level path rounds to float32 before the inverse transform

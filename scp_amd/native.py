@@ -156,6 +156,9 @@ def lib():
         "scp_rate_leaf_share": (C.c_int, [_vp, _vp, _vp, i64, _vp, _vp, _vp, i32, i64, _vp, _vp, _vp, _vp, i64, _vp]),
         "scp_ring_bins_f64": (C.c_int, [_vp, i64, _vp, _vp, i32, _vp, i32, _vp, _vp, _vp]),
         "scp_share_segments_f64": (C.c_int, [_vp, _vp, _vp, i64, _vp, i32, _vp, _vp]),
+        "scp_rate_depth_share_workspace_bytes": (C.c_int64, [i64, i32]),
+        "scp_rate_depth_share": (C.c_int, [_vp, _vp, _vp, i64, _vp, _vp, _vp, i32, i64, i32, _vp, _vp, _vp, _vp, i64, _vp]),
+        "scp_share_segments_depth_f64": (C.c_int, [_vp, _vp, _vp, i64, _vp, i32, i32, i64, _vp, _vp]),
         "scp_ac_encode_cdf": (C.c_int, [_vp, _vp, i64, i32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "scp_ac_encode_lohi": (C.c_int, [_vp, i64, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "scp_ac_dec_new": (C.c_int, [C.POINTER(_vp), _vp, C.c_size_t, i32]),
@@ -1885,6 +1888,64 @@ def share_record_views(raw):
     """The fields of scp_share_seg records held as int64 [n_bins, 4] (a torch tensor or a numpy array, device or host) -> dict of views."""
     f64 = (lambda c: c.view(torch.float64)) if isinstance(raw, torch.Tensor) else (lambda c: c.view(np.float64))
     return {name: (raw[:, k] if name == "leaves" else f64(raw[:, k])) for k, name in enumerate(SHARE_FIELDS)}
+
+
+# ------------------------------------------------------------------------------------------------- depth report (csrc/depthshare.hip)
+def rate_depth_share(occ, level, parent, bits_ideal, bits_table, segs, total_leaves, max_drop):
+    """scp_rate_depth_share: every leaf's share of the bits of levels 1 .. D - k for k = 0 .. max_drop (include/scp.h states the
+    definition); the arguments of rate_leaf_share plus max_drop (0 .. MAX_DEPTH).  -> dict of device tensors: leaves int64 [N],
+    cost_ideal / cost_table float64 [max_drop + 1, total_leaves] (plane k = cost_k; plane 0 = rate_leaf_share's costs bit for bit; a plane
+    with k >= a segment's depth holds +0.0 there).  A table the library's validation pass objects to raises ScpError (SCP_EINVAL)."""
+    N = int(occ.shape[0])
+    for t, dt, name in ((occ, torch.uint8, "occ"), (level, torch.uint8, "level"), (parent, torch.int32, "parent"),
+                        (bits_ideal, torch.float64, "bits_ideal"), (bits_table, torch.float64, "bits_table")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != (N,):
+            raise ScpError(f"rate_depth_share: {name} is a device tensor of {dt} with one entry per node ({N})")
+    segs = np.ascontiguousarray(segs, np.int64)
+    if segs.ndim != 2 or segs.shape[1] != 4:
+        raise ScpError(f"rate_depth_share: the segment table is int64 [S,4] (node_base, n_nodes, depth, leaf_base), got {segs.shape}")
+    max_drop = int(max_drop)
+    if max_drop < 0 or max_drop > MAX_DEPTH:
+        raise ScpError(f"rate_depth_share: max_drop {max_drop} outside 0 .. {MAX_DEPTH}")
+    S, total_leaves = int(segs.shape[0]), int(total_leaves)
+    ws_bytes = int(lib().scp_rate_depth_share_workspace_bytes(N, S))
+    if ws_bytes < 0:
+        raise ScpError(f"rate_depth_share: {N} nodes in {S} segments: 1 .. 2^30 nodes in 1 .. {MAX_SEGMENTS} segments expected")
+    dev = occ.device
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    leaves = torch.empty(N, dtype=torch.int64, device=dev)
+    ci = torch.empty((max_drop + 1, max(total_leaves, 0)), dtype=torch.float64, device=dev)
+    ct = torch.empty((max_drop + 1, max(total_leaves, 0)), dtype=torch.float64, device=dev)
+    rc = lib().scp_rate_depth_share(_dev(occ), _dev(level), _dev(parent), N, _dev(bits_ideal), _dev(bits_table), segs.ctypes.data, S, total_leaves,
+                                    max_drop, leaves.data_ptr(), ci.data_ptr(), ct.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
+    _check(rc, "scp_rate_depth_share")
+    return dict(leaves=leaves, cost_ideal=ci, cost_table=ct)
+
+
+def share_segments_depth(cost_ideal, cost_table, bins, n_bins):
+    """scp_share_segments_depth_f64: share_segments on every plane of cost_ideal / cost_table [K, n] (rate_depth_share) in one launch; the
+    leaves' bins (int32 [n]) are the same for every plane.  -> dict of device tensors, views of `raw` int64 [K, n_bins, 4]: leaves int64,
+    ideal_bits, table_bits, max_ideal_bits float64 [K, n_bins]; raw[0] is share_segments' raw on plane 0, field for field."""
+    n_bins = int(n_bins)
+    if n_bins < 1 or n_bins > DIST_MAX_BINS:
+        raise ScpError(f"share_segments_depth: between 1 and {DIST_MAX_BINS} bins expected, got {n_bins}")
+    for t, dt, name in ((cost_ideal, torch.float64, "cost_ideal"), (cost_table, torch.float64, "cost_table"), (bins, torch.int32, "bins")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
+            raise ScpError(f"share_segments_depth: {name} is a device tensor of {dt} (there is no CPU path in the product)")
+    if cost_ideal.dim() != 2 or cost_ideal.shape[1] < 1 or cost_table.shape != cost_ideal.shape or tuple(bins.shape) != (cost_ideal.shape[1],):
+        raise ScpError(f"share_segments_depth: cost_ideal [K, n], cost_table [K, n], bins [n] with n >= 1 expected, got {tuple(cost_ideal.shape)}, "
+                       f"{tuple(cost_table.shape)}, {tuple(bins.shape)}")
+    K, n = int(cost_ideal.shape[0]), int(cost_ideal.shape[1])
+    if K < 1 or K > MAX_DEPTH + 1:
+        raise ScpError(f"share_segments_depth: between 1 and {MAX_DEPTH + 1} planes expected, got {K}")
+    cost_ideal, cost_table = cost_ideal.contiguous(), cost_table.contiguous()
+    ordered, order = torch.sort(bins, stable=True)
+    seg_off = torch.searchsorted(ordered, torch.arange(n_bins + 1, dtype=torch.int32, device=bins.device)).to(torch.int64).contiguous()
+    raw = torch.empty((K, n_bins, len(SHARE_FIELDS)), dtype=torch.int64, device=cost_ideal.device)
+    _check(lib().scp_share_segments_depth_f64(cost_ideal.data_ptr(), cost_table.data_ptr(), order.data_ptr(), n, seg_off.data_ptr(), n_bins, K, n,
+                                              raw.data_ptr(), _stream()), "scp_share_segments_depth_f64")
+    views = {name: (raw[..., k] if name == "leaves" else raw[..., k].view(torch.float64)) for k, name in enumerate(SHARE_FIELDS)}
+    return dict(views, raw=raw)
 
 
 # ------------------------------------------------------------------------------------------------- range coder (host)
