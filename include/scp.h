@@ -415,9 +415,10 @@ SCP_API int scp_pmf_cdf(const float *pmf, int64_t n, int32_t nsym, const uint8_t
  *   table_bits = 16 - log2(w), w = (hi ? hi : 65536) - lo          what the 16-bit table of scp_softmax_cdf charges for the symbol
  *   top1       = (x[sym] == m)                                     a tie with the maximum is a hit
  * summed over nseg segments of consecutive rows: seg_off int64 [nseg + 1] (DEVICE), non-decreasing, seg_off[0] = 0, seg_off[nseg] = n
- * (offsets are clamped to [0, n]; a segment may be empty).  A row with w < 1 (no table of this library has one), with sym >= nsym or with
- * a non-finite cross-entropy is counted in bad_rows, contributes 0 to both sums and is written as 0 to row_ideal / row_table; it still
- * counts in rows, and in top1 when its symbol holds the maximum.  No inf / NaN is ever written.
+ * (offsets are clamped to [0, n]; a segment may be empty).  A row with w < 1 (no table of this library has one) or with sym >= nsym is
+ * counted in bad_rows, contributes 0 to both sums and is written as 0 to row_ideal / row_table; a row with a non-finite cross-entropy (the
+ * symbol's logit is -inf) is counted in bad_rows and contributes 0 ideal bits, but keeps the table bits of its pair: the coder spends
+ * them.  A bad row still counts in rows, and in top1 when its symbol holds the maximum.  No inf / NaN is ever written.
  * logits [n][nsym] with row stride ld >= nsym floats, 2 <= nsym <= 256.  With ld == 256 and a 16-byte aligned base the rows are read with
  * 16-byte loads, ALL 256 floats of every row: the last row's columns nsym .. 255 must then be readable memory too (as for scp_softmax_cdf;
  * the encoders' tables are [n][256]).  sym uint8 [n];

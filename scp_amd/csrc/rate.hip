@@ -86,13 +86,15 @@ __global__ __launch_bounds__(256) void rate_rows_kernel(const float *__restrict_
                 ideal = (md - (double)xs + log(sum)) / 0.693147180559945309417232121458;
                 if (xs == m) flag |= RATE_FLAG_TOP1;
             }
-            if (w < 1 || s >= nsym || !(fabs(ideal) <= 1.79769313486231570815e308)) {
-                // a width below one cannot come from this library's tables: counted, kept out of both sums, nothing non-finite written
+            const bool pair_ok = w >= 1 && s < nsym;
+            // Bad rows are counted and nothing non-finite is written.  Two kinds: a pair no table of this library has (width below one, or a
+            // symbol outside the alphabet) stays out of both sums; a non-finite cross-entropy (the symbol's logit is -inf) adds 0 ideal bits,
+            // but its pair is a real table entry of width 1 or more - the coder spends those bits, so the table bits keep them.
+            if (!pair_ok || !(fabs(ideal) <= 1.79769313486231570815e308)) {
                 flag |= RATE_FLAG_BAD;
                 ideal = 0.0;
-            } else {
-                table = 16.0 - log2((double)w);
             }
+            if (pair_ok) table = 16.0 - log2((double)w);
             ws_bits[2 * r] = ideal;
             ws_bits[2 * r + 1] = table;
             ws_flag[r] = (uint8_t)flag;

@@ -65,13 +65,15 @@ def top1(logits, sym):
 
 
 def rows(logits, sym, lohi):
-    """Everything per row: dict(ideal, table, width, top1, bad) - a row whose width is below 1 is `bad` and carries 0 in both columns."""
+    """Everything per row: dict(ideal, table, width, top1, bad) - a row whose width is below 1 is `bad` and carries 0 in both columns; a row
+    whose cross-entropy is not finite (the symbol's logit is -inf) is `bad` with 0 ideal bits, and keeps the table bits of its pair."""
     lo, hi = unpack(lohi)
     w = hi - lo
-    bad = w < 1
-    ideal = np.where(bad, 0.0, ideal_bits(logits, sym))
-    table = np.where(bad, 0.0, 16.0 - np.log2(np.maximum(w, 1).astype(np.float64)))
-    return dict(ideal=ideal, table=table, width=w, top1=top1(logits, sym), bad=bad)
+    with np.errstate(invalid="ignore"):
+        ideal = ideal_bits(logits, sym)
+    table = np.where(w < 1, 0.0, 16.0 - np.log2(np.maximum(w, 1).astype(np.float64)))
+    bad = (w < 1) | ~np.isfinite(ideal)
+    return dict(ideal=np.where(bad, 0.0, ideal), table=table, width=w, top1=top1(logits, sym), bad=bad)
 
 
 def segments(r, seg_off):

@@ -173,6 +173,34 @@ def test_row_chain_entry_points_reject_bad_arguments_without_a_gpu():
     assert L.scp_swin_post_attn(one, one, 256, one, 256, one, one, one, one, 1e-5, one, 256, 300, one, 4, z) == -1  # more listed tiles than the rows hold
 
 
+def test_cdf_entry_points_reject_bad_arguments_without_a_gpu():
+    """scp_softmax_cdf / scp_pmf_cdf: an alphabet outside 2 .. 255, a row stride below the row, pairs without symbols, a NULL input and a
+    negative row count return SCP_EINVAL (-1) before anything is launched; an empty table is fine whatever the pointers are."""
+    from scp_amd import native
+    L = native.lib()
+    z, one = None, 4096            # NULL and a fake (never dereferenced) non-NULL address
+    #                    logits ld  n  nsym sym pmf lohi cdf stream
+    assert L.scp_softmax_cdf(one, 255, 10, 1, one, z, one, z, z) == -1               # nsym 1
+    assert L.scp_softmax_cdf(one, 256, 10, 256, one, z, one, z, z) == -1             # nsym 256
+    assert L.scp_softmax_cdf(one, 300, 10, 0, one, z, one, z, z) == -1
+    assert L.scp_softmax_cdf(one, 254, 10, 255, one, z, one, z, z) == -1             # ld < nsym
+    assert L.scp_softmax_cdf(one, 1, 10, 2, one, z, one, z, z) == -1
+    assert L.scp_softmax_cdf(one, 255, 10, 255, z, z, one, z, z) == -1               # lohi without sym
+    assert L.scp_softmax_cdf(one, 255, 10, 255, z, one, one, one, z) == -1
+    assert L.scp_softmax_cdf(z, 255, 10, 255, one, z, one, z, z) == -1               # logits NULL
+    assert L.scp_softmax_cdf(one, 255, -1, 255, one, z, one, z, z) == -1             # n < 0
+    assert L.scp_softmax_cdf(z, 0, 0, 0, z, z, z, z, z) == 0                         # n == 0: nothing to do, nothing looked at
+    assert L.scp_softmax_cdf(one, 255, 0, 255, z, z, one, z, z) == 0
+    #                pmf  n  nsym sym lohi cdf stream
+    assert L.scp_pmf_cdf(one, 10, 1, one, one, z, z) == -1
+    assert L.scp_pmf_cdf(one, 10, 256, one, one, z, z) == -1
+    assert L.scp_pmf_cdf(one, 10, 255, z, one, z, z) == -1                           # lohi without sym
+    assert L.scp_pmf_cdf(z, 10, 255, one, one, z, z) == -1                           # pmf NULL
+    assert L.scp_pmf_cdf(one, -1, 255, one, one, z, z) == -1
+    assert L.scp_pmf_cdf(z, 0, 0, z, z, z, z) == 0
+    assert L.scp_pmf_cdf(one, 0, 255, z, one, z, z) == 0
+
+
 def test_range_coder_round_trips_under_address_and_ub_sanitizers(tmp_path):
     """csrc/rangecoder.cpp (host code: burst renormalisation, 64-bit bit window, AVX2 symbol search with its verified fallback) built with
     -fsanitize=address,undefined on the CPU and driven through the C ABI: 200 random streams (peaky / flat / tail-heavy tables, 1 - 5 000

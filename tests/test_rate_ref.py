@@ -145,6 +145,22 @@ def test_library_exports_the_rate_entry_points():
     assert L.scp_rate_workspace_bytes(-1, 3) == -1 and L.scp_rate_workspace_bytes(10, -1) == -1
 
 
+def test_a_symbol_with_a_minus_inf_logit_is_bad_yet_keeps_its_table_bits(orc):
+    """An infinite cross-entropy: the row is bad and carries 0 ideal bits, but its pair is the oracle table's entry of width 1 - the 16
+    bits the coder spends stay in the table column, so stream length minus table bits keeps its bound."""
+    x = np.zeros((3, 255), np.float32)
+    x[1, 7] = -np.inf
+    x[2, :200] = -np.inf
+    sym = np.array([7, 7, 254], np.uint8)
+    lo, hi = rate_ref.pairs(rate_ref.softmax_f32(x), sym)
+    r = rate_ref.rows(x, sym, rate_ref.pack(lo, hi))
+    assert r["bad"].tolist() == [False, True, False] and r["width"][1] == 1
+    assert r["ideal"][1] == 0.0 and r["table"][1] == 16.0 and np.isfinite(r["ideal"]).all() and np.isfinite(r["table"]).all()
+    assert abs(r["ideal"][0] - math.log2(255.0)) < 1e-12 and abs(r["ideal"][2] - math.log2(55.0)) < 1e-12
+    stream = orc.ac_encode(orc.pmf_to_cdf(rate_ref.softmax_f32(x)), sym.astype(np.int16))
+    assert 0 < 8 * len(stream) - math.fsum(r["table"]) <= 16
+
+
 def test_rate_segments_rejects_bad_arguments_without_a_gpu():
     """The argument checks come before any HIP call: SCP_EINVAL (-1), nothing launched."""
     L = _lib_or_skip()
