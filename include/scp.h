@@ -436,6 +436,43 @@ SCP_API int scp_rate_segments(const float *logits, int64_t ld, int64_t n, int32_
                               const int64_t *seg_off, int32_t nseg, scp_rate_seg *out, double *row_ideal, double *row_table,
                               void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Per-level temperature (csrc/temper.hip; additive, no new ABI version; DESIGN.md 6, "Temperature").  A scaled logit is
+ * y = fl32(beta * x), ONE float32 multiply; everything below is defined through it.
+ * scp_temper_sweep: for the logits table, symbols and segments of scp_rate_segments (same layout rules, same 16-byte fast path) and a grid
+ * of nt inverse temperatures betas[nt] (HOST float32, 1 <= nt <= SCP_TEMPER_MAX_NT, every one finite and > 0):
+ *   seg_bits float64 [nseg][nt], seg_bad int32 [nseg][nt] (DEVICE): entry (s, j) is what scp_rate_segments writes as ideal_bits / bad_rows
+ *   for segment s of the table whose every element x was replaced by fl32(betas[j] * x) - bit for bit: the same row and segment order,
+ *   through the same device functions (csrc/rate_common.h).  (scp_rate_segments also counts a row whose (c_low, c_high) pair is no table
+ *   entry as bad; no table scp_softmax_cdf writes has one, and the sweep takes no pairs.)  A row whose cross-entropy at beta_j is not
+ *   finite, or whose symbol is outside the alphabet, adds 0 at that j and counts in seg_bad[s][j]; no inf / NaN is ever written.
+ *   row_bits float64 [n][nt], optional (NULL): the rows' own bits.  workspace: device memory, 8-byte aligned,
+ *   scp_temper_workspace_bytes(n, nseg, nt) bytes.  n == 0: SCP_OK, both outputs zero.  The table is read once whatever nt is; the cost is
+ *   the nt * nsym float64 exponentials per row.
+ * scp_temper_choose: group int32 [nseg] (DEVICE; any order; values are clamped to 0 .. ngroup - 1 on the device) assigns every segment to a
+ *   group; unit is the index of the grid's 1.0f (betas[unit] == 1.0f is checked).  Per group and j the group's segments are added in
+ *   segment-index order (float64, serial), and the group's choice is the j with the smallest sum - a tie goes to the index nearest unit,
+ *   then to the lower index.  The group keeps unit when the best sum does not beat the unit sum by MORE than min_gain_bits (>= 0, finite:
+ *   what the group's index costs as side information), when any of its segments has a bad row at any j, or when it has no rows.
+ *   Outputs (DEVICE): choice int32 [ngroup], group_bits float64 [ngroup][2] (the sum at unit, the sum at the choice), seg_beta float32
+ *   [nseg] (every segment's group's chosen beta).  seg_off / n as in the sweep (for the groups' row counts).
+ * scp_scale_rows: out[r][c] = fl32(seg_beta[s] * in[r][c]) for c < nsym and the segment s that holds row r (seg_off int64 [nseg + 1],
+ *   seg_beta float32 [nseg], both DEVICE; empty segments allowed; a row no segment holds is copied).  in / out: n rows of strides ld_in /
+ *   ld_out >= nsym floats; out == in with ld_out == ld_in scales in place and then leaves columns >= nsym alone; otherwise the two must
+ *   not overlap and the columns nsym .. min(ld_in, ld_out) - 1 are copied unchanged.  beta == 1.0f leaves every bit as it was (-inf and
+ *   NaN payloads included: x * 1.0f is x).  With both strides 256 and 16-byte aligned bases the rows are read with 16-byte loads (all 256
+ *   floats readable, as for scp_softmax_cdf).
+ * All three enqueue on `stream` and wait for nothing; argument errors are found on the host before any launch (SCP_EINVAL). */
+#define SCP_TEMPER_MAX_NT 32
+SCP_API int64_t scp_temper_workspace_bytes(int64_t n, int32_t nseg, int32_t nt);   /* bytes, or SCP_EINVAL */
+SCP_API int scp_temper_sweep(const float *logits, int64_t ld, int64_t n, int32_t nsym, const uint8_t *sym, const int64_t *seg_off,
+                             int32_t nseg, const float *betas, int32_t nt, double *seg_bits, int32_t *seg_bad, double *row_bits,
+                             void *workspace, int64_t workspace_bytes, void *stream);
+SCP_API int scp_temper_choose(const double *seg_bits, const int32_t *seg_bad, const int64_t *seg_off, int64_t n, const int32_t *group,
+                              int32_t nseg, int32_t ngroup, const float *betas, int32_t nt, int32_t unit, double min_gain_bits,
+                              int32_t *choice, double *group_bits, float *seg_beta, void *stream);
+SCP_API int scp_scale_rows(const float *in, int64_t ld_in, float *out, int64_t ld_out, int64_t n, int32_t nsym, const int64_t *seg_off,
+                           const float *seg_beta, int32_t nseg, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Range coder (host, serial) - replaces numpyAc/backend/numpyAc_backend.cpp
  *   encode_cdf :327-334 / encode :245-323  ->  scp_ac_encode_cdf, scp_ac_encode_lohi

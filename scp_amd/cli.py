@@ -25,6 +25,11 @@ same stdout block per frame, same summary file.  Differences, all additive:
     error of the cloud those levels describe (the cells of size 2^k, which `decode_ehem.py --lod k` writes): one more line per frame
     (ideal bits per point and D1 PSNR for every k) and a `<stream>.depth.json` next to every stream (tools/rd_depth.py reads it).
     Implies the rate kernels; the streams themselves do not change.
+  * `--temper` (EHEM) / `--temper_report`: one inverse temperature per (octree level, phase) out of a grid of 25, chosen on the frame as the
+    one that costs the fewest ideal bits (csrc/temper.hip) when that saves more than the byte its index costs.  `--temper` codes the
+    scaled rows: the stream's name gains `_temper` in front of the coordinate token and the side-info file the grid and the indices, which
+    `decode_ehem*.py` require for such a name.  `--temper_report` alone leaves the streams as they are.  One more line per frame (ideal
+    bits per point at 1 and as chosen, the side bits, the groups that moved); `--temper_report` also writes `<stream>.temper.json`.
   * `--normals estimate|DIR` (with `--metrics`, EHEM): the D2 (point-to-plane) PSNR as well, on normals estimated on the device or
     read from the `<DIR>/<sequence>/<frame>.ply` files `gene_normals.py` writes; one more line per frame, `PSNR_D2:` in the summary.
 """
@@ -121,6 +126,12 @@ def depth_request(args):
     return (True, DEPTH_REPORT_DEFAULT, None) if v is True else (True, v[0], None if v[1] is None else tuple(v[1]))
 
 
+def temper_request(args):
+    """--temper / --temper_report -> (the encoder's `temper` mode: None, "report" or "code"; whether <stream>.temper.json is written)."""
+    code, rep = getattr(args, "temper", False), getattr(args, "temper_report", False)
+    return ("code" if code else ("report" if rep else None)), bool(rep)
+
+
 def get_args(argv=None, mullevel=False):
     p = argparse.ArgumentParser()
     p.add_argument("--ckpt_path", type=str, default="", help="example: outputs/obj/2023-04-28/10-43-45/ckpt/epoch=7-step=64088.ckpt")
@@ -167,6 +178,15 @@ def get_args(argv=None, mullevel=False):
                         "and the D1 PSNR of the cloud they describe on one more line, and <stream>.depth.json next to the stream with both per "
                         "range ring and rho shell (what decode_ehem*.py --lod k would write); EDGES as for --rate_rings, with the same defaults; "
                         "implies the rate kernels; the streams do not change")
+    # (absent from the namespace unless given, like --rate_report: read them with temper_request(args))
+    p.add_argument("--temper", action="store_true", default=argparse.SUPPRESS,
+                   help="EHEM: code every (octree level, phase) under the inverse temperature - out of a grid of 25 from 0.354 to 2.83 - that "
+                        "costs the fewest ideal bits on this frame, when that saves more than the byte its index costs; the stream's name gains "
+                        "`_temper`, its side-info file the grid and the indices, and decode_ehem*.py reads them; one more line per frame")
+    p.add_argument("--temper_report", action="store_true", default=argparse.SUPPRESS,
+                   help="per frame: what --temper would choose and save in ideal bits, on one more line and in <stream>.temper.json next to the "
+                        "stream with the bits of every group at every grid value; the streams do not change (with --temper: the same report, "
+                        "columns included, of the choice that was coded)")
     p.add_argument("--host_transform", action="store_true",
                    help="strict identity with the reference from the frame on: the coordinate transform + quantiser run in numpy float32 on the "
                         "host exactly as data_preprocess.py:42-70 does (the device transform is more accurate, hence not bit-identical); "
@@ -215,6 +235,9 @@ def refuse_unsupported(args, name, mullevel):
         raise native.ScpError("--metrics is available for the EHEM encoders only")
     if getattr(args, "normals", None) and (name == "OctAttention" or not args.metrics):
         raise native.ScpError("--normals adds the D2 PSNR to --metrics, which the EHEM encoders have: give --metrics as well, with an EHEM model")
+    if temper_request(args)[0] == "code" and name == "OctAttention":
+        raise native.ScpError("--temper is available for the EHEM encoders only: OctAttention's decodable profile decodes one node per step, and "
+                              "a tempered form of it is not part of this library (--temper_report measures what it would save)")
     want_dist, dist_edges = distortion_request(args)
     if want_dist:
         if name == "OctAttention":
@@ -374,6 +397,7 @@ def main(argv=None, mullevel=False):
     name = cfg.model.class_name
     refuse_unsupported(args, name, mullevel)
     rate_report = getattr(args, "rate_report", False)
+    temper, temper_report = temper_request(args)
     want_dist, dist_edges = distortion_request(args)
     want_rings, ring_edges = rings_request(args)
     want_depth, depth_drop, depth_edges = depth_request(args)
@@ -399,11 +423,13 @@ def main(argv=None, mullevel=False):
         mul = mullevel and args.spher and not obj       # encode_dataset_mullevel.py:76: the three-shell form exists for --spher
         enc = OctAttnFrameEncoder(model, args.type, args.lidar_level, spher=args.spher and not obj, cylin=args.cylin and not obj, device=dev,
                                   mullevel=mul, level_wise=args.level_wise and mullevel, named=mullevel,
-                                  host_transform=True if args.host_transform else None, decodable=args.decodable, rate=rate_report)
+                                  host_transform=True if args.host_transform else None, decodable=args.decodable, rate=rate_report, temper=temper)
     else:
         enc = FrameEncoder(model, args.type, args.lidar_level, spher=args.spher, cylin=args.cylin, mullevel=mullevel, device=dev,
                            host_transform=True if args.host_transform else None, rate=rate_report or want_rings or want_depth,
-                           rate_rows=want_rings or want_depth)
+                           rate_rows=want_rings or want_depth, temper=temper)
+    if temper_report:
+        enc.temper_sums = True                 # the columns of <stream>.temper.json, under --temper as well
 
     mine = D.shard(files, rank, world)
     # fast path: frames are enqueued with encode_async (stage G on a side stream, two model lanes, range coder on a worker thread)
@@ -455,6 +481,14 @@ def main(argv=None, mullevel=False):
                 json.dump(dict(rate, model=name, profile=enc.profile_string(), lidar_level=args.lidar_level, bits=res["bits"],
                                n_points=res["n_points"], n_nodes=res["n_nodes"]), f, indent=1)
             rate_sums[0] += rate["bpp_ideal"]; rate_sums[1] += rate["bpp_table"]; rate_sums[2] += res["bpp"]; rate_sums[3] += 1
+        if temper:
+            tp = res["temper"]
+            print("temper bpp unit / chosen, side bits, moved :", tp["ideal_bits_unit"] / res["n_points"], tp["ideal_bits_chosen"] / res["n_points"],
+                  tp["side_bits"], tp["moved"])
+            if temper_report:
+                with open(outfile[:-len(".bin")] + ".temper.json", "w") as f:
+                    json.dump(dict(tp, model=name, profile=enc.profile_string(), lidar_level=args.lidar_level, bits=res["bits"],
+                                   n_points=res["n_points"], n_nodes=res["n_nodes"]), f, indent=1)
         if drep:
             worse = max((drep["a_to_b"]["total"], drep["b_to_a"]["total"]), key=lambda e: e["mse"])     # the direction D1's mseF takes
             share = [worse[k] / worse["mse"] if worse["mse"] > 0 else 0.0 for k in ("mse_r", "mse_phi", "mse_theta")]
@@ -681,7 +715,7 @@ def decode_octattn_main(argv=None):
 
 
 def find_stream(out_root, ori):
-    """The stream the encode CLIs wrote for the original file `ori`: `<stem>[_spher|_cylin]_<levels>_<bin_num>_<z_offset>.bin` with
+    """The stream the encode CLIs wrote for the original file `ori`: `<stem>[_temper][_spher|_cylin]_<levels>_<bin_num>_<z_offset>.bin` with
     stem = `<sequence dir><frame>` for KITTI EHEM runs (encode.py:140-144 via the dataset's file name) or the plain file stem.  The
     reference takes the first name that merely CONTAINS the frame number (decode_ehem.py:206-214), which picks the wrong sequence's
     stream as soon as two sequences hold the same frame number; here the name must match exactly, and 0 or several candidates are
@@ -691,7 +725,7 @@ def find_stream(out_root, ori):
     names = [f for f in os.listdir(out_root) if f.endswith(".bin")]
     tried = []
     for stem in ([p.parent.name + p.stem] if p.parent.name else []) + [p.stem]:
-        pat = re.compile("^" + re.escape(stem) + r"((_spher|_cylin)?_\d+_-?\d+_-?\d+)?\.bin$")
+        pat = re.compile("^" + re.escape(stem) + r"((_temper)?(_spher|_cylin)?_\d+_-?\d+_-?\d+)?\.bin$")
         c = sorted(f for f in names if pat.match(f))
         if len(c) == 1:
             return c[0], stem

@@ -14,44 +14,10 @@
 //            1024 partial sums - a function of the segment's length alone, wherever the segment lies in the table.
 // No floating-point atomics anywhere: a segment's sums are the same bits in every run, for either row stride, alone or inside a batch.
 // The row kernel leaves two float64 and one flag byte per row in the caller's workspace; the segment kernel reads them back.
-#include "scp_internal.h"
+#include "rate_common.h"        // the row and segment contracts as device functions (shared with csrc/temper.hip)
 
-#define RATE_ROWS_PER_BLOCK 4          // a wavefront per row
-#define RATE_SEG_THREADS 1024
 #define RATE_FLAG_TOP1 1
 #define RATE_FLAG_BAD 2
-
-__device__ __forceinline__ double rate_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);      // a + b == b + a: every lane ends with the same bits
-    return v;
-}
-
-__device__ __forceinline__ float rate_wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-// the four columns 4 lane .. 4 lane + 3 of one row; columns >= nsym come back as -inf (they take no part in the maximum and are skipped in the sum)
-template <bool VEC>
-__device__ __forceinline__ float4 rate_load(const float *__restrict__ row, int lane, int nsym) {
-    const int c = 4 * lane;
-    float4 v;
-    if (VEC) {
-        v = *(const float4 *)(row + c);              // ld == 256, 16-byte aligned rows: all 256 floats of the row are the caller's
-        if (c + 1 >= nsym) v.y = -INFINITY;
-        if (c + 2 >= nsym) v.z = -INFINITY;
-        if (c + 3 >= nsym) v.w = -INFINITY;
-        if (c >= nsym) v.x = -INFINITY;
-    } else {
-        v.x = c < nsym ? row[c] : -INFINITY;
-        v.y = c + 1 < nsym ? row[c + 1] : -INFINITY;
-        v.z = c + 2 < nsym ? row[c + 2] : -INFINITY;
-        v.w = c + 3 < nsym ? row[c + 3] : -INFINITY;
-    }
-    return v;
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void rate_rows_kernel(const float *__restrict__ logits, int64_t ld, int64_t n, int nsym,
@@ -68,29 +34,23 @@ __global__ __launch_bounds__(256) void rate_rows_kernel(const float *__restrict_
         if (r + nwave < n) next = rate_load<VEC>(logits + (r + nwave) * ld, lane, nsym);      // the next row is in flight under this row's exponentials
         const int s = (int)sym[r];
         const uint32_t p = lohi[r];
-        const float m = rate_wave_max(fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
+        const float m = rate_row_max(v);
         const double md = (double)m;
-        const int c = 4 * lane;
-        double acc = 0.0;                             // column order inside the lane; a column >= nsym adds nothing
-        if (c < nsym) acc = exp((double)v.x - md);
-        if (c + 1 < nsym) acc += exp((double)v.y - md);
-        if (c + 2 < nsym) acc += exp((double)v.z - md);
-        if (c + 3 < nsym) acc += exp((double)v.w - md);
-        const double sum = rate_wave_sum(acc);
+        const double sum = rate_row_expsum(v, md, lane, nsym);
         if (lane == 0) {
             const int w = (int)((p >> 16) ? (p >> 16) : 65536u) - (int)(p & 0xFFFFu);
             double ideal = 0.0, table = 0.0;
             int flag = 0;
             if (s < nsym) {                           // (a symbol outside the alphabet has no logit to read)
                 const float xs = logits[r * ld + s];
-                ideal = (md - (double)xs + log(sum)) / 0.693147180559945309417232121458;
+                ideal = rate_row_ideal(md, xs, sum);
                 if (xs == m) flag |= RATE_FLAG_TOP1;
             }
             const bool pair_ok = w >= 1 && s < nsym;
             // Bad rows are counted and nothing non-finite is written.  Two kinds: a pair no table of this library has (width below one, or a
             // symbol outside the alphabet) stays out of both sums; a non-finite cross-entropy (the symbol's logit is -inf) adds 0 ideal bits,
             // but its pair is a real table entry of width 1 or more - the coder spends those bits, so the table bits keep them.
-            if (!pair_ok || !(fabs(ideal) <= 1.79769313486231570815e308)) {
+            if (!pair_ok || !rate_finite(ideal)) {
                 flag |= RATE_FLAG_BAD;
                 ideal = 0.0;
             }
@@ -111,10 +71,8 @@ __global__ __launch_bounds__(RATE_SEG_THREADS) void rate_segments_kernel(const d
     __shared__ double s_ideal[RATE_SEG_THREADS], s_table[RATE_SEG_THREADS];
     __shared__ int s_top1[RATE_SEG_THREADS], s_bad[RATE_SEG_THREADS];
     const int t = threadIdx.x;
-    // the offsets live in device memory, so nobody has checked them: clamp to the table
-    int64_t a = seg_off[blockIdx.x], b = seg_off[blockIdx.x + 1];
-    a = a < 0 ? 0 : (a > n ? n : a);
-    b = b < a ? a : (b > n ? n : b);
+    int64_t a, b;
+    rate_seg_bounds(seg_off, blockIdx.x, n, a, b);
     double ideal = 0.0, table = 0.0;
     int top1 = 0, bad = 0;
     for (int64_t i = a + t; i < b; i += RATE_SEG_THREADS) {
@@ -125,16 +83,7 @@ __global__ __launch_bounds__(RATE_SEG_THREADS) void rate_segments_kernel(const d
         bad += (f & RATE_FLAG_BAD) >> 1;
     }
     s_ideal[t] = ideal; s_table[t] = table; s_top1[t] = top1; s_bad[t] = bad;
-    __syncthreads();
-    for (int h = RATE_SEG_THREADS / 2; h >= 1; h >>= 1) {
-        if (t < h) {
-            s_ideal[t] += s_ideal[t + h];
-            s_table[t] += s_table[t + h];
-            s_top1[t] += s_top1[t + h];
-            s_bad[t] += s_bad[t + h];
-        }
-        __syncthreads();
-    }
+    rate_block_tree(t, s_ideal, s_table, s_top1, s_bad);
     if (t == 0) {
         scp_rate_seg o;
         o.rows = b - a;

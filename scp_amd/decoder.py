@@ -51,9 +51,62 @@ def write_sidecar(outfile, enc, res, model_name):
         # and the octree depth the positions are normalised by
         side.update(context_size=int(enc.context_size), level_wise=bool(enc.level_wise), sequential=bool(res.get("sequential", False)),
                     depth=int(res["depth"]) if "depth" in res else None)
+    if getattr(enc, "temper", None) == "code":
+        # a tempered stream ("Temperature"): the grid as float32 bit patterns and one grid index per (level, phase) group in
+        # level order - the side information the decoder scales its rows by
+        t = res["temper"]
+        side["temper"] = dict(betas_u32=[int(b) for b in t["grid_u32"]], index=[int(g["index"]) for g in t["groups"]])
     with open(outfile + SIDECAR, "w") as f:
         json.dump(side, f)
     return side
+
+
+TEMPER_TOKEN = "temper"
+
+
+def is_tempered(binfile):
+    """A stream whose rows were scaled by per-level inverse temperatures says so in its file name: the field `temper` where
+    FrameEncoder.outfile puts it - directly in front of the coordinate token, or of the last three fields of a Cartesian name
+    (`..._temper_spher_<levels>_<bin>_<z>.bin`).  A `temper` field anywhere else belongs to the original file's own name."""
+    fields = os.path.basename(binfile)[:-len(".bin")].split("_")
+    k = len(fields) - 4
+    if k >= 0 and fields[k] in ("spher", "cylin"):
+        k -= 1
+    return k >= 0 and fields[k] == TEMPER_TOKEN
+
+
+def stream_temper(binfile, side, n_levels):
+    """The inverse temperatures of a stream -> None (a plain stream: any `temper` entry of its side-info file is ignored), or float32
+    [2 * n_levels]: the value of group 2 l + p (level l of the file's level list, phase p).  A tempered stream without the table cannot
+    be decoded: refused with the reason."""
+    if not is_tempered(binfile):
+        return None
+    if side is None:
+        raise native.ScpError(f"{binfile}: a tempered stream (`_{TEMPER_TOKEN}_` in its name) without its side-info file ({SIDECAR}), which "
+                              "holds the inverse temperatures the encoder scaled its rows by")
+    t = side.get("temper")
+    if not isinstance(t, dict) or "betas_u32" not in t or "index" not in t:
+        raise native.ScpError(f"{binfile}: a tempered stream whose side-info file has no `temper` entry (betas_u32, index)")
+    def ints(name):
+        v = t[name]
+        if not isinstance(v, list) or not all(isinstance(x, int) and not isinstance(x, bool) for x in v):
+            raise native.ScpError(f"{binfile}: the side-info file's `temper` entry: `{name}` is not a list of integers")
+        return v
+
+    betas, index = ints("betas_u32"), ints("index")
+    if len(index) != 2 * n_levels:
+        raise native.ScpError(f"{binfile}: the side-info file's `temper` entry holds {len(index)} indices, a stream of {n_levels} levels has "
+                              f"{2 * n_levels} (one per level and phase)")
+    if not 1 <= len(betas) <= native.TEMPER_MAX_NT or not all(0 <= b < 2 ** 32 for b in betas):
+        raise native.ScpError(f"{binfile}: the side-info file's `temper` grid holds {len(betas)} values: 1 .. {native.TEMPER_MAX_NT} float32 bit "
+                              "patterns expected")
+    grid = np.array(betas, np.uint32).view(np.float32)
+    if not (np.isfinite(grid).all() and (grid > 0).all()):
+        raise native.ScpError(f"{binfile}: the side-info file's `temper` grid holds a value that is not finite and positive")
+    for i in index:
+        if not 0 <= i < len(grid):
+            raise native.ScpError(f"{binfile}: temper index {i} out of range: the side-info file's grid has {len(grid)} values")
+    return grid[index]
 
 
 def read_sidecar(binfile):
@@ -461,9 +514,10 @@ def _ehem_job(binfile, lidar_level=None, data_type=None, mullevel=False, profile
         bins = side["bin_nums"]
     else:
         bins = [bin_num] + [round((bin_num - 1) * qs[0] / q) + 1 for q in qs[1:]]
+    temper = stream_temper(binfile, side, n_levels)
     with open(binfile, "rb") as f:
         stream = f.read()
-    return dict(name=binfile, stream=stream, side=side, spher=spher, cylin=cylin, polar=spher or cylin, pos_mm=pos_mm, n_levels=n_levels,
+    return dict(name=binfile, stream=stream, side=side, temper=temper, spher=spher, cylin=cylin, polar=spher or cylin, pos_mm=pos_mm, n_levels=n_levels,
                 bin_num=bin_num, z_offset=z_offset, lidar_level=lidar_level, data_type=data_type, mullevel=mullevel, qs=qs, bins=bins)
 
 
@@ -518,7 +572,7 @@ def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False
     and levels_decoded (over all shells: D - K for one tree); `leaves` holds None for the shell that stopped.  lod = 0 is the path without the option."""
     job = _ehem_job(binfile, lidar_level, data_type, mullevel, profile)
     dec = FrameDecoder(model, job["lidar_level"], mullevel=mullevel, polar=job["polar"], device=device, profile=profile)
-    return _ehem_result(job, dec.decode(job["stream"], job["n_levels"], job["pos_mm"], lod), lod)
+    return _ehem_result(job, dec.decode(job["stream"], job["n_levels"], job["pos_mm"], lod, temper=job["temper"]), lod)
 
 
 def shell_depths(n_levels, mullevel):
@@ -701,11 +755,21 @@ class _EhemRounds(_Stamps):
             bases = [b + r for b, r in zip(bases, rows)]
         return out
 
-    def _decode_round(self, decs, steps, ctx, posn, sym, first):
+    def _scale(self, rows, lengths, betas):
+        """A tempered round: the logits rows of consecutive windows (`lengths` rows each) times their windows' inverse temperatures, in place -
+        the encoder's own product (native.scale_rows).  Nothing is launched when every value is 1 (x * 1.0f is x, bit for bit)."""
+        from itertools import accumulate
+        if all(b == 1.0 for b in betas):
+            return
+        native.scale_rows(rows, list(accumulate(lengths, initial=0)), np.asarray(betas, np.float32))
+
+    def _decode_round(self, decs, steps, ctx, posn, sym, first, temper=None):
         """The windows of a round.  decs[col]: the column's range decoder; steps: EhemLockstep.layout's; ctx uint8 [T, 12] (own occupancy =
         255 placeholder) / posn f32 [T, 3]: the round's inputs in window order; the symbols of column col go to sym[first[col]:] (host
         int64: they stay on the host until the round is complete, a step sends only its even symbols up).  Runs the SAME packed kernels as
-        the encoder: encoder and decoder must produce bit-identical integer CDFs.  A window of one node has no phase 2."""
+        the encoder: encoder and decoder must produce bit-identical integer CDFs.  A window of one node has no phase 2.
+        temper: per column the inverse temperatures (phase 1, phase 2) of a tempered stream, (1, 1) for a plain one in the same round; None
+        (no tempered stream in the round) adds nothing."""
         from itertools import accumulate
         from .models.packed import ehem_phase1_packed, ehem_phase2_packed
         cs, model = self.context_size, self.model
@@ -717,7 +781,10 @@ class _EhemRounds(_Stamps):
             plan = self._plan(lengths)
             prob1, st = ehem_phase1_packed(model, ctx[t_row:t_row + ntok], posn[t_row:t_row + ntok], plan)
             t = self._stamp("phase1_model", t)
-            cdf1_dev = native.softmax_cdf(prob1.contiguous(), want_lohi=False, want_cdf=True)["cdf"]
+            prob1 = prob1.contiguous()
+            if temper is not None:
+                self._scale(prob1, [(c + 1) // 2 for c in lengths], [temper[col][0] for st_ in steps[k0:k1] for col, _ in st_])
+            cdf1_dev = native.softmax_cdf(prob1, want_lohi=False, want_cdf=True)["cdf"]
             # the run's query stream + pre_attn_mlp: one packed pass over all windows, launched while the CDF rows travel
             ahead = self.prepare_ahead and max(lengths) > 1
 
@@ -744,11 +811,13 @@ class _EhemRounds(_Stamps):
                     if done is not None:
                         torch.cuda.current_stream(self.device).wait_event(done)
                         done = None
-                    prob2 = ehem_phase2_packed(model, stw, pw, po, prep=pwin)
-                    t = self._stamp("phase2_model", t)
-                    cdf2, _ = self._cdf_to_host(native.softmax_cdf(prob2.contiguous(), want_lohi=False, want_cdf=True)["cdf"], slot=1)
-                    t = self._stamp("cdf_d2h", t)
+                    prob2 = ehem_phase2_packed(model, stw, pw, po, prep=pwin).contiguous()
                     odd = [(col, c) for col, c in grp if c > 1]
+                    if temper is not None:
+                        self._scale(prob2, [c // 2 for _, c in odd], [temper[col][1] for col, _ in odd])
+                    t = self._stamp("phase2_model", t)
+                    cdf2, _ = self._cdf_to_host(native.softmax_cdf(prob2, want_lohi=False, want_cdf=True)["cdf"], slot=1)
+                    t = self._stamp("cdf_d2h", t)
                     ends = list(accumulate((c // 2 for _, c in odd), initial=0))
                     for (col, c), o in zip(odd, self._run_coders(decs, odd, [cdf2[a:b] for a, b in zip(ends, ends[1:])])):
                         r0 = first[col] + k * cs
@@ -769,18 +838,19 @@ class FrameDecoder(_EhemRounds):
         self.mullevel = mullevel
         self.polar = polar            # spherical / cylindrical: positions normalised with the .dat (min, max) pairs
 
-    def _decode_level(self, dec, ctx, pos, n_total):
+    def _decode_level(self, dec, ctx, pos, n_total, temper=None):
         """All windows of one level -> int64 device tensor [n_total]: the symbols of the ctx.shape[0] coded nodes, -1 behind them (the dropped last
         node of a multi-level shell).  ctx uint8 [n, 12], pos f32 [n, 3]."""
         sym = np.full(n_total, -1, np.int64)
         steps = [[(0, c)] for c in window_lengths(ctx.shape[0], self.context_size)]
-        self._decode_round([dec], steps, ctx, pos, sym, [0])
+        self._decode_round([dec], steps, ctx, pos, sym, [0], None if temper is None else [temper])
         return torch.from_numpy(sym).to(self.device)
 
-    def _decode_tree(self, dec, depth, pos_mm, lod=0, stop=False):
+    def _decode_tree(self, dec, depth, pos_mm, lod=0, stop=False, temper=None):
         """One octree: returns (codes per level as device uint8 tensors, leaf integer coordinates [U,3]).  lod = K >= 1: a third entry,
         the origins of the level-(depth - K + 1) nodes (int64 [C,3], leaf units, node order) - what the symbols of level depth - K name;
-        with `stop` the tree ends there (the levels below are not decoded, the leaves are None).
+        with `stop` the tree ends there (the levels below are not decoded, the leaves are None).  temper: float32 [2 * depth], the
+        tree's inverse temperatures (level 1 phase 1, level 1 phase 2, ...) of a tempered stream.
         Level state: pos int32 [n,3] node origins, anc uint8 [n,9] = (level, octant, symbol) of (ggp, gp, p) with pad = (0, 0, 255), octant uint8 [n];
         the children of a decoded level and the model inputs of the level they form come from one launch (native.decode_expand)."""
         dev = self.device
@@ -804,7 +874,8 @@ class FrameDecoder(_EhemRounds):
             last = L == depth
             rows = n - (1 if (self.mullevel and last) else 0)                  # the dropped last node is never coded
             t = self._stamp("tree_expansion", t)
-            sym = self._decode_level(dec, ctx[:rows], posn[:rows], n) if rows > 0 else torch.full((n,), -1, dtype=torch.int64, device=dev)
+            beta = None if temper is None else (float(temper[2 * L - 2]), float(temper[2 * L - 1]))
+            sym = self._decode_level(dec, ctx[:rows], posn[:rows], n, beta) if rows > 0 else torch.full((n,), -1, dtype=torch.int64, device=dev)
             t = self._t0()
             # children in (parent, digit) order; occupancy 1..255, 0 = unknown (dropped node)
             if last:
@@ -820,8 +891,8 @@ class FrameDecoder(_EhemRounds):
             if last:
                 return (codes, pos.long(), cells) if lod else (codes, pos.long())
 
-    def decode(self, stream, n_levels, pos_mm, lod=0):
-        """stream: bytes; n_levels: total level count from the file name; pos_mm: [n_levels,2] array from the .dat file.
+    def decode(self, stream, n_levels, pos_mm, lod=0, temper=None):
+        """stream: bytes; temper: a tempered stream's inverse temperatures (decoder.stream_temper: float32 [2 * n_levels]); n_levels: total level count from the file name; pos_mm: [n_levels,2] array from the .dat file.
         Returns list of (codes_per_level, leaf_points int64 [U,3]) - one entry per shell.  lod = K >= 1 (at most the shallowest shell's
         depth - 1): every entry gains the origins of the shell's LOD-K cells; the shells of a multi-level stream are coded one after the
         other, so those before the last are decoded in full (the range decoder has to pass them) and only the last one stops after its
@@ -833,7 +904,8 @@ class FrameDecoder(_EhemRounds):
         from . import ops
         with native.use_profile(self.profile), ops.frozen_weights():            # (the weights do not change inside a frame: validated once per frame)
             for k, d in enumerate(depths):
-                out.append(self._decode_tree(dec, d, pos_mm[off:off + d] if self.polar else None, lod, stop=lod > 0 and k == len(depths) - 1))
+                out.append(self._decode_tree(dec, d, pos_mm[off:off + d] if self.polar else None, lod, stop=lod > 0 and k == len(depths) - 1,
+                                             temper=None if temper is None else temper[2 * off:2 * (off + d)]))
                 off += d
         return out
 
@@ -949,6 +1021,18 @@ class EhemBatchDecoder(_EhemRounds):
         mm = j["pos_mm"][off:off + d] if j["polar"] else None
         return ehem_level_params(L, d, last_coded_level(d, mm, j["mullevel"], j["polar"]), mm, j["lidar_level"], j["mullevel"], j["polar"])
 
+    def _round_temper(self, info):
+        """Per column of the round the (phase 1, phase 2) inverse temperatures of its stream's current level - every slot has its own table
+        and its own level; a plain stream's are (1, 1) -, or None when no stream in the round is tempered."""
+        if all(self._jobs[r[1]].get("temper") is None for r in info):
+            return None
+        out = []
+        for s, f, tree, L, n, rows in info:
+            tb = self._jobs[f].get("temper")
+            g = 2 * (sum(self._depths[f][:tree]) + L - 1)
+            out.append((1.0, 1.0) if tb is None else (float(tb[g]), float(tb[g + 1])))
+        return out
+
     def _put_roots(self, ctx, posn, roots):
         """roots: [(input row, file, tree)] - the root's context row and normalised origin, as FrameDecoder._decode_tree makes them."""
         if not roots:
@@ -1047,7 +1131,7 @@ class EhemBatchDecoder(_EhemRounds):
                 buf[:] = -1
                 t = self._stamp("tree_expansion", t)
                 if steps:
-                    self._decode_round([decs[r[1]] for r in info], steps, ctx, posn, buf, [int(x) for x in first])
+                    self._decode_round([decs[r[1]] for r in info], steps, ctx, posn, buf, [int(x) for x in first], self._round_temper(info))
                 t = self._t0()
                 sym, cum, m = self._upload_symbols(N, first + ns - 1)
                 cfirst = np.cumsum(m) - m

@@ -144,16 +144,19 @@ def _upload_ints(hq, device):
     return qs
 
 
-def _result(stream, meta, times, debug=None, rate=None):
+def _result(stream, meta, times, debug=None, rate=None, temper=None):
     """The dict every entry point of both encoders returns: the coded stream and its size, the frame's `meta` fields (what the reference
     prints, what its file names and the side-info file carry), the wall times; `_debug` (device tensors) from the synchronous calls only.
-    rate: (host scp_rate_seg records, the frame's levels in `_rate_layout` form) of an encoder made with rate=True -> the `rate` entry."""
+    rate: (host scp_rate_seg records, the frame's levels in `_rate_layout` form) of an encoder made with rate=True -> the `rate` entry.
+    temper: the frame's `temper` entry (`_temper_entry`) of an encoder made with temper="report" / "code"."""
     bits = 8 * len(stream)
     res = dict(bytes=stream, bits=bits, bpp=bits / meta["n_points"], times=times, **meta)
     if debug is not None:
         res["_debug"] = debug
     if rate is not None:
         res["rate"] = _rate_report(rate[0], rate[1], bits, meta["n_points"])
+    if temper is not None:
+        res["temper"] = temper
     return res
 
 
@@ -210,6 +213,51 @@ def _rate_report(raw, levels, bits, n_points):
                 bits_per_node_ideal=total["ideal_bits"] / max(nodes, 1), coder_overhead_bits=bits - total["table_bits"])
 
 
+def _temper_layout(level_sizes, context_size=None):
+    """The groups of the per-level temperature ("Temperature") over `_rate_layout`'s segments: EHEM two per entry of
+    level_sizes, (phase 1, phase 2) in level order - group 2 l + p; an empty phase still counts -, OctAttention (context_size None) one
+    per level.  -> (row offsets of the segments, group of every segment, [(level, phase or None, rows)] per group)."""
+    off, levels = _rate_layout(level_sizes, context_size)
+    group = np.zeros(len(off) - 1, np.int32)
+    meta = []
+    for l, parts in enumerate(levels):
+        for p, idx in enumerate(parts):
+            if idx:
+                group[idx] = len(meta)
+            meta.append((l, p + 1 if len(parts) == 2 else None, int(sum(off[i + 1] - off[i] for i in idx))))
+    return off, group, meta
+
+
+def _temper_groups(raw, info):
+    """The host image of a frame's temperature buffer (`_FrontEnd._temper_launch`) -> one dict per group: level, phase, rows, index,
+    bits_unit, bits_chosen; with the report (`temper_sums`) also `sums`, the group's bits at every grid value - its segments added in segment order in
+    float64, the device's own order."""
+    S, G, nt = info["S"], info["G"], info["nt"]
+    f = raw.view(np.float64)
+    seg_bits, group_bits = f[:S * nt].reshape(S, nt), f[S * nt:S * nt + 2 * G].reshape(G, 2)
+    choice = raw[S * nt + 2 * G:].view(np.int32)[:G]
+    out = []
+    for g, (level, phase, rows) in enumerate(info["meta"]):
+        d = dict(level=level, phase=phase, rows=rows, index=int(choice[g]), bits_unit=float(group_bits[g, 0]), bits_chosen=float(group_bits[g, 1]))
+        if info["sums"]:
+            sums = np.zeros(nt)
+            for i in np.flatnonzero(info["group"] == g):
+                sums = sums + seg_bits[i]
+            d["sums"] = [float(v) for v in sums]
+        out.append(d)
+    return out
+
+
+def _temper_entry(groups, info, level0=0):
+    """The `temper` entry of a result dict from the frame's groups (a batch: its slice of the launch's, its first level `level0`)."""
+    grid = info["grid"]
+    groups = [dict(g, level=g["level"] - level0) for g in groups]
+    return dict(mode=info["mode"], grid=[float(b) for b in grid], grid_u32=[int(b) for b in grid.view(np.uint32)], unit=info["unit"],
+                groups=groups, ideal_bits_unit=math.fsum(g["bits_unit"] for g in groups),
+                ideal_bits_chosen=math.fsum(g["bits_chosen"] for g in groups), side_bits=8 * len(groups),
+                moved=sum(g["index"] != info["unit"] for g in groups))
+
+
 class _CoderPipeline:
     """The asynchronous tail of a frame, shared by both encoders' `*_async` calls: the model part of consecutive frames on alternating
     streams (lanes), the (c_low, c_high) pairs D2H on a copy stream, the serial host range coder on a worker thread (ctypes releases the
@@ -238,12 +286,13 @@ class _CoderPipeline:
         main.wait_stream(caller)
         return main
 
-    def submit(self, main, lohi, fills0, cuts=None, rate=None):
+    def submit(self, main, lohi, fills0, cuts=None, rate=None, temper=None):
         """lohi: the frame's pairs, enqueued on `main` (the last thing of its model part).  -> (future of the coded stream, or - cuts: row
         bounds of the frames of a batch - of the list of every frame's own stream; None).  fills0: native.CACHE_FILLS before the frame began.
         rate: the device records of the frame's rate report (native.rate_segments, enqueued on `main` behind the pairs): they ride to a pinned
         host tensor on the copy stream next to the pairs - no wait on this thread - and that tensor takes the place of the None; it is
-        complete once the future is."""
+        complete once the future is.  temper: the device buffer of the frame's temperature choice (`_temper_launch`), which travels the same
+        way -> third entry."""
         done = torch.cuda.Event()
         done.record(main)
         if native.CACHE_FILLS != fills0:               # device-side caches were built during this call (first frames only):
@@ -258,6 +307,11 @@ class _CoderPipeline:
                 rate_host = torch.empty(rate.shape, dtype=rate.dtype, pin_memory=True)
                 rate_host.copy_(rate, non_blocking=True)
                 rate.record_stream(self.copy_stream)
+            temper_host = None
+            if temper is not None:
+                temper_host = torch.empty(temper.shape, dtype=temper.dtype, pin_memory=True)
+                temper_host.copy_(temper, non_blocking=True)
+                temper.record_stream(self.copy_stream)
             copied = torch.cuda.Event(blocking=True)      # the coder thread SLEEPS until the pairs have landed (a default event spins a core)
             copied.record()
 
@@ -268,7 +322,7 @@ class _CoderPipeline:
                 return native.ac_encode_lohi(h)
             return [native.ac_encode_lohi(h[a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
 
-        return self.pool.submit(work), rate_host
+        return self.pool.submit(work), rate_host, temper_host
 
 
 class _FrontEnd:
@@ -276,8 +330,16 @@ class _FrontEnd:
     device quantiser, and the lazily created coding pipeline of the asynchronous calls."""
     LANES_ENV = None                      # the environment variable that sets the number of lanes (read at the first asynchronous call)
 
-    def __init__(self, model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate=False, rate_rows=False):
+    def __init__(self, model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate=False, rate_rows=False,
+                 temper=None, temper_grid=None):
         self.model = model
+        # per-level temperature (DESIGN.md 6, "Temperature"): None - nothing is launched or allocated; "report" - every result dict gains
+        # `temper`, the stream's bytes stay; "code" - the table is scaled by the chosen inverse temperatures before it is coded
+        if temper not in (None, "report", "code"):
+            raise native.ScpError(f"temper={temper!r}: None, 'report' or 'code' expected")
+        self.temper = temper
+        self.temper_grid, self.temper_unit = native.temper_grid(temper_grid) if temper else (None, None)
+        self.temper_sums = temper == "report"     # every group of `temper` also carries its bits at every grid value (the CLIs' --temper_report)
         self.rate = bool(rate)                # every result dict gains `rate` (one more read of the logits table per frame; the stream's bytes stay)
         # with rate: the synchronous calls keep the per-row bits of their last frame on the device (two float64 per coded row) for
         # FrameEncoder.ring_rate; off, the rate kernels allocate and launch exactly what they did before the option existed
@@ -354,16 +416,52 @@ class _FrontEnd:
         return ((r["raw"], r["keep"], (r["row_ideal"], r["row_table"])) if keep_rows else (r["raw"], r["keep"])), levels
 
 
+    def _temper_launch(self, table, sym_coded, level_sizes):
+        """temper="report" / "code": sweep and choice on the current stream, between the model and the CDF launch; "code" then scales the
+        table in place, so that everything behind this call sees the table that is coded.  -> (device buffer int64: the sweep's segment
+        bits, the groups' bits at unit and at the choice, the choices - one copy brings them to the host -, what the launches use, the
+        layout for `_temper_groups`); None when the option is off."""
+        if not self.temper:
+            return None
+        off, group, meta = _temper_layout(level_sizes, self.context_size if self.RATE_PHASES else None)
+        S, G, nt = len(off) - 1, len(meta), len(self.temper_grid)
+        raw = torch.zeros(S * nt + 2 * G + (G + S * nt + 1) // 2, dtype=torch.int64, device=table.device)
+        ints = raw[S * nt + 2 * G:].view(torch.int32)
+        seg_bits, seg_bad = raw[:S * nt].view(torch.float64).view(S, nt), ints[G:G + S * nt].view(S, nt)
+        sw = native.temper_sweep(table, sym_coded, off, self.temper_grid, out=(seg_bits, seg_bad))
+        ch = native.temper_choose(seg_bits, seg_bad, sw["seg_off"], table.shape[0], group, G, self.temper_grid, self.temper_unit,
+                                  out=(ints[:G], raw[S * nt:S * nt + 2 * G].view(torch.float64).view(G, 2)))
+        if self.temper == "code":
+            native.scale_rows(table, sw["seg_off"], ch["seg_beta"])
+        info = dict(S=S, G=G, nt=nt, meta=meta, group=group, mode=self.temper, grid=self.temper_grid, unit=self.temper_unit,
+                    sums=self.temper_sums)
+        return raw, (sw["keep"], ch["keep"], ch["seg_beta"]), info
+
+    @staticmethod
+    def _temper_result(temper, host=None):
+        """`_temper_launch`'s triple (host: the buffer's pinned image of the asynchronous calls; None: copied here) -> the `temper` entry."""
+        if temper is None:
+            return None
+        raw = temper[0].cpu().numpy() if host is None else host.numpy()
+        return _temper_entry(_temper_groups(raw, temper[2]), temper[2])
+
+    def _temper_token(self, base):
+        """The file-name token of a tempered stream, in front of the coordinate token (decoder.stream_temper looks for it)."""
+        return base + "_temper" if self.temper == "code" else base
+
+
 class FrameEncoder(_FrontEnd):
     LANES_ENV = "SCP_LANES"
     RATE_PHASES = True
 
     def __init__(self, model, data_type=KITTI, lidar_level=12, spher=True, cylin=False, mullevel=False, max_batch=8,
-                 device=None, packed=True, max_tokens=1_000_000, host_transform=None, profile=None, rate=False, rate_rows=False):
+                 device=None, packed=True, max_tokens=1_000_000, host_transform=None, profile=None, rate=False, rate_rows=False,
+                 temper=None, temper_grid=None):
         if mullevel and not (spher or cylin):
             # encode_dataset_ehem_mullevel.py:97-186 has a cylindrical and a spherical branch only
             raise native.ScpError("--mullevel needs --spher or --cylin (the reference has no Cartesian multi-level path)")
-        super().__init__(model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate, rate_rows)
+        super().__init__(model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate, rate_rows,
+                         temper, temper_grid)
         self.profile = profile          # native.NumericProfile of THIS encoder (None: the process default); current around every launch
         self.packed = packed            # one packed forward for all windows (default) vs one forward per group of equal windows
         self.max_tokens = max_tokens
@@ -697,10 +795,11 @@ class FrameEncoder(_FrontEnd):
         main.wait_event(front["ready"])
         with torch.cuda.stream(main):
             table = self.logits_in_coding_order(front["pre"], front["plan"])
+            temper = self._temper_launch(table, front["sym_coded"], front["plan"].level_sizes)
             lohi = native.softmax_cdf(table, front["sym_coded"])["lohi"]
             rate, levels = self._rate_launch(table, front["sym_coded"], lohi, front["plan"].level_sizes)
-        future, rate_host = self._pipeline().submit(main, lohi, fills0, cuts, rate[0] if rate else None)
-        return dict(future=future, t0=t0, front=front, keep=(table, lohi, rate), rate=(rate_host, levels))
+        future, rate_host, temper_host = self._pipeline().submit(main, lohi, fills0, cuts, rate[0] if rate else None, temper[0] if temper else None)
+        return dict(future=future, t0=t0, front=front, keep=(table, lohi, rate, temper), rate=(rate_host, levels), temper=(temper, temper_host))
 
     def encode_async(self, xyz, ints=None, front=None):
         """Like encode(), but the front part runs on the front stream, the model part on the next lane, and the D2H copy of the
@@ -781,14 +880,19 @@ class FrameEncoder(_FrontEnd):
         if rate_host is not None:              # the batch's levels are the frames' level lists one after the other
             cuts = np.concatenate(([0], np.cumsum([len(m["level_sizes"]) for m in metas])))
             rates = [(rate_host.numpy(), levels[a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
-        return [_result(stream, self._meta(m, m["n_nodes"]), dict(total=(time.perf_counter() - h["t0"]) / len(metas)), rate=r)
-                for stream, m, r in zip(streams, metas, rates)]
+        tempers, (temper, temper_host) = [None] * len(metas), h["temper"]
+        if temper is not None:                 # two groups per level, the frames' levels one after the other
+            cuts = np.concatenate(([0], np.cumsum([len(m["level_sizes"]) for m in metas])))
+            groups = _temper_groups(temper_host.numpy(), temper[2])
+            tempers = [_temper_entry(groups[2 * a:2 * b], temper[2], level0=int(a)) for a, b in zip(cuts[:-1], cuts[1:])]
+        return [_result(stream, self._meta(m, m["n_nodes"]), dict(total=(time.perf_counter() - h["t0"]) / len(metas)), rate=r, temper=tp)
+                for stream, m, r, tp in zip(streams, metas, rates, tempers)]
 
     def finish(self, h):
         stream = h["future"].result()
         rate_host, levels = h["rate"]
         return _result(stream, self._meta(h["front"]["pre"], h["front"]["plan"].n_rows), dict(total=time.perf_counter() - h["t0"]),
-                       rate=None if rate_host is None else (rate_host.numpy(), levels))
+                       rate=None if rate_host is None else (rate_host.numpy(), levels), temper=self._temper_result(*h["temper"]))
 
     def _encode_pre(self, pre, t0, timing):
         if timing:
@@ -800,6 +904,7 @@ class FrameEncoder(_FrontEnd):
         if timing:
             torch.cuda.synchronize()
         t2 = time.perf_counter()
+        temper = self._temper_launch(table, sym_coded, plan.level_sizes)
         lohi_dev = native.softmax_cdf(table, sym_coded)["lohi"]
         keep_rows = self.rate and self.rate_rows and pre.get("sym_coded") is not None      # (record files: no geometry to join the rows with)
         rate, levels = self._rate_launch(table, sym_coded, lohi_dev, plan.level_sizes, keep_rows=keep_rows)
@@ -809,10 +914,12 @@ class FrameEncoder(_FrontEnd):
         stream = native.ac_encode_lohi(lohi)
         t4 = time.perf_counter()
         return _result(stream, self._meta(pre, plan.n_rows), dict(geom=t1 - t0, model=t2 - t1, cdf=t3 - t2, coder=t4 - t3, total=t4 - t0),
-                       debug=dict(table=table, sym_coded=sym_coded, pre=pre), rate=rate and (rate[0].cpu().numpy(), levels))
+                       debug=dict(table=table, sym_coded=sym_coded, pre=pre), rate=rate and (rate[0].cpu().numpy(), levels),
+                       temper=self._temper_result(temper))
 
     def outfile(self, base, res):
-        """encode.py:140-144 file name."""
+        """encode.py:140-144 file name; a tempered stream says so in front of the coordinate token (`..._temper_spher_<levels>_<bin>_<z>.bin`)."""
+        base = self._temper_token(base)
         if self.spher:
             base += "_spher"
         elif self.cylin:
@@ -834,7 +941,10 @@ class OctAttnFrameEncoder(_FrontEnd):
     LANES_ENV = "SCP_LANES_OCTATTN"
 
     def __init__(self, model, data_type=KITTI, lidar_level=12, spher=True, cylin=False, max_batch=128, device=None, mullevel=False,
-                 level_wise=False, named=False, host_transform=None, decodable=False, rate=False):
+                 level_wise=False, named=False, host_transform=None, decodable=False, rate=False, temper=None, temper_grid=None):
+        if temper == "code":
+            raise native.ScpError("OctAttention: temper='code' is not available - the decodable profile decodes one node per step, and a "
+                                  "tempered form of it is not part of this library; temper='report' measures what it would save")
         # decodable=True: the octattn/1d numeric profile (models/oct_attention.py) - every PMF row a function of its own window's rows
         # 0..t, so OctAttnFrameDecoder can reproduce it node by node; the default (octattn/1) keeps the round-6 bits
         self.decodable = bool(decodable)
@@ -843,7 +953,8 @@ class OctAttnFrameEncoder(_FrontEnd):
         if mullevel and (cylin or not spher):
             # encode_dataset_mullevel.py:76-86: the three-shell records exist for --spher only
             raise native.ScpError("OctAttention multi-level encoding needs --spher (encode_dataset_mullevel.py:76)")
-        super().__init__(model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate)
+        super().__init__(model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate,
+                         temper=temper, temper_grid=temper_grid)
         self.level_wise = level_wise
         self.named = named or mullevel        # encode_mullevel.py's file-name scheme (also for its single-shell Cartesian input)
 
@@ -1001,16 +1112,17 @@ class OctAttnFrameEncoder(_FrontEnd):
                 self._chunk_rows(chunks, table)
         finally:
             self.model.decodable = prev
+        temper = self._temper_launch(table, sym, [c[2] for c in chunks])
         lohi = native.softmax_cdf(table, sym)["lohi"]
         z_off = float(quant[0]["offset"][2]) if (quant and self.cylin) else 0.0
         meta = dict(n_nodes=N, n_points=n_points, bin_num=bin_num, z_offset=z_off, quant=quant, n_levels=len(chunks), pos_mm=np.zeros((0, 2)),
                     level_sizes=[c[2] for c in chunks], depth=int(self.geom.info[0].depth), sequential=bool(sequential))
         rate, levels = self._rate_launch(table, sym, lohi, meta["level_sizes"])
         if defer:
-            return lohi, meta, (table, sym, chunks), (rate, levels)
+            return lohi, meta, (table, sym, chunks), (rate, levels), temper
         stream = native.ac_encode_lohi(lohi.cpu().numpy())
         return _result(stream, meta, dict(total=time.perf_counter() - t0), debug=dict(table=table, sym_coded=sym),
-                       rate=rate and (rate[0].cpu().numpy(), levels))
+                       rate=rate and (rate[0].cpu().numpy(), levels), temper=self._temper_result(temper))
 
     def encode_async(self, xyz):
         """Like encode(), but stage G runs on the front stream, the model part on the next lane, and the D2H copy of the (c_low, c_high)
@@ -1034,16 +1146,19 @@ class OctAttnFrameEncoder(_FrontEnd):
             ready.record()
         main.wait_event(ready)
         with torch.cuda.stream(main):
-            lohi, meta, keep, (rate, levels) = self.encode_ints(q, bin_num, xyz_dev.shape[0], t0, defer=True, front=front, quant=self.quant_info())
+            lohi, meta, keep, (rate, levels), temper = self.encode_ints(q, bin_num, xyz_dev.shape[0], t0, defer=True, front=front,
+                                                                        quant=self.quant_info())
         # (the handle keeps what the front stream allocated - the frame, its integers, the context sequences - and the table referenced
         # until finish(): see FrameEncoder._model_async)
-        future, rate_host = pipe.submit(main, lohi, fills0, rate=rate[0] if rate else None)
-        return dict(future=future, meta=meta, t0=t0, keep=(keep, lohi, q, xyz_dev, rate), rate=(rate_host, levels))
+        future, rate_host, temper_host = pipe.submit(main, lohi, fills0, rate=rate[0] if rate else None, temper=temper[0] if temper else None)
+        return dict(future=future, meta=meta, t0=t0, keep=(keep, lohi, q, xyz_dev, rate, temper), rate=(rate_host, levels),
+                    temper=(temper, temper_host))
 
     def finish(self, h):
         stream = h["future"].result()
         rate_host, levels = h["rate"]
-        return _result(stream, h["meta"], dict(total=time.perf_counter() - h["t0"]), rate=None if rate_host is None else (rate_host.numpy(), levels))
+        return _result(stream, h["meta"], dict(total=time.perf_counter() - h["t0"]), rate=None if rate_host is None else (rate_host.numpy(), levels),
+                       temper=self._temper_result(*h["temper"]))
 
     def outfile(self, base, res):
         """encode.py:24 (`<base>.bin`) / encode_mullevel.py:68-72 (`<base>[_spher|_cylin]_<chunks>_<bin_num>_0.bin`)."""

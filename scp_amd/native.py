@@ -150,6 +150,10 @@ def lib():
         "scp_pmf_cdf": (C.c_int, [_vp, i64, i32, _vp, _vp, _vp, _vp]),
         "scp_rate_workspace_bytes": (C.c_int64, [i64, i32]),
         "scp_rate_segments": (C.c_int, [_vp, i64, i64, i32, _vp, _vp, _vp, i32, _vp, _vp, _vp, _vp, i64, _vp]),
+        "scp_temper_workspace_bytes": (C.c_int64, [i64, i32, i32]),
+        "scp_temper_sweep": (C.c_int, [_vp, i64, i64, i32, _vp, _vp, i32, _vp, i32, _vp, _vp, _vp, _vp, i64, _vp]),
+        "scp_temper_choose": (C.c_int, [_vp, _vp, _vp, i64, _vp, i32, i32, _vp, i32, i32, C.c_double, _vp, _vp, _vp, _vp]),
+        "scp_scale_rows": (C.c_int, [_vp, i64, _vp, i64, i64, i32, _vp, _vp, i32, _vp]),
         "scp_nn_error_split_f64": (C.c_int, [_vp, i64, _vp, i64, _vp, _vp, i32, _vp, i32, _vp, _vp, _vp, _vp, _vp, _vp]),
         "scp_dist_segments_f64": (C.c_int, [_vp, _vp, _vp, _vp, i64, _vp, i32, _vp, _vp]),
         "scp_rate_leaf_share_workspace_bytes": (C.c_int64, [i64, i32]),
@@ -1675,6 +1679,111 @@ def rate_segments(logits, sym, lohi, seg_off, want_rows=False):
     for k, name in enumerate(RATE_FIELDS):
         out[name] = raw[:, k].view(torch.float64) if name.endswith("_bits") else raw[:, k]
     return out
+
+
+# ------------------------------------------------------------------------------------------------- temperature (csrc/temper.hip)
+TEMPER_MAX_NT = 32                                                         # include/scp.h: SCP_TEMPER_MAX_NT
+TEMPER_MIN_GAIN_BITS = 8.0                                                 # the byte a group's index costs as side information
+
+
+def temper_grid(grid=None):
+    """The grid of inverse temperatures as (numpy float32 [nt], index of its 1.0f).  None: float32(2 ** (j / 8)) for j = -12 .. 12, 25
+    values from 0.354 to 2.83.  A grid holds 1 .. TEMPER_MAX_NT finite positive values, exactly one of them 1.0f."""
+    g = np.array([2.0 ** (j / 8) for j in range(-12, 13)] if grid is None else grid, dtype=np.float64).astype(np.float32).reshape(-1)
+    if not 1 <= g.shape[0] <= TEMPER_MAX_NT:
+        raise ScpError(f"temper grid: {g.shape[0]} values, 1 .. {TEMPER_MAX_NT} expected")
+    if not (np.isfinite(g).all() and (g > 0).all()):
+        raise ScpError("temper grid: every inverse temperature is finite and positive")
+    ones = np.flatnonzero(g == np.float32(1.0))
+    if ones.shape[0] != 1:
+        raise ScpError(f"temper grid: exactly one value is 1.0 (the stream as it is without the option), found {ones.shape[0]}")
+    return np.ascontiguousarray(g), int(ones[0])
+
+
+def _seg_off_dev(seg_off, dev):
+    if isinstance(seg_off, torch.Tensor):
+        return seg_off
+    host = torch.from_numpy(np.ascontiguousarray(seg_off, np.int64))
+    return (host.pin_memory() if torch.cuda.is_available() else host).to(dev, non_blocking=True)
+
+
+def _row_stride(t):
+    n, nsym = t.shape
+    return int(t.stride(0)) if n > 1 else max(int(t.stride(0)), nsym)      # (the stride of a single row says nothing)
+
+
+def temper_sweep(logits, sym, seg_off, betas, want_rows=False, out=None):
+    """scp_temper_sweep: the ideal bits of every segment of a coding-order logits table at every inverse temperature of `betas` (float32
+    values, at most TEMPER_MAX_NT, finite and positive).  logits / sym / seg_off as for rate_segments.  -> dict of device tensors: seg_bits
+    float64 [S,nt], seg_bad int32 [S,nt] (column j = rate_segments' ideal_bits / bad_rows on the table scaled by betas[j], bit for bit),
+    with want_rows row_bits float64 [n,nt]; seg_off (on the device); `keep`: what the launches use.  out: (seg_bits, seg_bad) to write into."""
+    n, nsym = logits.shape
+    if logits.stride(1) != 1:
+        raise ScpError("temper_sweep: unit column stride expected")
+    dev = logits.device
+    seg_off = _seg_off_dev(seg_off, dev)
+    betas = np.ascontiguousarray(betas, np.float32).reshape(-1)
+    S, nt = int(seg_off.shape[0]) - 1, int(betas.shape[0])
+    if S < 0 or sym.shape[0] != n:
+        raise ScpError("temper_sweep: one symbol per row, and at least one offset, expected")
+    ws_bytes = int(lib().scp_temper_workspace_bytes(n, S, nt))
+    if ws_bytes < 0:
+        raise ScpError(f"temper_sweep: a grid of {nt} values: 1 .. {TEMPER_MAX_NT} expected")
+    seg_bits, seg_bad = out if out is not None else (torch.empty((S, nt), dtype=torch.float64, device=dev),
+                                                     torch.empty((S, nt), dtype=torch.int32, device=dev))
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    rows = torch.empty((n, nt), dtype=torch.float64, device=dev) if want_rows else None
+    rc = lib().scp_temper_sweep(logits.data_ptr(), _row_stride(logits), n, nsym, _dev(sym, torch.uint8), _dev(seg_off, torch.int64), S,
+                                betas.ctypes.data, nt, _dev(seg_bits, torch.float64), _dev(seg_bad, torch.int32), _opt(rows), ws.data_ptr(),
+                                ws_bytes, _stream())
+    _check(rc, "scp_temper_sweep")
+    return dict(seg_bits=seg_bits, seg_bad=seg_bad, row_bits=rows, seg_off=seg_off, keep=(ws, seg_off))
+
+
+def temper_choose(seg_bits, seg_bad, seg_off, n, group, ngroup, betas, unit, min_gain_bits=TEMPER_MIN_GAIN_BITS, out=None):
+    """scp_temper_choose: one grid index per group of segments from a sweep's seg_bits / seg_bad (include/scp.h states the rule).  group:
+    int32 [S], the group of every segment (device tensor, or a host sequence - uploaded out of pinned memory, nothing awaited); seg_off: the
+    sweep's device offsets; n: the table's rows.  -> dict of device tensors: choice int32 [G], group_bits float64 [G,2] (at unit, at the
+    choice), seg_beta float32 [S]; `keep`.  out: (choice, group_bits) to write into."""
+    dev = seg_bits.device
+    betas = np.ascontiguousarray(betas, np.float32).reshape(-1)
+    S, nt = seg_bits.shape
+    if not isinstance(group, torch.Tensor):
+        host = torch.from_numpy(np.ascontiguousarray(group, np.int32))
+        group = (host.pin_memory() if torch.cuda.is_available() else host).to(dev, non_blocking=True)
+    if nt != betas.shape[0] or group.shape[0] != S or seg_bad.shape != seg_bits.shape or seg_off.shape[0] != S + 1:
+        raise ScpError("temper_choose: seg_bits / seg_bad [S,nt] of a sweep over this grid, S + 1 offsets and one group per segment expected")
+    choice, group_bits = out if out is not None else (torch.empty(ngroup, dtype=torch.int32, device=dev),
+                                                      torch.empty((ngroup, 2), dtype=torch.float64, device=dev))
+    seg_beta = torch.empty(S, dtype=torch.float32, device=dev)
+    rc = lib().scp_temper_choose(_dev(seg_bits, torch.float64), _dev(seg_bad, torch.int32), _dev(seg_off, torch.int64), n, _dev(group, torch.int32),
+                                 S, ngroup, betas.ctypes.data, nt, unit, float(min_gain_bits), _dev(choice, torch.int32),
+                                 _dev(group_bits, torch.float64), seg_beta.data_ptr(), _stream())
+    _check(rc, "scp_temper_choose")
+    return dict(choice=choice, group_bits=group_bits, seg_beta=seg_beta, keep=(group, seg_off))
+
+
+def scale_rows(table, seg_off, seg_beta, out=None):
+    """scp_scale_rows: out[r, c] = float32(seg_beta[s] * table[r, c]) for the segment s of seg_off that holds row r - one float32 multiply,
+    the arithmetic the encoder and the decoder of a tempered stream share.  table cuda f32 [n,nsym] (row stride allowed); seg_off: S + 1
+    offsets (device int64, or a host sequence), seg_beta float32 [S] (device, or a host sequence).  out None: in place (columns beyond
+    nsym of a strided table are left alone) -> table; else a f32 [n,nsym] tensor that does not overlap it -> out."""
+    n, nsym = table.shape
+    dev = table.device
+    dst = table if out is None else out
+    if table.stride(1) != 1 or dst.stride(1) != 1 or dst.shape != table.shape or dst.dtype != torch.float32 or table.dtype != torch.float32:
+        raise ScpError("scale_rows: float32 tables of one shape with unit column stride expected")
+    seg_off = _seg_off_dev(seg_off, dev)
+    if not isinstance(seg_beta, torch.Tensor):
+        host = torch.from_numpy(np.ascontiguousarray(seg_beta, np.float32))
+        seg_beta = (host.pin_memory() if torch.cuda.is_available() else host).to(dev, non_blocking=True)
+    S = int(seg_off.shape[0]) - 1
+    if S < 0 or seg_beta.shape[0] != S:
+        raise ScpError("scale_rows: S + 1 offsets and S inverse temperatures expected")
+    rc = lib().scp_scale_rows(table.data_ptr(), _row_stride(table), dst.data_ptr(), _row_stride(dst), n, nsym, _dev(seg_off, torch.int64),
+                              _dev(seg_beta, torch.float32), S, _stream())
+    _check(rc, "scp_scale_rows")
+    return dst
 
 
 DIST_MAX_RINGS, DIST_MAX_BINS = 64, 4096                                   # include/scp.h: SCP_DIST_MAX_*
