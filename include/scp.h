@@ -474,6 +474,41 @@ SCP_API int scp_scale_rows(const float *in, int64_t ld_in, float *out, int64_t l
                            const float *seg_beta, int32_t nseg, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Ring LOD (csrc/ringlod.hip; DESIGN.md 6, "Ring LOD"): a truncation depth per range ring, decided on integers only.
+ * A TABLE is nring - 1 thresholds t_0 <= t_1 <= ... (int64, 0 .. 2^31 - 1, on axis 0 of the quantised coordinates) and nring drops
+ * (uint8, 0 .. SCP_RINGLOD_MAX).  The cell of size 2^j around a position x has the origin o = (x >> j) << j per axis, the doubled radial
+ * centre c2 = 2 o[0] + 2^j - 1 (int64) and the ring #{i : c2 >= 2 t_i}; it is TERMINAL iff drops[ring] >= j.
+ * J(x, s) = the largest j in max(s, 1) .. max(drops) whose cell around x is terminal, 0 if there is none (drops need not be monotone).
+ * scp_ringlod_cells: j[r] = J(origins[r], s_r) for n rows of int32 [n][3] (DEVICE), uint8 [n] out (DEVICE).  thresholds [ntab][nring - 1]
+ *   and drops [ntab][nring] are HOST arrays (all tables of a call have nring rings; thresholds may be NULL for nring == 1), segs a HOST
+ *   array of nseg disjoint row ranges.  nseg == 0: every row uses table 0 and s_r = start; level must be NULL.  nseg > 0: a row of
+ *   segment k uses table segs[k].table and s_r = start, or - level (DEVICE uint8 [n], the node's octree level, root = 1) given -
+ *   segs[k].depth - level[r] + 1, the size exponent of a level-L node of a tree of that depth; a row in no segment gets 0.
+ *   snapped (DEVICE int32 [n][3], optional, may be `origins` itself): (x >> j[r]) << j[r] per axis.  workspace: device memory, 8-byte
+ *   aligned, scp_ringlod_workspace_bytes(ntab, nseg) bytes (the tables' device image).  SCP_EINVAL - before anything is written - for
+ *   NULL pointers, n < 0, nring outside 1 .. SCP_RINGLOD_MAX_RINGS, ntab / nseg above SCP_RINGLOD_MAX_TABLES, thresholds that descend,
+ *   are negative or exceed 2^31 - 1, a drop above SCP_RINGLOD_MAX, overlapping or out-of-range segments, a short workspace.
+ * scp_force_rows: for every row r with mask[r] != 0 (DEVICE uint8 [n]) the columns 0 .. nsym - 1 of table row r (f32, row stride ld >=
+ *   nsym) become 0.0f, -1000.0f, -1000.0f, ...; other rows, and columns >= nsym, keep their bits.  scp_softmax_cdf turns such a row into
+ *   (c_low, c_high) = (0, 65536 - nsym + 1) for symbol 0, and it stays one-hot under every scp_scale_rows factor of the temper grid.
+ *   sym (DEVICE uint8 [n]) and mismatch (DEVICE int64 [1]) go together or are both NULL: *mismatch grows by the number of masked rows with
+ *   sym[r] != 0 (integer atomic add; the caller zeroes it).  With ld == 256 and a 16-byte aligned base whole column quads are stored at once.
+ * Both enqueue on `stream` and wait for nothing. */
+#define SCP_RINGLOD_MAX 8
+#define SCP_RINGLOD_MAX_RINGS 32
+#define SCP_RINGLOD_MAX_TABLES 64
+typedef struct scp_ringlod_seg {
+    int64_t first, count;     /* rows first .. first + count - 1 */
+    int32_t depth, table;     /* the tree's depth (read with `level` only), the rows' table */
+} scp_ringlod_seg;
+SCP_API int64_t scp_ringlod_workspace_bytes(int32_t ntab, int32_t nseg);   /* bytes, or SCP_EINVAL */
+SCP_API int scp_ringlod_cells(const int32_t *origins, int64_t n, int32_t start, const uint8_t *level, const scp_ringlod_seg *segs, int32_t nseg,
+                              const int64_t *thresholds, const uint8_t *drops, int32_t ntab, int32_t nring, uint8_t *j, int32_t *snapped,
+                              void *workspace, int64_t workspace_bytes, void *stream);
+SCP_API int scp_force_rows(float *table, int64_t ld, int64_t n, int32_t nsym, const uint8_t *mask, const uint8_t *sym, int64_t *mismatch,
+                           void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Range coder (host, serial) - replaces numpyAc/backend/numpyAc_backend.cpp
  *   encode_cdf :327-334 / encode :245-323  ->  scp_ac_encode_cdf, scp_ac_encode_lohi
  *   class decode :134-217                  ->  scp_ac_dec_*

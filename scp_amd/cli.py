@@ -30,6 +30,11 @@ same stdout block per frame, same summary file.  Differences, all additive:
     scaled rows: the stream's name gains `_temper` in front of the coordinate token and the side-info file the grid and the indices, which
     `decode_ehem*.py` require for such a name.  `--temper_report` alone leaves the streams as they are.  One more line per frame (ideal
     bits per point at 1 and as chosen, the side bits, the groups that moved); `--temper_report` also writes `<stream>.temper.json`.
+  * `--ring_lod EDGES:DROPS` (EHEM, `--spher` / `--cylin`): a truncation depth per range ring - the points of a ring with drop k are snapped
+    to cells of size 2^k before the octree is built, the rows below such a cell are forced to symbol 0 on both sides (csrc/ringlod.hip), and
+    the decoder writes the cells' centres.  The stream's name gains `_ringlod` in front of `_temper` / the coordinate token and the
+    side-info file the drops and the integer thresholds, which `decode_ehem*.py` require for such a name (not with `--lod` / `--streams`).
+    One more line per frame; `--metrics` and the reports then describe the tree that was coded.  All drops 0: the streams of today.
   * `--normals estimate|DIR` (with `--metrics`, EHEM): the D2 (point-to-plane) PSNR as well, on normals estimated on the device or
     read from the `<DIR>/<sequence>/<frame>.ply` files `gene_normals.py` writes; one more line per frame, `PSNR_D2:` in the summary.
 """
@@ -132,6 +137,26 @@ def temper_request(args):
     return ("code" if code else ("report" if rep else None)), bool(rep)
 
 
+def parse_ring_lod(text):
+    """`--ring_lod 0,10,25:2,1,0`: (ring edges in --distortion_report's syntax, one drop per ring) as FrameEncoder(ring_lod=) takes them."""
+    e, sep, d = text.partition(":")
+    try:
+        drops = [int(v) for v in d.split(",")] if sep else None
+    except ValueError:
+        drops = None
+    if drops is None:
+        raise native.ScpError(f"--ring_lod: EDGES:DROPS expected - ring edges from 0 and one integer drop per ring, as in 0,10,25:2,1,0 - got {text!r}")
+    from .encoder import parse_ring_lod as check
+    edges = parse_edges(e, "--ring_lod")
+    check((edges, drops))
+    return edges, tuple(drops)
+
+
+def ring_lod_request(args):
+    """--ring_lod -> the encoder's `ring_lod` argument, None without the flag."""
+    return getattr(args, "ring_lod", None)
+
+
 def get_args(argv=None, mullevel=False):
     p = argparse.ArgumentParser()
     p.add_argument("--ckpt_path", type=str, default="", help="example: outputs/obj/2023-04-28/10-43-45/ckpt/epoch=7-step=64088.ckpt")
@@ -187,6 +212,12 @@ def get_args(argv=None, mullevel=False):
                    help="per frame: what --temper would choose and save in ideal bits, on one more line and in <stream>.temper.json next to the "
                         "stream with the bits of every group at every grid value; the streams do not change (with --temper: the same report, "
                         "columns included, of the choice that was coded)")
+    # (absent from the namespace unless given: read it with ring_lod_request(args))
+    p.add_argument("--ring_lod", type=parse_ring_lod, default=argparse.SUPPRESS, metavar="EDGES:DROPS",
+                   help="EHEM, with --spher or --cylin: every range ring leaves out its own number of octree levels - EDGES as for "
+                        "--distortion_report (the last ring open), DROPS one integer 0 .. 8 per ring, e.g. 0,10,25:2,1,0; the stream's name gains "
+                        "`_ringlod`, its side-info file the drops and the integer thresholds, and decode_ehem*.py writes the centres of the "
+                        "cells; one more line per frame (points snapped per drop, implied rows, leaves)")
     p.add_argument("--host_transform", action="store_true",
                    help="strict identity with the reference from the frame on: the coordinate transform + quantiser run in numpy float32 on the "
                         "host exactly as data_preprocess.py:42-70 does (the device transform is more accurate, hence not bit-identical); "
@@ -238,6 +269,16 @@ def refuse_unsupported(args, name, mullevel):
     if temper_request(args)[0] == "code" and name == "OctAttention":
         raise native.ScpError("--temper is available for the EHEM encoders only: OctAttention's decodable profile decodes one node per step, and "
                               "a tempered form of it is not part of this library (--temper_report measures what it would save)")
+    if ring_lod_request(args) is not None:
+        if name == "OctAttention":
+            raise native.ScpError("--ring_lod is available for the EHEM encoders only: OctAttention's decoder has no forced rows")
+        if args.type == "obj":
+            raise native.ScpError("--ring_lod cuts rings by the range from a LiDAR sensor at the origin: --type obj has none")
+        if not (args.spher or args.cylin):
+            raise native.ScpError("--ring_lod: Cartesian coordinates have no radial axis to cut rings on - encode with --spher or --cylin")
+        if args.preproc_path:
+            raise native.ScpError("--ring_lod with --preproc_path: the record files hold a finished octree, and the option snaps the points "
+                                  "before the tree is built")
     want_dist, dist_edges = distortion_request(args)
     if want_dist:
         if name == "OctAttention":
@@ -427,7 +468,7 @@ def main(argv=None, mullevel=False):
     else:
         enc = FrameEncoder(model, args.type, args.lidar_level, spher=args.spher, cylin=args.cylin, mullevel=mullevel, device=dev,
                            host_transform=True if args.host_transform else None, rate=rate_report or want_rings or want_depth,
-                           rate_rows=want_rings or want_depth, temper=temper)
+                           rate_rows=want_rings or want_depth, temper=temper, ring_lod=ring_lod_request(args))
     if temper_report:
         enc.temper_sums = True                 # the columns of <stream>.temper.json, under --temper as well
 
@@ -489,6 +530,9 @@ def main(argv=None, mullevel=False):
                 with open(outfile[:-len(".bin")] + ".temper.json", "w") as f:
                     json.dump(dict(tp, model=name, profile=enc.profile_string(), lidar_level=args.lidar_level, bits=res["bits"],
                                    n_points=res["n_points"], n_nodes=res["n_nodes"]), f, indent=1)
+        if res.get("ring_lod"):
+            rl = res["ring_lod"]
+            print("ring LOD snapped per drop, implied rows, leaves :", rl["snapped"], rl["implied_rows"], sum(rl["leaves"]))
         if drep:
             worse = max((drep["a_to_b"]["total"], drep["b_to_a"]["total"]), key=lambda e: e["mse"])     # the direction D1's mseF takes
             share = [worse[k] / worse["mse"] if worse["mse"] > 0 else 0.0 for k in ("mse_r", "mse_phi", "mse_theta")]
@@ -715,7 +759,7 @@ def decode_octattn_main(argv=None):
 
 
 def find_stream(out_root, ori):
-    """The stream the encode CLIs wrote for the original file `ori`: `<stem>[_temper][_spher|_cylin]_<levels>_<bin_num>_<z_offset>.bin` with
+    """The stream the encode CLIs wrote for the original file `ori`: `<stem>[_ringlod][_temper][_spher|_cylin]_<levels>_<bin_num>_<z_offset>.bin` with
     stem = `<sequence dir><frame>` for KITTI EHEM runs (encode.py:140-144 via the dataset's file name) or the plain file stem.  The
     reference takes the first name that merely CONTAINS the frame number (decode_ehem.py:206-214), which picks the wrong sequence's
     stream as soon as two sequences hold the same frame number; here the name must match exactly, and 0 or several candidates are
@@ -725,7 +769,7 @@ def find_stream(out_root, ori):
     names = [f for f in os.listdir(out_root) if f.endswith(".bin")]
     tried = []
     for stem in ([p.parent.name + p.stem] if p.parent.name else []) + [p.stem]:
-        pat = re.compile("^" + re.escape(stem) + r"((_temper)?(_spher|_cylin)?_\d+_-?\d+_-?\d+)?\.bin$")
+        pat = re.compile("^" + re.escape(stem) + r"((_ringlod)?(_temper)?(_spher|_cylin)?_\d+_-?\d+_-?\d+)?\.bin$")
         c = sorted(f for f in names if pat.match(f))
         if len(c) == 1:
             return c[0], stem

@@ -56,6 +56,11 @@ def write_sidecar(outfile, enc, res, model_name):
         # level order - the side information the decoder scales its rows by
         t = res["temper"]
         side["temper"] = dict(betas_u32=[int(b) for b in t["grid_u32"]], index=[int(g["index"]) for g in t["groups"]])
+    if getattr(enc, "ring_lod", None) is not None:
+        # a ring-LOD stream ("Ring LOD"): one drop per ring and, per shell, the integer thresholds on the radial axis - the
+        # integers the decoder finds the implied nodes and the cell sizes with (the ring edges in metres are not part of the rule)
+        r = res["ring_lod"]
+        side["ring_lod"] = dict(drops=[int(d) for d in r["drops"]], thresholds=[[int(t) for t in shell] for shell in r["thresholds"]])
     with open(outfile + SIDECAR, "w") as f:
         json.dump(side, f)
     return side
@@ -107,6 +112,61 @@ def stream_temper(binfile, side, n_levels):
         if not 0 <= i < len(grid):
             raise native.ScpError(f"{binfile}: temper index {i} out of range: the side-info file's grid has {len(grid)} values")
     return grid[index]
+
+
+RINGLOD_TOKEN = "ringlod"
+
+
+def is_ringlod(binfile):
+    """A stream coded with a truncation depth per range ring says so in its file name: the field `ringlod` where FrameEncoder.outfile
+    puts it - in front of `temper` (if there), which stands in front of the coordinate token
+    (`..._ringlod[_temper]_spher_<levels>_<bin>_<z>.bin`).  A `ringlod` field anywhere else belongs to the original file's own name."""
+    fields = os.path.basename(binfile)[:-len(".bin")].split("_")
+    k = len(fields) - 4
+    if k >= 0 and fields[k] in ("spher", "cylin"):
+        k -= 1
+    if k >= 0 and fields[k] == TEMPER_TOKEN:
+        k -= 1
+    return k >= 0 and fields[k] == RINGLOD_TOKEN
+
+
+def stream_ringlod(binfile, side, n_levels, mullevel):
+    """The ring-LOD table of a stream -> None (a name without the field: any `ring_lod` entry of its side-info file is ignored), or
+    dict(drops tuple, thresholds: one tuple per shell).  A ring-LOD stream without a well-formed table cannot be decoded - the decoder
+    would not know which rows are implied -: refused with the reason, before anything is decoded."""
+    if not is_ringlod(binfile):
+        return None
+    if side is None:
+        raise native.ScpError(f"{binfile}: a ring-LOD stream (`_{RINGLOD_TOKEN}_` in its name) without its side-info file ({SIDECAR}), which "
+                              "holds the drops and the integer thresholds the encoder cut its rings with")
+    t = side.get("ring_lod")
+    if not isinstance(t, dict) or "drops" not in t or "thresholds" not in t:
+        raise native.ScpError(f"{binfile}: a ring-LOD stream whose side-info file has no `ring_lod` entry (drops, thresholds)")
+
+    def ints(v, name):
+        if not isinstance(v, list) or not all(isinstance(x, int) and not isinstance(x, bool) for x in v):
+            raise native.ScpError(f"{binfile}: the side-info file's `ring_lod` entry: `{name}` is not a list of integers")
+        return v
+
+    drops, shells = ints(t["drops"], "drops"), t["thresholds"]
+    depths = shell_depths(n_levels, mullevel)
+    if not isinstance(shells, list) or len(shells) != len(depths):
+        raise native.ScpError(f"{binfile}: the side-info file's `ring_lod` entry holds the thresholds of "
+                              f"{len(shells) if isinstance(shells, list) else 'no'} shells, the stream has {len(depths)}")
+    if not 1 <= len(drops) <= native.RINGLOD_MAX_RINGS:
+        raise native.ScpError(f"{binfile}: the side-info file's `ring_lod` entry holds {len(drops)} drops: 1 .. {native.RINGLOD_MAX_RINGS} rings expected")
+    for s, thr in enumerate(shells):
+        ints(thr, f"thresholds[{s}]")
+        if len(thr) != len(drops) - 1:
+            raise native.ScpError(f"{binfile}: the side-info file's `ring_lod` entry holds {len(drops)} drops for the {len(thr)} thresholds of "
+                                  f"shell {s}: one more drop than thresholds expected")
+        if any(not 0 <= x <= 2 ** 31 - 1 for x in thr) or any(b < a for a, b in zip(thr, thr[1:])):
+            raise native.ScpError(f"{binfile}: the side-info file's `ring_lod` thresholds of shell {s} are negative, beyond 2^31 - 1 or descending: {thr}")
+    top = min(native.RINGLOD_MAX, min(depths) - 1)
+    for d in drops:
+        if not 0 <= d <= top:
+            raise native.ScpError(f"{binfile}: ring-LOD drop {d} out of range: 0 .. {top} for shells {depths} levels deep")
+    return dict(drops=tuple(drops), thresholds=[tuple(thr) for thr in shells])
 
 
 def read_sidecar(binfile):
@@ -515,9 +575,10 @@ def _ehem_job(binfile, lidar_level=None, data_type=None, mullevel=False, profile
     else:
         bins = [bin_num] + [round((bin_num - 1) * qs[0] / q) + 1 for q in qs[1:]]
     temper = stream_temper(binfile, side, n_levels)
+    ring_lod = stream_ringlod(binfile, side, n_levels, mullevel)
     with open(binfile, "rb") as f:
         stream = f.read()
-    return dict(name=binfile, stream=stream, side=side, temper=temper, spher=spher, cylin=cylin, polar=spher or cylin, pos_mm=pos_mm, n_levels=n_levels,
+    return dict(name=binfile, stream=stream, side=side, temper=temper, ring_lod=ring_lod, spher=spher, cylin=cylin, polar=spher or cylin, pos_mm=pos_mm, n_levels=n_levels,
                 bin_num=bin_num, z_offset=z_offset, lidar_level=lidar_level, data_type=data_type, mullevel=mullevel, qs=qs, bins=bins)
 
 
@@ -540,6 +601,12 @@ def _ehem_result(job, shells, lod=0):
     the dict gains lod, cells (per shell) and levels_decoded (the levels of all shells that were decoded)."""
     binfile, side, spher, cylin, data_type = job["name"], job["side"], job["spher"], job["cylin"], job["data_type"]
     full = shells
+    ring = job.get("ring_lod") is not None
+    if ring:
+        # a ring-LOD stream: the shells carry J(leaf, 0) as a third entry - every leaf is the origin of a terminal cell of size 2^j (j = 0:
+        # the leaf itself), and the point written is the cell's centre, origin + (2^j - 1) / 2 per axis (exact in float64)
+        shells = [(c, lv.to(torch.float64) + ((torch.bitwise_left_shift(torch.ones_like(j, dtype=torch.int64), j.long()) - 1).to(torch.float64) / 2)[:, None])
+                  for c, lv, j in full]
     if lod:
         from . import metrics
         shells = [(c, metrics.lod_centres(cells, lod)) for c, _, cells in full]
@@ -558,7 +625,16 @@ def _ehem_result(job, shells, lod=0):
                lidar_level=job["lidar_level"])
     if lod:
         out.update(leaves=[lv for _, lv, _ in full], lod=lod, cells=[cells for _, _, cells in full], levels_decoded=sum(len(c) for c, _, _ in full))
+    if ring:
+        out.update(leaves=[lv for _, lv, _ in full], cell_j=[j for _, _, j in full], ring_lod=job["ring_lod"])
     return out
+
+
+def _refuse_ringlod_mode(job, what):
+    """--lod / --streams on a ring-LOD stream: refused with the reason (plain and tempered files in those modes are unaffected)."""
+    if job.get("ring_lod") is not None:
+        raise native.ScpError(f"{job['name']}: a ring-LOD stream with {what}: its cells have mixed sizes already, and the lockstep driver and "
+                              "previews of such trees are not part of this library - decode it alone, in full (--streams 1, --lod 0)")
 
 
 def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False, device=None, profile=None, lod=0):
@@ -571,8 +647,10 @@ def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False
     full, since the range decoder has to pass them, and stops the last one early.  The dict gains lod, cells (int64 origins per shell)
     and levels_decoded (over all shells: D - K for one tree); `leaves` holds None for the shell that stopped.  lod = 0 is the path without the option."""
     job = _ehem_job(binfile, lidar_level, data_type, mullevel, profile)
+    if lod:
+        _refuse_ringlod_mode(job, f"--lod {lod}")
     dec = FrameDecoder(model, job["lidar_level"], mullevel=mullevel, polar=job["polar"], device=device, profile=profile)
-    return _ehem_result(job, dec.decode(job["stream"], job["n_levels"], job["pos_mm"], lod, temper=job["temper"]), lod)
+    return _ehem_result(job, dec.decode(job["stream"], job["n_levels"], job["pos_mm"], lod, temper=job["temper"], ring_lod=job["ring_lod"]), lod)
 
 
 def shell_depths(n_levels, mullevel):
@@ -763,13 +841,29 @@ class _EhemRounds(_Stamps):
             return
         native.scale_rows(rows, list(accumulate(lengths, initial=0)), np.asarray(betas, np.float32))
 
-    def _decode_round(self, decs, steps, ctx, posn, sym, first, temper=None):
+    def _force(self, rows, implied, row0, lengths, odd):
+        """A ring-LOD round: the logits rows of the implied nodes become the encoder's forced row (native.force_rows), in place.  rows: the
+        phase-1 (odd False) or phase-2 rows of consecutive windows of `lengths` nodes whose first input row is row0; implied: the round's
+        mask in the row order of `ctx` - a window's phase-1 rows are its nodes 0, 2, .., its phase-2 rows its nodes 1, 3, .."""
+        idx, o = [], row0
+        for c in lengths:
+            idx.append(np.arange(o + (1 if odd else 0), o + c, 2, dtype=np.int64))
+            o += c
+        idx = np.concatenate(idx) if idx else np.zeros(0, np.int64)
+        if idx.shape[0] > rows.shape[0]:
+            raise native.ScpError(f"ring LOD: {rows.shape[0]} logits rows for {idx.shape[0]} nodes of the round")
+        if idx.shape[0]:
+            native.force_rows(rows[:idx.shape[0]], implied[torch.from_numpy(idx).to(self.device)].contiguous())
+
+    def _decode_round(self, decs, steps, ctx, posn, sym, first, temper=None, implied=None):
         """The windows of a round.  decs[col]: the column's range decoder; steps: EhemLockstep.layout's; ctx uint8 [T, 12] (own occupancy =
         255 placeholder) / posn f32 [T, 3]: the round's inputs in window order; the symbols of column col go to sym[first[col]:] (host
         int64: they stay on the host until the round is complete, a step sends only its even symbols up).  Runs the SAME packed kernels as
         the encoder: encoder and decoder must produce bit-identical integer CDFs.  A window of one node has no phase 2.
         temper: per column the inverse temperatures (phase 1, phase 2) of a tempered stream, (1, 1) for a plain one in the same round; None
-        (no tempered stream in the round) adds nothing."""
+        (no tempered stream in the round) adds nothing.
+        implied: uint8 device mask [T] in the row order of `ctx` - the implied nodes of a ring-LOD stream, whose phase-1 and phase-2 rows
+        are forced before anything else reads them; the range decoder then returns symbol 0 for them by itself.  None adds nothing."""
         from itertools import accumulate
         from .models.packed import ehem_phase1_packed, ehem_phase2_packed
         cs, model = self.context_size, self.model
@@ -782,6 +876,8 @@ class _EhemRounds(_Stamps):
             prob1, st = ehem_phase1_packed(model, ctx[t_row:t_row + ntok], posn[t_row:t_row + ntok], plan)
             t = self._stamp("phase1_model", t)
             prob1 = prob1.contiguous()
+            if implied is not None:
+                self._force(prob1, implied, t_row, lengths, odd=False)
             if temper is not None:
                 self._scale(prob1, [(c + 1) // 2 for c in lengths], [temper[col][0] for st_ in steps[k0:k1] for col, _ in st_])
             cdf1_dev = native.softmax_cdf(prob1, want_lohi=False, want_cdf=True)["cdf"]
@@ -794,9 +890,10 @@ class _EhemRounds(_Stamps):
 
             cdf1, (done, views) = self._cdf_to_host(cdf1_dev, then)
             t = self._stamp("cdf_d2h", t)
-            e0 = 0
+            e0, step_row = 0, t_row
             for k, (stw, pwin, qps) in zip(range(k0, k1), views):
                 grp = steps[k]
+                row0, step_row = step_row, step_row + sum(c for _, c in grp)          # the step's first input row
                 ends = list(accumulate(((c + 1) // 2 for _, c in grp), initial=e0))
                 evens = self._run_coders(decs, grp, [cdf1[a:b] for a, b in zip(ends, ends[1:])])
                 e0 = ends[-1]
@@ -813,6 +910,8 @@ class _EhemRounds(_Stamps):
                         done = None
                     prob2 = ehem_phase2_packed(model, stw, pw, po, prep=pwin).contiguous()
                     odd = [(col, c) for col, c in grp if c > 1]
+                    if implied is not None:
+                        self._force(prob2, implied, row0, [c for _, c in grp], odd=True)
                     if temper is not None:
                         self._scale(prob2, [c // 2 for _, c in odd], [temper[col][1] for col, _ in odd])
                     t = self._stamp("phase2_model", t)
@@ -838,19 +937,21 @@ class FrameDecoder(_EhemRounds):
         self.mullevel = mullevel
         self.polar = polar            # spherical / cylindrical: positions normalised with the .dat (min, max) pairs
 
-    def _decode_level(self, dec, ctx, pos, n_total, temper=None):
+    def _decode_level(self, dec, ctx, pos, n_total, temper=None, implied=None):
         """All windows of one level -> int64 device tensor [n_total]: the symbols of the ctx.shape[0] coded nodes, -1 behind them (the dropped last
-        node of a multi-level shell).  ctx uint8 [n, 12], pos f32 [n, 3]."""
+        node of a multi-level shell).  ctx uint8 [n, 12], pos f32 [n, 3]; implied: the level's ring-LOD mask, uint8 [n], or None."""
         sym = np.full(n_total, -1, np.int64)
         steps = [[(0, c)] for c in window_lengths(ctx.shape[0], self.context_size)]
-        self._decode_round([dec], steps, ctx, pos, sym, [0], None if temper is None else [temper])
+        self._decode_round([dec], steps, ctx, pos, sym, [0], None if temper is None else [temper], implied)
         return torch.from_numpy(sym).to(self.device)
 
-    def _decode_tree(self, dec, depth, pos_mm, lod=0, stop=False, temper=None):
+    def _decode_tree(self, dec, depth, pos_mm, lod=0, stop=False, temper=None, ring=None):
         """One octree: returns (codes per level as device uint8 tensors, leaf integer coordinates [U,3]).  lod = K >= 1: a third entry,
         the origins of the level-(depth - K + 1) nodes (int64 [C,3], leaf units, node order) - what the symbols of level depth - K name;
         with `stop` the tree ends there (the levels below are not decoded, the leaves are None).  temper: float32 [2 * depth], the
-        tree's inverse temperatures (level 1 phase 1, level 1 phase 2, ...) of a tempered stream.
+        tree's inverse temperatures (level 1 phase 1, level 1 phase 2, ...) of a tempered stream.  ring: (thresholds, drops) of this tree
+        in a ring-LOD stream - the nodes of level L with J(origin, depth - L + 1) > 0 are implied and their rows forced; a third entry,
+        J(leaf, 0) uint8 [U], says how large the cell is that every leaf stands for.
         Level state: pos int32 [n,3] node origins, anc uint8 [n,9] = (level, octant, symbol) of (ggp, gp, p) with pad = (0, 0, 255), octant uint8 [n];
         the children of a decoded level and the model inputs of the level they form come from one launch (native.decode_expand)."""
         dev = self.device
@@ -875,7 +976,10 @@ class FrameDecoder(_EhemRounds):
             rows = n - (1 if (self.mullevel and last) else 0)                  # the dropped last node is never coded
             t = self._stamp("tree_expansion", t)
             beta = None if temper is None else (float(temper[2 * L - 2]), float(temper[2 * L - 1]))
-            sym = self._decode_level(dec, ctx[:rows], posn[:rows], n, beta) if rows > 0 else torch.full((n,), -1, dtype=torch.int64, device=dev)
+            implied = None
+            if ring is not None and rows > 0 and depth - L + 1 <= max(ring[1]):       # (a node larger than every terminal cell is never implied)
+                implied = native.ringlod_cells(pos[:rows], ring[0], ring[1], start=depth - L + 1).clamp_(max=1)
+            sym = self._decode_level(dec, ctx[:rows], posn[:rows], n, beta, implied) if rows > 0 else torch.full((n,), -1, dtype=torch.int64, device=dev)
             t = self._t0()
             # children in (parent, digit) order; occupancy 1..255, 0 = unknown (dropped node)
             if last:
@@ -889,9 +993,11 @@ class FrameDecoder(_EhemRounds):
                 if stop:
                     return codes, None, cells
             if last:
+                if ring is not None:
+                    return codes, pos.long(), native.ringlod_cells(pos, ring[0], ring[1])
                 return (codes, pos.long(), cells) if lod else (codes, pos.long())
 
-    def decode(self, stream, n_levels, pos_mm, lod=0, temper=None):
+    def decode(self, stream, n_levels, pos_mm, lod=0, temper=None, ring_lod=None):
         """stream: bytes; temper: a tempered stream's inverse temperatures (decoder.stream_temper: float32 [2 * n_levels]); n_levels: total level count from the file name; pos_mm: [n_levels,2] array from the .dat file.
         Returns list of (codes_per_level, leaf_points int64 [U,3]) - one entry per shell.  lod = K >= 1 (at most the shallowest shell's
         depth - 1): every entry gains the origins of the shell's LOD-K cells; the shells of a multi-level stream are coded one after the
@@ -900,12 +1006,15 @@ class FrameDecoder(_EhemRounds):
         dec = native.AcDecoder(stream)
         depths = shell_depths(n_levels, self.mullevel)
         lod = check_lod(lod, depths)
+        if ring_lod is not None and lod:
+            raise native.ScpError("a ring-LOD stream has no --lod preview: its cells have mixed sizes already")
         out, off = [], 0
         from . import ops
         with native.use_profile(self.profile), ops.frozen_weights():            # (the weights do not change inside a frame: validated once per frame)
             for k, d in enumerate(depths):
                 out.append(self._decode_tree(dec, d, pos_mm[off:off + d] if self.polar else None, lod, stop=lod > 0 and k == len(depths) - 1,
-                                             temper=None if temper is None else temper[2 * off:2 * (off + d)]))
+                                             temper=None if temper is None else temper[2 * off:2 * (off + d)],
+                                             ring=None if ring_lod is None else (ring_lod["thresholds"][k], ring_lod["drops"])))
                 off += d
         return out
 
@@ -1172,6 +1281,7 @@ def decode_files(binfiles, model, streams=1, lidar_level=None, data_type=None, m
         raise native.ScpError("decode_files: 1 .. 64 streams expected")
     jobs = [_ehem_job(str(b), lidar_level, data_type, mullevel, profile) for b in binfiles]
     for j in jobs:
+        _refuse_ringlod_mode(j, "--streams (the lockstep decoder)")
         if j["data_type"] == "obj" and not (j["side"] or {}).get("quant"):
             raise _obj_without_quant(j["name"])                               # decode_file's refusal, before anything is decoded
     if not jobs:

@@ -144,11 +144,12 @@ def _upload_ints(hq, device):
     return qs
 
 
-def _result(stream, meta, times, debug=None, rate=None, temper=None):
+def _result(stream, meta, times, debug=None, rate=None, temper=None, ring_lod=None):
     """The dict every entry point of both encoders returns: the coded stream and its size, the frame's `meta` fields (what the reference
     prints, what its file names and the side-info file carry), the wall times; `_debug` (device tensors) from the synchronous calls only.
     rate: (host scp_rate_seg records, the frame's levels in `_rate_layout` form) of an encoder made with rate=True -> the `rate` entry.
-    temper: the frame's `temper` entry (`_temper_entry`) of an encoder made with temper="report" / "code"."""
+    temper: the frame's `temper` entry (`_temper_entry`) of an encoder made with temper="report" / "code".
+    ring_lod: the frame's `ring_lod` entry (`FrameEncoder._ring_entries`) of an encoder made with ring_lod=(edges, drops)."""
     bits = 8 * len(stream)
     res = dict(bytes=stream, bits=bits, bpp=bits / meta["n_points"], times=times, **meta)
     if debug is not None:
@@ -157,7 +158,35 @@ def _result(stream, meta, times, debug=None, rate=None, temper=None):
         res["rate"] = _rate_report(rate[0], rate[1], bits, meta["n_points"])
     if temper is not None:
         res["temper"] = temper
+    if ring_lod is not None:
+        res["ring_lod"] = ring_lod
     return res
+
+
+def parse_ring_lod(ring_lod):
+    """The `ring_lod` argument of FrameEncoder, (ring edges, one drop per ring) -> (edges, drops) as tuples, or None when the option is
+    off: None, or every drop 0 ("Ring LOD").  Edges in native.dist_edges' form - ascending from 0, the last ring open -,
+    at most native.RINGLOD_MAX_RINGS of them; drops: integers 0 .. native.RINGLOD_MAX.  Anything else is refused with the reason."""
+    if ring_lod is None:
+        return None
+    try:
+        edges, drops = ring_lod
+        drops = list(drops)
+    except (TypeError, ValueError):
+        raise native.ScpError(f"ring_lod: (ring edges, one drop per ring) expected, got {ring_lod!r}")
+    try:
+        edges = native.dist_edges(edges)
+    except native.ScpError as e:
+        raise native.ScpError(f"ring_lod: the ring edges are not ascending from 0 ({e})")
+    if len(edges) > native.RINGLOD_MAX_RINGS:
+        raise native.ScpError(f"ring_lod: {len(edges)} rings, at most {native.RINGLOD_MAX_RINGS} expected")
+    if len(drops) != len(edges):
+        raise native.ScpError(f"ring_lod: {len(drops)} drops for {len(edges)} rings (the edges {edges}, the last ring open): one drop per ring expected")
+    for d in drops:
+        if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or not 0 <= d <= native.RINGLOD_MAX:
+            raise native.ScpError(f"ring_lod: drop {d!r}: an integer 0 .. {native.RINGLOD_MAX} (the number of octree levels the ring leaves out) expected")
+    drops = tuple(int(d) for d in drops)
+    return (edges, drops) if any(drops) else None
 
 
 def _rate_layout(level_sizes, context_size=None):
@@ -286,13 +315,13 @@ class _CoderPipeline:
         main.wait_stream(caller)
         return main
 
-    def submit(self, main, lohi, fills0, cuts=None, rate=None, temper=None):
+    def submit(self, main, lohi, fills0, cuts=None, rate=None, temper=None, ring=None):
         """lohi: the frame's pairs, enqueued on `main` (the last thing of its model part).  -> (future of the coded stream, or - cuts: row
         bounds of the frames of a batch - of the list of every frame's own stream; None).  fills0: native.CACHE_FILLS before the frame began.
         rate: the device records of the frame's rate report (native.rate_segments, enqueued on `main` behind the pairs): they ride to a pinned
         host tensor on the copy stream next to the pairs - no wait on this thread - and that tensor takes the place of the None; it is
         complete once the future is.  temper: the device buffer of the frame's temperature choice (`_temper_launch`), which travels the same
-        way -> third entry."""
+        way -> third entry.  ring: the device counters of a ring-LOD frame (`FrameEncoder._ring_force`), likewise -> fourth entry."""
         done = torch.cuda.Event()
         done.record(main)
         if native.CACHE_FILLS != fills0:               # device-side caches were built during this call (first frames only):
@@ -312,6 +341,11 @@ class _CoderPipeline:
                 temper_host = torch.empty(temper.shape, dtype=temper.dtype, pin_memory=True)
                 temper_host.copy_(temper, non_blocking=True)
                 temper.record_stream(self.copy_stream)
+            ring_host = None
+            if ring is not None:
+                ring_host = torch.empty(ring.shape, dtype=ring.dtype, pin_memory=True)
+                ring_host.copy_(ring, non_blocking=True)
+                ring.record_stream(self.copy_stream)
             copied = torch.cuda.Event(blocking=True)      # the coder thread SLEEPS until the pairs have landed (a default event spins a core)
             copied.record()
 
@@ -322,7 +356,7 @@ class _CoderPipeline:
                 return native.ac_encode_lohi(h)
             return [native.ac_encode_lohi(h[a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
 
-        return self.pool.submit(work), rate_host, temper_host
+        return self.pool.submit(work), rate_host, temper_host, ring_host
 
 
 class _FrontEnd:
@@ -331,8 +365,12 @@ class _FrontEnd:
     LANES_ENV = None                      # the environment variable that sets the number of lanes (read at the first asynchronous call)
 
     def __init__(self, model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate=False, rate_rows=False,
-                 temper=None, temper_grid=None):
+                 temper=None, temper_grid=None, ring_lod=None):
         self.model = model
+        # ring LOD ("Ring LOD"): None - nothing is launched or allocated and every stream is the one without the option;
+        # (edges, drops) - every range ring leaves out its own number of octree levels
+        self.ring_lod = parse_ring_lod(ring_lod)
+        self._ring_thr = None                 # per tree of the last build its integer thresholds
         # per-level temperature ("Temperature"): None - nothing is launched or allocated; "report" - every result dict gains
         # `temper`, the stream's bytes stay; "code" - the table is scaled by the chosen inverse temperatures before it is coded
         if temper not in (None, "report", "code"):
@@ -449,6 +487,10 @@ class _FrontEnd:
         """The file-name token of a tempered stream, in front of the coordinate token (decoder.stream_temper looks for it)."""
         return base + "_temper" if self.temper == "code" else base
 
+    def _ring_token(self, base):
+        """The file-name token of a ring-LOD stream, in front of `temper` / the coordinate token (decoder.stream_ringlod looks for it)."""
+        return base + "_ringlod" if getattr(self, "ring_lod", None) is not None else base
+
 
 class FrameEncoder(_FrontEnd):
     LANES_ENV = "SCP_LANES"
@@ -456,12 +498,17 @@ class FrameEncoder(_FrontEnd):
 
     def __init__(self, model, data_type=KITTI, lidar_level=12, spher=True, cylin=False, mullevel=False, max_batch=8,
                  device=None, packed=True, max_tokens=1_000_000, host_transform=None, profile=None, rate=False, rate_rows=False,
-                 temper=None, temper_grid=None):
+                 temper=None, temper_grid=None, ring_lod=None):
         if mullevel and not (spher or cylin):
             # encode_dataset_ehem_mullevel.py:97-186 has a cylindrical and a spherical branch only
             raise native.ScpError("--mullevel needs --spher or --cylin (the reference has no Cartesian multi-level path)")
         super().__init__(model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate, rate_rows,
-                         temper, temper_grid)
+                         temper, temper_grid, ring_lod)
+        if self.ring_lod is not None:
+            if self.mode == native.CART:
+                raise native.ScpError("ring_lod: Cartesian coordinates have no radial axis to cut rings on - encode with --spher or --cylin")
+            if data_type not in (KITTI, FORD):
+                raise native.ScpError(f"ring_lod: --type {data_type} has no LiDAR sensor at the origin to measure a range from")
         self.profile = profile          # native.NumericProfile of THIS encoder (None: the process default); current around every launch
         self.packed = packed            # one packed forward for all windows (default) vs one forward per group of equal windows
         self.max_tokens = max_tokens
@@ -502,9 +549,101 @@ class FrameEncoder(_FrontEnd):
         from . import metrics
         pts = []
         for s, info in enumerate(infos or self._infos):   # infos: per shell, anything with .qs[3] and .offset[3] (tests: the oracle's)
-            pts.append(metrics.dequantize(self.geom.leaves(s), info.qs, info.offset, spher=self.spher, cylin=self.cylin,
+            leaves = self.geom.leaves(s)
+            if self.ring_lod is not None:                 # the cloud a ring-LOD decoder writes: the centre of every leaf's terminal cell
+                leaves = self.ring_centres(leaves, s)[0]
+            pts.append(metrics.dequantize(leaves, info.qs, info.offset, spher=self.spher, cylin=self.cylin,
                                           f32=not self.mullevel).double())
         return pts
+
+    # ------------------------------------------------------------------------------------------ ring LOD
+    def ring_centres(self, leaves, s):
+        """The leaves (device int32 [U,3]) of tree s of the geometry just built -> (centres of their terminal cells, float64 [U,3]: origin
+        + (2^j - 1) / 2 per axis, exact; j uint8 [U]).  A snapped leaf is its cell's origin, so J(leaf, 0) is the cell's size."""
+        j = native.ringlod_cells(leaves, self._ring_thr[s], self.ring_lod[1])
+        return leaves.to(torch.float64) + ((torch.bitwise_left_shift(torch.ones_like(j, dtype=torch.int64), j.long()) - 1).to(torch.float64) / 2)[:, None], j
+
+    def _ring_snap(self, q, clouds, infos):
+        """ring_lod: the integer clouds `clouds` (consecutive row ranges of q, one per tree of the build to come: every frame's shells) with
+        their quantiser infos -> (q snapped, out of place: every point on the origin of its terminal cell; the state `_ring_mask`
+        completes).  One launch for all clouds, each with the thresholds of its own shell's step and offset."""
+        edges, drops = self.ring_lod
+        if len(infos) != len(clouds):
+            raise native.ScpError(f"ring_lod: {len(clouds)} integer clouds but the quantiser infos of {len(infos)}: the thresholds need every "
+                                  "shell's step and offset - quantise with this encoder (quantize / host_ints) or pass encode_ints(..., infos=)")
+        if len(clouds) > native.RINGLOD_MAX_TABLES:
+            raise native.ScpError(f"ring_lod: a batch holds at most {native.RINGLOD_MAX_TABLES} (frame, shell) trees")
+        thr = [native.ringlod_thresholds(edges, i.qs[0], i.offset[0]) for i in infos]
+        cuts = np.concatenate(([0], np.cumsum([int(c.shape[0]) for c in clouds])))
+        # a tree is as deep as its cloud's largest coordinate has bits (scp_geom_build), and the snap must leave that bit alone: one read-back
+        top = torch.stack([c.max() if c.numel() else torch.zeros((), dtype=c.dtype, device=c.device) for c in clouds]).cpu().tolist()
+        depths = [int(v).bit_length() for v in top]
+        if max(drops) > min(depths) - 1:
+            raise native.ScpError(f"ring_lod: a drop of {max(drops)} levels, but the shells of this frame are {depths} levels deep: at most "
+                                  f"{max(min(depths) - 1, 0)}, a tree keeps at least its root level")
+        segs = [(int(a), int(b - a), 0, k) for k, (a, b) in enumerate(zip(cuts[:-1], cuts[1:]))]
+        j, snapped = native.ringlod_cells(q, thr, drops, segs=segs, snapped=True)
+        return snapped, dict(thr=thr, j_points=j, point_cuts=cuts, x0=snapped[:, 0])
+
+    def _ring_mask(self, ring, n_frames=1):
+        """The implied rows of the geometry just built from snapped clouds, in frame order: a node of level L in a tree of depth D is
+        implied iff J(origin, D - L + 1) > 0 - it lies inside a terminal cell, so its only child is child 0 and its symbol 0."""
+        g, (edges, drops) = self.geom, self.ring_lod
+        depths = [int(i.depth) for i in g.info]
+        nd = g.nodes(("level", "pos"))
+        segs = [(int(i.node_base), int(i.n_nodes), int(i.depth), s) for s, i in enumerate(g.info)]
+        jn = native.ringlod_cells(nd["pos"], ring["thr"], drops, level=nd["level"], segs=segs)
+        node_of_row = torch.cat([torch.arange(int(i.node_base), int(i.node_base) + g.rows(s), device=self.device) for s, i in enumerate(g.info)])
+        # a multi-level cloud holds every point of the frame and the build keeps those of its rho shell (the top bits of axis 0 equal the
+        # shell's path, which the snap leaves alone): `snapped` counts the points a tree holds, once each
+        j_own, cuts = [], ring["point_cuts"]
+        for s, (_, _, path, _) in enumerate(g.segments):
+            j, path = ring["j_points"][int(cuts[s]):int(cuts[s + 1])], list(path or [])
+            if path:
+                bits = 0
+                for p in path:
+                    bits = (bits << 1) | int(p)
+                j = j[torch.bitwise_right_shift(ring["x0"][int(cuts[s]):int(cuts[s + 1])], depths[s] - len(path)) == bits]
+            j_own.append(j)
+        ring.update(mask_rows=(jn[node_of_row] > 0).to(torch.uint8), leaves=[int(i.n_leaves) for i in g.info], n_frames=n_frames, j_own=j_own)
+        self._ring_thr = ring["thr"]
+        return ring
+
+    def _ring_force(self, table, sym_coded, pre, plan, row_cuts=None):
+        """ring_lod: the implied rows of the coding-order table forced to symbol 0, directly behind the model and in front of everything
+        that reads the table (temper, CDF, rate).  -> (device int64 counters: [0] the implied rows whose symbol is NOT 0 - the encoder's
+        check of its own tree -, then per frame its implied rows and its points per j = 0 .. RINGLOD_MAX; the state); None when off."""
+        ring = pre.get("ring")
+        if ring is None:
+            return None
+        F, K1 = ring["n_frames"], native.RINGLOD_MAX + 1
+        mask = ring["mask_rows"][plan.coding_order_device(self.device)].contiguous()
+        buf = torch.zeros(1 + F + F * K1, dtype=torch.int64, device=self.device)
+        native.force_rows(table, mask, sym_coded, buf[:1])
+        row_cuts = [0, plan.n_rows] if row_cuts is None else [int(c) for c in row_cuts]
+        ns = len(ring["thr"]) // F
+        for f in range(F):
+            buf[1 + f] = mask[row_cuts[f]:row_cuts[f + 1]].sum()
+            buf[1 + F + f * K1:1 + F + (f + 1) * K1] = torch.bincount(torch.cat(ring["j_own"][f * ns:(f + 1) * ns]).long(), minlength=K1)[:K1]
+        return buf, ring, mask
+
+    def _ring_entries(self, forced, host=None):
+        """`_ring_force`'s result (host: the counters' pinned image of the asynchronous calls; None: copied here) -> the `ring_lod` entry of
+        every frame: edges, drops, thresholds and leaves per shell, snapped (points per j), implied_rows.  An implied row with a symbol
+        other than 0 means that the tree is not the one the rule describes: nothing of the frame is handed out."""
+        if forced is None:
+            return None
+        buf, ring, _ = forced
+        h = (buf.cpu() if host is None else host).numpy()
+        if int(h[0]) != 0:
+            raise native.ScpError(f"ring_lod: {int(h[0])} implied rows of the octree carry a symbol other than 0: the tree that was built is not "
+                                  "the tree of the snapped points (internal error: nothing was written)")
+        edges, drops = self.ring_lod
+        F, K1 = ring["n_frames"], native.RINGLOD_MAX + 1
+        ns = len(ring["thr"]) // F
+        return [dict(edges=list(edges), drops=list(drops), thresholds=[list(t) for t in ring["thr"][f * ns:(f + 1) * ns]],
+                     snapped=[int(v) for v in h[1 + F + f * K1:1 + F + f * K1 + max(drops) + 1]], implied_rows=int(h[1 + f]),
+                     leaves=ring["leaves"][f * ns:(f + 1) * ns]) for f in range(F)]
 
     def distortion_report(self, xyz_dev, edges=None, infos=None):
         """Where the D1 error of the frame just encoded goes (metrics.distortion_report on the cloud `distortion` measures): per range
@@ -630,7 +769,8 @@ class FrameEncoder(_FrontEnd):
         return d
 
     def preprocess(self, xyz_dev, ints=None):
-        if ints is None and not self.host_transform:
+        # (ring_lod snaps the integers between the quantiser and the build: the route of the integer inputs)
+        if ints is None and not self.host_transform and self.ring_lod is None:
             self._infos = self._build_xyz([xyz_dev])
             pre = self._tables(self._infos[0].bin_num, self._infos[0].offset[2] if self.cylin else 0.0, xyz_dev.shape[0])
         else:
@@ -658,8 +798,15 @@ class FrameEncoder(_FrontEnd):
         (the reference's --preproc_path flow).  -> ctx/pos/sym device tensors for all shells, level sizes, meta."""
         packed = getattr(qs, "packed", None)
         q = packed if packed is not None else (torch.cat(qs) if len(qs) > 1 else qs[0])
-        self.geom.build(q.contiguous(), self._segments(qs))
-        return self._tables(bin_num, z_offset, n_points)
+        if self.ring_lod is None:
+            self.geom.build(q.contiguous(), self._segments(qs))
+            return self._tables(bin_num, z_offset, n_points)
+        q, ring = self._ring_snap(q.contiguous(), qs, self._infos)
+        self.geom.build(q, self._segments(qs))
+        ring = self._ring_mask(ring)
+        pre = self._tables(bin_num, z_offset, n_points)
+        pre["ring"] = ring
+        return pre
 
     def preprocess_records(self, records, bin_num, z_offset, n_points):
         """--preproc_path flow (encode_dataset_ehem.py:149-157 + :52-105): the reference's int64 [N,4,6] record files (one per
@@ -692,6 +839,9 @@ class FrameEncoder(_FrontEnd):
     def encode_records(self, records, bin_num, z_offset, n_points, timing=False):
         """Encode from the reference's preprocessed record files (list of int64 [N,4,6], one per shell)."""
         t0 = time.perf_counter()
+        if self.ring_lod is not None:
+            raise native.ScpError("ring_lod with record files (--preproc_path): the records hold a finished octree, and the option snaps the "
+                                  "points before the tree is built")
         return self._encode_pre(self.preprocess_records(records, bin_num, z_offset, n_points), t0, timing)
 
     # ------------------------------------------------------------------------------------------ stage M + C
@@ -748,9 +898,12 @@ class FrameEncoder(_FrontEnd):
         xyz_dev = xyz.to(self.device, non_blocking=True)
         return self._encode_pre(self.preprocess(xyz_dev, ints), t0, timing)
 
-    def encode_ints(self, qs, bin_num, z_offset, n_points, timing=False):
-        """Encode from already-quantised integer coordinates (list of per-shell int32 [P_s,3] arrays / tensors)."""
+    def encode_ints(self, qs, bin_num, z_offset, n_points, timing=False, infos=None):
+        """Encode from already-quantised integer coordinates (list of per-shell int32 [P_s,3] arrays / tensors).  infos: the quantiser
+        infos the integers were made with (ring_lod takes its thresholds from their steps and offsets); None: the last quantiser call's."""
         t0 = time.perf_counter()
+        if infos is not None:
+            self._infos = list(infos)
         dq = [_as_tensor(q, np.int32).to(self.device) for q in qs]
         return self._encode_pre(self.preprocess_ints(dq, bin_num, z_offset, n_points), t0, timing)
 
@@ -795,11 +948,14 @@ class FrameEncoder(_FrontEnd):
         main.wait_event(front["ready"])
         with torch.cuda.stream(main):
             table = self.logits_in_coding_order(front["pre"], front["plan"])
+            forced = self._ring_force(table, front["sym_coded"], front["pre"], front["plan"], cuts)
             temper = self._temper_launch(table, front["sym_coded"], front["plan"].level_sizes)
             lohi = native.softmax_cdf(table, front["sym_coded"])["lohi"]
             rate, levels = self._rate_launch(table, front["sym_coded"], lohi, front["plan"].level_sizes)
-        future, rate_host, temper_host = self._pipeline().submit(main, lohi, fills0, cuts, rate[0] if rate else None, temper[0] if temper else None)
-        return dict(future=future, t0=t0, front=front, keep=(table, lohi, rate, temper), rate=(rate_host, levels), temper=(temper, temper_host))
+        future, rate_host, temper_host, ring_host = self._pipeline().submit(main, lohi, fills0, cuts, rate[0] if rate else None,
+                                                                            temper[0] if temper else None, forced[0] if forced else None)
+        return dict(future=future, t0=t0, front=front, keep=(table, lohi, rate, temper, forced), rate=(rate_host, levels),
+                    temper=(temper, temper_host), ring=(forced, ring_host))
 
     def encode_async(self, xyz, ints=None, front=None):
         """Like encode(), but the front part runs on the front stream, the model part on the next lane, and the D2H copy of the
@@ -823,17 +979,29 @@ class FrameEncoder(_FrontEnd):
         ns = len(self.shells())
         if len(frames) * ns > 62:
             raise native.ScpError("a batch holds at most 62 (frame, shell) trees (SCP_MAX_SEGMENTS)")
-        if self.host_transform or ints is not None:
+        ring = None
+        if self.host_transform or ints is not None or self.ring_lod is not None:
             qs_all, infos = [], []
             for f, xyz_dev in enumerate(frames):
-                hq, inf = ints[f] if ints is not None else self.host_ints(xyz_dev)
-                qs_all += _upload_ints(hq, self.device)
+                if self.host_transform or ints is not None:
+                    hq, inf = ints[f] if ints is not None else self.host_ints(xyz_dev)
+                    qs_all += _upload_ints(hq, self.device)
+                else:                                  # ring_lod: the device quantiser, shell by shell, then the snap below
+                    qs_all += self._quantize_device(xyz_dev)
+                    inf = self._infos
                 infos += inf
-            self.geom.build(torch.cat(qs_all).contiguous(), self._segments(qs_all))
+            q = torch.cat(qs_all).contiguous()
+            if self.ring_lod is not None:
+                q, ring = self._ring_snap(q, qs_all, infos)
+            self.geom.build(q, self._segments(qs_all))
         else:
             infos = self._build_xyz(frames)
         self._infos = infos[-ns:]
+        if ring is not None:
+            ring = self._ring_mask(ring, len(frames))
         pre = self._tables(infos[0].bin_num, 0.0, 0)
+        if ring is not None:
+            pre["ring"] = ring
         metas, sizes, mm0 = [], pre["level_sizes"], 0
         depths = [i.depth for i in self.geom.info]
         for f, xyz_dev in enumerate(frames):
@@ -844,7 +1012,10 @@ class FrameEncoder(_FrontEnd):
                               bin_nums=[float(i.bin_num) for i in fi], quant=_quant_of(fi), pos_mm=pre["pos_mm"][mm0:mm0 + nl],
                               level_sizes=fsizes, n_nodes=int(sum(fsizes))))
             mm0 += nl
-        return dict(ctx=pre["ctx"], pos=pre["pos"], sym_coded=pre["sym_coded"], level_sizes=sizes), metas
+        out = dict(ctx=pre["ctx"], pos=pre["pos"], sym_coded=pre["sym_coded"], level_sizes=sizes)
+        if ring is not None:
+            out["ring"] = pre["ring"]
+        return out, metas
 
     def encode_batch_async(self, frames, ints=None):
         """k frames through ONE stage G, ONE packed forward and ONE CDF launch (the small-frame configurations: a level-12 frame has
@@ -885,14 +1056,17 @@ class FrameEncoder(_FrontEnd):
             cuts = np.concatenate(([0], np.cumsum([len(m["level_sizes"]) for m in metas])))
             groups = _temper_groups(temper_host.numpy(), temper[2])
             tempers = [_temper_entry(groups[2 * a:2 * b], temper[2], level0=int(a)) for a, b in zip(cuts[:-1], cuts[1:])]
-        return [_result(stream, self._meta(m, m["n_nodes"]), dict(total=(time.perf_counter() - h["t0"]) / len(metas)), rate=r, temper=tp)
-                for stream, m, r, tp in zip(streams, metas, rates, tempers)]
+        rings = self._ring_entries(*h["ring"]) or [None] * len(metas)
+        return [_result(stream, self._meta(m, m["n_nodes"]), dict(total=(time.perf_counter() - h["t0"]) / len(metas)), rate=r, temper=tp, ring_lod=rg)
+                for stream, m, r, tp, rg in zip(streams, metas, rates, tempers, rings)]
 
     def finish(self, h):
         stream = h["future"].result()
         rate_host, levels = h["rate"]
+        ring = self._ring_entries(*h["ring"])
         return _result(stream, self._meta(h["front"]["pre"], h["front"]["plan"].n_rows), dict(total=time.perf_counter() - h["t0"]),
-                       rate=None if rate_host is None else (rate_host.numpy(), levels), temper=self._temper_result(*h["temper"]))
+                       rate=None if rate_host is None else (rate_host.numpy(), levels), temper=self._temper_result(*h["temper"]),
+                       ring_lod=ring and ring[0])
 
     def _encode_pre(self, pre, t0, timing):
         if timing:
@@ -901,6 +1075,7 @@ class FrameEncoder(_FrontEnd):
         plan = EncodePlan(pre["level_sizes"], self.context_size)
         table = self.logits_in_coding_order(pre, plan)
         sym_coded = self._sym_coded(pre, plan)
+        forced = self._ring_force(table, sym_coded, pre, plan)
         if timing:
             torch.cuda.synchronize()
         t2 = time.perf_counter()
@@ -910,16 +1085,21 @@ class FrameEncoder(_FrontEnd):
         rate, levels = self._rate_launch(table, sym_coded, lohi_dev, plan.level_sizes, keep_rows=keep_rows)
         self._rate_rows = (*rate[2], plan) if keep_rows else None
         lohi = lohi_dev.cpu().numpy()
+        ring = self._ring_entries(forced)           # (raises before anything is coded when an implied row carries a symbol other than 0)
         t3 = time.perf_counter()
         stream = native.ac_encode_lohi(lohi)
         t4 = time.perf_counter()
+        debug = dict(table=table, sym_coded=sym_coded, pre=pre)
+        if forced is not None:
+            debug["implied"] = forced[2]
         return _result(stream, self._meta(pre, plan.n_rows), dict(geom=t1 - t0, model=t2 - t1, cdf=t3 - t2, coder=t4 - t3, total=t4 - t0),
-                       debug=dict(table=table, sym_coded=sym_coded, pre=pre), rate=rate and (rate[0].cpu().numpy(), levels),
-                       temper=self._temper_result(temper))
+                       debug=debug, rate=rate and (rate[0].cpu().numpy(), levels), temper=self._temper_result(temper),
+                       ring_lod=ring and ring[0])
 
     def outfile(self, base, res):
-        """encode.py:140-144 file name; a tempered stream says so in front of the coordinate token (`..._temper_spher_<levels>_<bin>_<z>.bin`)."""
-        base = self._temper_token(base)
+        """encode.py:140-144 file name; a ring-LOD and a tempered stream say so in front of the coordinate token
+        (`..._ringlod_temper_spher_<levels>_<bin>_<z>.bin`)."""
+        base = self._temper_token(self._ring_token(base))
         if self.spher:
             base += "_spher"
         elif self.cylin:
@@ -941,7 +1121,9 @@ class OctAttnFrameEncoder(_FrontEnd):
     LANES_ENV = "SCP_LANES_OCTATTN"
 
     def __init__(self, model, data_type=KITTI, lidar_level=12, spher=True, cylin=False, max_batch=128, device=None, mullevel=False,
-                 level_wise=False, named=False, host_transform=None, decodable=False, rate=False, temper=None, temper_grid=None):
+                 level_wise=False, named=False, host_transform=None, decodable=False, rate=False, temper=None, temper_grid=None, ring_lod=None):
+        if parse_ring_lod(ring_lod) is not None:
+            raise native.ScpError("OctAttention: ring_lod is not available - its decoder has no forced rows; the EHEM encoders have the option")
         if temper == "code":
             raise native.ScpError("OctAttention: temper='code' is not available - the decodable profile decodes one node per step, and a "
                                   "tempered form of it is not part of this library; temper='report' measures what it would save")
@@ -1150,7 +1332,7 @@ class OctAttnFrameEncoder(_FrontEnd):
                                                                         quant=self.quant_info())
         # (the handle keeps what the front stream allocated - the frame, its integers, the context sequences - and the table referenced
         # until finish(): see FrameEncoder._model_async)
-        future, rate_host, temper_host = pipe.submit(main, lohi, fills0, rate=rate[0] if rate else None, temper=temper[0] if temper else None)
+        future, rate_host, temper_host, _ = pipe.submit(main, lohi, fills0, rate=rate[0] if rate else None, temper=temper[0] if temper else None)
         return dict(future=future, meta=meta, t0=t0, keep=(keep, lohi, q, xyz_dev, rate, temper), rate=(rate_host, levels),
                     temper=(temper, temper_host))
 

@@ -154,6 +154,9 @@ def lib():
         "scp_temper_sweep": (C.c_int, [_vp, i64, i64, i32, _vp, _vp, i32, _vp, i32, _vp, _vp, _vp, _vp, i64, _vp]),
         "scp_temper_choose": (C.c_int, [_vp, _vp, _vp, i64, _vp, i32, i32, _vp, i32, i32, C.c_double, _vp, _vp, _vp, _vp]),
         "scp_scale_rows": (C.c_int, [_vp, i64, _vp, i64, i64, i32, _vp, _vp, i32, _vp]),
+        "scp_ringlod_workspace_bytes": (C.c_int64, [i32, i32]),
+        "scp_ringlod_cells": (C.c_int, [_vp, i64, i32, _vp, _vp, i32, _vp, _vp, i32, i32, _vp, _vp, _vp, i64, _vp]),
+        "scp_force_rows": (C.c_int, [_vp, i64, i64, i32, _vp, _vp, _vp, _vp]),
         "scp_nn_error_split_f64": (C.c_int, [_vp, i64, _vp, i64, _vp, _vp, i32, _vp, i32, _vp, _vp, _vp, _vp, _vp, _vp]),
         "scp_dist_segments_f64": (C.c_int, [_vp, _vp, _vp, _vp, i64, _vp, i32, _vp, _vp]),
         "scp_rate_leaf_share_workspace_bytes": (C.c_int64, [i64, i32]),
@@ -1784,6 +1787,91 @@ def scale_rows(table, seg_off, seg_beta, out=None):
                               _dev(seg_beta, torch.float32), S, _stream())
     _check(rc, "scp_scale_rows")
     return dst
+
+
+# ------------------------------------------------------------------------------------------------- ring LOD (csrc/ringlod.hip)
+RINGLOD_MAX, RINGLOD_MAX_RINGS, RINGLOD_MAX_TABLES = 8, 32, 64             # include/scp.h: SCP_RINGLOD_MAX*
+RINGLOD_SEG = np.dtype([("first", np.int64), ("count", np.int64), ("depth", np.int32), ("table", np.int32)])      # scp_ringlod_seg
+# what a forced row costs under the coder's 16-bit tables: its one-hot CDF row is (c_low, c_high) = (0, 65282) - DESIGN.md 6, "Ring LOD"
+FORCED_ROW_TABLE_BITS = 16.0 - float(np.log2(65282.0))
+
+
+def ringlod_thresholds(edges, qs0, offset0):
+    """Ring edges (dist_edges form: 0 = E_0 < E_1 < ...) -> the integer thresholds of E_1 .. on the radial axis of a shell quantised with
+    step qs0 and offset offset0: t_i = clamp(ceil((E_i - offset0) / qs0), 0, 2^31 - 1), in float64 on the host.  A point of quantised
+    radius q lies at q * qs0 + offset0, so q >= t_i says that it lies at or beyond E_i."""
+    import math
+    out = []
+    for e in list(edges)[1:]:
+        v = (float(e) - float(offset0)) / float(qs0)
+        out.append(int(min(max(math.ceil(v), 0), 2 ** 31 - 1)) if v == v and abs(v) != float("inf") else (0 if v < 0 else 2 ** 31 - 1))
+    return out
+
+
+def _ringlod_tables(thresholds, drops):
+    """One table (a flat list of thresholds) or several (a list of lists), one list of drops for all or one per table -> (int64 [T,R-1],
+    uint8 [T,R]).  Shapes only: the library checks the values."""
+    drops = np.asarray(drops)
+    thr = np.asarray(thresholds, dtype=np.int64)
+    if drops.ndim == 1:
+        thr = thr.reshape(1, -1) if thr.ndim <= 1 else thr
+        drops = np.broadcast_to(drops, (thr.shape[0], drops.shape[0]))
+    if thr.ndim == 1:
+        thr = thr.reshape(drops.shape[0], -1)
+    if drops.ndim != 2 or thr.ndim != 2 or drops.shape[0] != thr.shape[0] or drops.shape[1] != thr.shape[1] + 1:
+        raise ScpError(f"ring LOD: {tuple(drops.shape)} drops for {tuple(thr.shape)} thresholds: one more drop than thresholds per table expected")
+    if drops.size and (not np.issubdtype(drops.dtype, np.integer) or drops.min() < 0 or drops.max() > 255):
+        raise ScpError(f"ring LOD: drops are integers 0 .. {RINGLOD_MAX}")
+    return np.ascontiguousarray(thr), np.ascontiguousarray(drops.astype(np.uint8))
+
+
+def ringlod_cells(origins, thresholds, drops, start=0, level=None, segs=None, snapped=None):
+    """scp_ringlod_cells: j = J(origin, s) per row of origins (cuda int32 [n,3]) under the integer rule of include/scp.h.  thresholds /
+    drops: one table, or one per entry of a list (host integers); segs: None (every row table 0, s = start) or [(first row, count, depth,
+    table)] - with level (cuda uint8 [n]: the rows' octree levels) s = depth - level + 1 per row.  snapped: None, True (a new tensor) or a
+    cuda int32 [n,3] tensor (origins itself allowed) that receives (x >> j) << j.  -> j cuda uint8 [n], or (j, snapped)."""
+    thr, dr = _ringlod_tables(thresholds, drops)
+    n, dev = int(origins.shape[0]), origins.device
+    if origins.dim() != 2 or origins.shape[1] != 3:
+        raise ScpError(f"ringlod_cells: int32 [n,3] origins expected, got {tuple(origins.shape)}")
+    seg = np.zeros(0, RINGLOD_SEG)
+    if segs is not None:
+        seg = np.zeros(len(segs), RINGLOD_SEG)
+        for k, s in enumerate(segs):
+            seg[k] = tuple(int(v) for v in s)
+    if level is not None and tuple(level.shape) != (n,):
+        raise ScpError("ringlod_cells: one level per row expected")
+    ws_bytes = int(lib().scp_ringlod_workspace_bytes(thr.shape[0], seg.shape[0]))
+    if ws_bytes < 0:
+        raise ScpError(f"ringlod_cells: {thr.shape[0]} tables and {seg.shape[0]} segments: 1 .. {RINGLOD_MAX_TABLES} tables and at most "
+                       f"{RINGLOD_MAX_TABLES} segments expected")
+    j = torch.empty(n, dtype=torch.uint8, device=dev)
+    out = torch.empty_like(origins) if snapped is True else snapped
+    if out is not None and (out.shape != origins.shape or out.dtype != torch.int32):
+        raise ScpError("ringlod_cells: snapped is an int32 tensor of the origins' shape")
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.int64, device=dev)
+    rc = lib().scp_ringlod_cells(_dev(origins, torch.int32), n, int(start), None if level is None else _dev(level, torch.uint8),
+                                 seg.ctypes.data if seg.shape[0] else None, seg.shape[0], thr.ctypes.data if thr.size else None,
+                                 dr.ctypes.data, thr.shape[0], dr.shape[1], _dev(j), None if out is None else _dev(out), ws.data_ptr(),
+                                 ws_bytes, _stream())
+    _check(rc, "scp_ringlod_cells")
+    return j if out is None else (j, out)
+
+
+def force_rows(table, mask, sym=None, mismatch=None):
+    """scp_force_rows: the rows of table (cuda f32 [n,nsym], row stride allowed) whose mask (cuda uint8 [n]) is set become (0, -1000,
+    -1000, ...), in place.  sym (cuda uint8 [n]) with mismatch (cuda int64 [1], zeroed by the caller): the counter grows by the masked rows
+    whose symbol is not 0.  -> table."""
+    n, nsym = table.shape
+    if not table.is_cuda or table.dtype != torch.float32 or table.stride(1) != 1 or tuple(mask.shape) != (n,):
+        raise ScpError("force_rows: a device float32 table with unit column stride and one mask byte per row expected")
+    if (sym is None) != (mismatch is None) or (sym is not None and (tuple(sym.shape) != (n,) or mismatch.numel() != 1)):
+        raise ScpError("force_rows: symbols (one per row) and the mismatch counter (int64 [1]) go together")
+    rc = lib().scp_force_rows(table.data_ptr(), _row_stride(table), n, nsym, _dev(mask, torch.uint8),
+                              None if sym is None else _dev(sym, torch.uint8), None if mismatch is None else _dev(mismatch, torch.int64),
+                              _stream())
+    _check(rc, "scp_force_rows")
+    return table
 
 
 DIST_MAX_RINGS, DIST_MAX_BINS = 64, 4096                                   # include/scp.h: SCP_DIST_MAX_*
