@@ -411,13 +411,17 @@ __global__ __launch_bounds__(256) void bbox32_kernel(const float *__restrict__ x
 // ---- fp32-faithful kernel on f16 MFMA ("f16x3") -----------------------------------------------------------------------------
 // split2_kernel scales every row by its own power of two (largest |feature| into [2^13, 2^14): exact, keeps f16 clear of
 // overflow and of its subnormal range for everything that matters) and writes it as two f16 terms x ~= xa + xb (11 + 11
-// significant bits, residual < 2^-22 |x|).  A dot product keeps the three partial products down to 2^-11 relative size,
+// significant bits, residual < 2^-22 |x| for entries within 2^16 of the row's largest; smaller ones leave f16's normal range
+// and keep an absolute residual of up to 2^-38 of the row's largest entry).  A dot product keeps the three partial products
+// down to 2^-11 relative size,
 //     x.y ~= xb.ya + xa.yb + xa.ya,          dropped: xb.yb < 2^-22 |x||y|,
 // accumulated in fp32 by v_mfma_f32_32x32x16_f16, small terms first, then multiplied by the two rows' inverse scales (powers
-// of two, exact).  Three f16 MFMAs cover 16 features in 96 cycles where the fp32 MFMA needs 512.  The distance values agree
-// with the fp32 chain to about its own rounding error (worst case 7e-7 of sum |x_i y_i|; the k-ordered fp32 chain itself
-// carries up to K 2^-24 of it), so the two kernels select the same neighbours except among candidates whose distances are
-// closer than that - the same class of difference as the ordering of exact ties (measured: tests/test_gpu_model.py).
+// of two, exact).  Three f16 MFMAs cover 16 features in 96 cycles where the fp32 MFMA needs 512.  Worst case per pair
+// (derived in tests/knn_ref.py, `bound`): the split and the dropped term cost 3 * 2^-22 = 7.2e-7 of sum |x_i y_i| (plus the
+// 2^-38 terms above), the fp32 accumulation of the 3 K products up to 3 K 2^-24 of it - the k-ordered fp32 chain itself
+// carries up to K 2^-24; a returned neighbour was never seen farther beyond the true 20th best than 2 % of the tolerance
+// that follows from these bounds (profiles/parity_r6.json, knn_cases/*).  The two kernels therefore select the same neighbours except among candidates whose distances are closer than that - the same
+// class of difference as the ordering of exact ties (measured: tests/test_gpu_model.py, tests/test_gpu_knn.py).
 // SCP_KNN=f32 selects the exact kernel instead.
 // Data: planes [row][2][K] f16 = rows of 4K bytes; swizzle as in the fp32 kernel (K = 192: q ^ (c & 15), K = 144: q ^ ((c >> 2) & 3)).
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
