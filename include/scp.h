@@ -671,7 +671,7 @@ SCP_API int scp_ring_bins_f64(const double *xyz, int64_t n, const double *view, 
 SCP_API int scp_share_segments_f64(const double *cost_ideal, const double *cost_table, const int64_t *order /* NULL ok */, int64_t n,
                                    const int64_t *seg_off, int32_t n_bins, scp_share_seg *out, void *stream);
 
-/* Depth report (csrc/depthshare.hip; additive, no new ABI version; host side: scp_amd/metrics.py depth_dict, FrameEncoder.depth_report):
+/* Depth report (csrc/ringrate.hip; additive, no new ABI version; host side: scp_amd/metrics.py depth_dict, FrameEncoder.depth_report):
  * what the first D - k levels of a tree cost, per leaf and per bin - an octree stream is progressive, its levels 1 .. D - k describe the
  * cloud at cell size 2^k.  With leaves(i), share(i), the ancestors a_l and the leaf order of the rate per ring above:
  *   cost_k(p) = ((share(a_1) + share(a_2)) + ..) + share(a_{D-k})   for 0 <= k < D: the operations of cost(p), the chain cut short;
@@ -683,9 +683,9 @@ SCP_API int scp_share_segments_f64(const double *cost_ideal, const double *cost_
  * scp_rate_leaf_share) at offset k * total_leaves.  workspace: scp_rate_depth_share_workspace_bytes(total_nodes, nseg) bytes, 8-byte
  * aligned device memory.  The host checks and the validation launch of scp_rate_leaf_share apply unchanged, and max_drop outside its
  * range is refused with them: SCP_EINVAL, nothing written to an output (the call synchronises `stream` once).
- * Order: leaves and the per-node sums as in scp_rate_leaf_share; then one launch in which every level-D node climbs up to max_drop
- * parents and writes every plane of the leaves it owns.  All segments share the launches, whose number (2 * deepest tree + 2) depends
- * on the depths alone - not on node counts, segment counts or max_drop.
+ * Order: leaves, the per-node sums and plane 0 by the launches of scp_rate_leaf_share; then, for max_drop >= 1, one launch in which every
+ * level-D node climbs up to max_drop parents and writes planes 1 .. max_drop of the leaves it owns.  All segments share the launches,
+ * whose number (2 * deepest tree + 2; + 1 for max_drop = 0) depends on the depths alone - not on node or segment counts.
  *
  * scp_share_segments_depth_f64: scp_share_segments_f64 on n_depths planes in one launch (depth on the second grid axis): plane d of
  * cost_ideal / cost_table starts at d * plane_stride (>= n); order, seg_off, n, clamping and the SUMMATION CONTRACT exactly as there, the

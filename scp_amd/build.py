@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libscp_hip.so")
 SOURCES = ["api.cpp", "geom.hip", "sort_u64.hip", "cdf.hip", "rangecoder.cpp", "legacy_octree.cpp",
-           "knn.hip", "edge.hip", "attn.hip", "octattn.hip", "octattn_f16.hip", "octattn_embed.hip", "octattn_rowinv.hip", "gemm.hip", "gemm_split.hip", "rowchain.hip", "lnlin2.hip", "fused.hip", "metrics.hip", "plan.hip", "normals.hip", "rate.hip", "distreport.hip", "ringrate.hip", "depthshare.hip", "temper.hip", "ringlod.hip"]
+           "knn.hip", "edge.hip", "attn.hip", "octattn.hip", "octattn_f16.hip", "octattn_embed.hip", "octattn_rowinv.hip", "gemm.hip", "gemm_split.hip", "rowchain.hip", "lnlin2.hip", "fused.hip", "metrics.hip", "plan.hip", "normals.hip", "rate.hip", "distreport.hip", "ringrate.hip", "temper.hip", "ringlod.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-fvisibility=hidden", "-x", "hip"]
@@ -18,8 +18,7 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 EXTRA = {"geom.hip": ["-ffp-contract=off"], "knn.hip": ["-ffp-contract=off"], "cdf.hip": ["-ffp-contract=off"],
          "edge.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"], "octattn_embed.hip": ["-ffp-contract=off"],
          "octattn_rowinv.hip": ["-ffp-contract=off"], "normals.hip": ["-ffp-contract=off"], "rate.hip": ["-ffp-contract=off"],
-         "distreport.hip": ["-ffp-contract=off"], "ringrate.hip": ["-ffp-contract=off"], "depthshare.hip": ["-ffp-contract=off"],
-         "temper.hip": ["-ffp-contract=off"]}
+         "distreport.hip": ["-ffp-contract=off"], "ringrate.hip": ["-ffp-contract=off"], "temper.hip": ["-ffp-contract=off"]}
 if os.environ.get("SCP_ATTN_DEFS"):    # experiment builds of csrc/attn.hip (e.g. SCP_ATTN_DEFS="-DPNS=3")
     EXTRA["attn.hip"] = os.environ["SCP_ATTN_DEFS"].split()
 if os.environ.get("SCP_KNN_DEFS"):     # experiment builds of csrc/knn.hip (e.g. SCP_KNN_DEFS="-DKNN_INSERT_CHAIN")

@@ -21,7 +21,7 @@ same stdout block per frame, same summary file.  Differences, all additive:
     (csrc/ringrate.hip): one more line per frame (ideal bits per leaf of every ring) and a `<stream>.rings.json` next to every stream
     (tools/rd_rings.py joins it with the `.dist.json`).  Implies the rate kernels; the streams themselves do not change.
   * `--depth_report [K[:EDGES]]` (EHEM): what every octree level costs and buys, from one encode - for every truncation depth k = 0 .. K
-    (default 4) the bits of levels 1 .. D - k per range ring and rho shell (csrc/depthshare.hip, on the bins of `--rate_rings`) and the D1
+    (default 4) the bits of levels 1 .. D - k per range ring and rho shell (csrc/ringrate.hip, on the bins of `--rate_rings`) and the D1
     error of the cloud those levels describe (the cells of size 2^k, which `decode_ehem.py --lod k` writes): one more line per frame
     (ideal bits per point and D1 PSNR for every k) and a `<stream>.depth.json` next to every stream (tools/rd_depth.py reads it).
     Implies the rate kernels; the streams themselves do not change.

@@ -20,13 +20,10 @@
 //   bin:       thread t of the bin's one workgroup adds rows t, t + 1024, .. of the bin in that order, then a fixed binary tree over the
 //              1024 partial sums - a function of the bin's rows in index order and of nothing else.
 // No floating-point atomics anywhere.  rows, axis_rows, max_sq and hist are exact by nature (the histogram uses integer LDS atomics).
-#include "scp_internal.h"
+#include "rate_common.h"
 
 #define DR_TILE 1024
-#define DR_SEG_THREADS 1024
 #define DR_NO_INDEX 0x7FFFFFFF
-
-struct dr_edges { double sq[SCP_DIST_MAX_RINGS]; };
 
 __global__ __launch_bounds__(256) void dr_init_kernel(int *__restrict__ idx, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -63,7 +60,7 @@ __global__ __launch_bounds__(256) void dr_nn_index_kernel(const double *__restri
 
 // one thread per query: the error vector in the local frame, the bin, the flags
 __global__ __launch_bounds__(256) void dr_split_kernel(const double *__restrict__ a, int64_t na, const double *__restrict__ b, int64_t nb,
-                                                       double vx, double vy, double vz, dr_edges edges, int n_rings,
+                                                       double vx, double vy, double vz, ring_edges edges, int n_rings,
                                                        const int *__restrict__ group, int n_groups, int *__restrict__ idx,
                                                        double *__restrict__ d2, double *__restrict__ comp, int *__restrict__ bin,
                                                        uint8_t *__restrict__ flag) {
@@ -82,8 +79,9 @@ __global__ __launch_bounds__(256) void dr_split_kernel(const double *__restrict_
         ex = b[3 * (int64_t)j] - ax; ey = b[3 * (int64_t)j + 1] - ay; ez = b[3 * (int64_t)j + 2] - az;
     }
     const double x = ax - vx, y = ay - vy, z = az - vz;
-    const double s2 = x * x + y * y;
-    const double rho2 = s2 + z * z;
+    double s2, rho2;
+    // (the Python binding refuses a group out of range before the launch)
+    const int bn = ring_bin(x, y, z, edges, n_rings, group ? group[i] : 0, n_groups, s2, rho2, f);
     const double s = sqrt(s2);
     double er = 0.0, ephi = 0.0, eth = 0.0;
     if (s == 0.0) {
@@ -97,15 +95,8 @@ __global__ __launch_bounds__(256) void dr_split_kernel(const double *__restrict_
         ephi = ey * ux - ex * uy;
         eth = eh * ct - ez * st;
     }
-    int ring = 0;
-    for (int r = 1; r < n_rings; ++r) ring = rho2 >= edges.sq[r] ? r : ring;      // edges ascend: the last hit is the largest r
-    int g = group ? group[i] : 0;
-    if (g < 0 || g >= n_groups) {                     // never an out-of-range bin: clamped and flagged (the Python binding refuses before the launch)
-        f |= SCP_DIST_FLAG_GROUP_CLAMPED;
-        g = g < 0 ? 0 : n_groups - 1;
-    }
     comp[3 * i] = er; comp[3 * i + 1] = ephi; comp[3 * i + 2] = eth;
-    bin[i] = g * n_rings + ring;
+    bin[i] = bn;
     flag[i] = (uint8_t)f;
 }
 
@@ -116,22 +107,22 @@ __device__ __forceinline__ int dr_bucket(double d) {
 }
 
 // one workgroup per bin
-__global__ __launch_bounds__(DR_SEG_THREADS) void dr_segments_kernel(const double *__restrict__ d2, const double *__restrict__ comp,
-                                                                     const uint8_t *__restrict__ flag, const int64_t *__restrict__ order,
-                                                                     int64_t n, const int64_t *__restrict__ seg_off, scp_dist_seg *__restrict__ out) {
-    __shared__ double s_sq[DR_SEG_THREADS], s_r2[DR_SEG_THREADS], s_p2[DR_SEG_THREADS], s_t2[DR_SEG_THREADS], s_r[DR_SEG_THREADS], s_mx[DR_SEG_THREADS];
-    __shared__ int s_axis[DR_SEG_THREADS], s_rows[DR_SEG_THREADS];
+__global__ __launch_bounds__(RATE_SEG_THREADS) void dr_segments_kernel(const double *__restrict__ d2, const double *__restrict__ comp,
+                                                                       const uint8_t *__restrict__ flag, const int64_t *__restrict__ order,
+                                                                       int64_t n, const int64_t *__restrict__ seg_off, scp_dist_seg *__restrict__ out) {
+    __shared__ double s_sq[RATE_SEG_THREADS], s_r2[RATE_SEG_THREADS], s_p2[RATE_SEG_THREADS], s_t2[RATE_SEG_THREADS], s_r[RATE_SEG_THREADS];
+    __shared__ rate_max s_mx[RATE_SEG_THREADS];
+    __shared__ int s_axis[RATE_SEG_THREADS], s_rows[RATE_SEG_THREADS];
     __shared__ unsigned s_hist[64];
     const int t = threadIdx.x;
     if (t < 64) s_hist[t] = 0u;
     __syncthreads();
-    // the offsets and the order live in device memory, so nobody has checked them: clamped to the table, a row outside it is skipped
-    int64_t lo = seg_off[blockIdx.x], hi = seg_off[blockIdx.x + 1];
-    lo = lo < 0 ? 0 : (lo > n ? n : lo);
-    hi = hi < lo ? lo : (hi > n ? n : hi);
+    // the order lives in device memory like the offsets, so nobody has checked it: a row outside the table is skipped
+    int64_t lo, hi;
+    rate_seg_bounds(seg_off, blockIdx.x, n, lo, hi);
     double sq = 0.0, r2 = 0.0, p2 = 0.0, t2 = 0.0, sr = 0.0, mx = 0.0;
     int axis = 0, rows = 0;
-    for (int64_t p = lo + t; p < hi; p += DR_SEG_THREADS) {
+    for (int64_t p = lo + t; p < hi; p += RATE_SEG_THREADS) {
         const int64_t i = order ? order[p] : p;
         if (i < 0 || i >= n) continue;
         const double d = d2[i];
@@ -147,29 +138,14 @@ __global__ __launch_bounds__(DR_SEG_THREADS) void dr_segments_kernel(const doubl
             r2 += er * er; p2 += ep * ep; t2 += et * et; sr += er;
         }
     }
-    s_sq[t] = sq; s_r2[t] = r2; s_p2[t] = p2; s_t2[t] = t2; s_r[t] = sr; s_mx[t] = mx; s_axis[t] = axis; s_rows[t] = rows;
-    __syncthreads();
-    for (int h = DR_SEG_THREADS / 2; h >= 1; h >>= 1) {
-        if (t < h) {
-            s_sq[t] += s_sq[t + h]; s_r2[t] += s_r2[t + h]; s_p2[t] += s_p2[t + h]; s_t2[t] += s_t2[t + h]; s_r[t] += s_r[t + h];
-            s_mx[t] = s_mx[t + h] > s_mx[t] ? s_mx[t + h] : s_mx[t];
-            s_axis[t] += s_axis[t + h]; s_rows[t] += s_rows[t + h];
-        }
-        __syncthreads();
-    }
+    s_sq[t] = sq; s_r2[t] = r2; s_p2[t] = p2; s_t2[t] = t2; s_r[t] = sr; s_mx[t].v = mx; s_axis[t] = axis; s_rows[t] = rows;
+    rate_block_tree(t, s_sq, s_r2, s_p2, s_t2, s_r, s_mx, s_axis, s_rows);
     scp_dist_seg *o = out + blockIdx.x;
     if (t == 0) {
         o->rows = s_rows[0]; o->axis_rows = s_axis[0];
-        o->sum_sq = s_sq[0]; o->sum_r2 = s_r2[0]; o->sum_phi2 = s_p2[0]; o->sum_theta2 = s_t2[0]; o->sum_r = s_r[0]; o->max_sq = s_mx[0];
+        o->sum_sq = s_sq[0]; o->sum_r2 = s_r2[0]; o->sum_phi2 = s_p2[0]; o->sum_theta2 = s_t2[0]; o->sum_r = s_r[0]; o->max_sq = s_mx[0].v;
     }
     if (t < 64) o->hist[t] = (int64_t)s_hist[t];
-}
-
-static bool dr_edges_ok(const double *edges_sq, int32_t n_rings) {
-    if (!edges_sq || n_rings < 1 || n_rings > SCP_DIST_MAX_RINGS || edges_sq[0] != 0.0) return false;
-    for (int r = 1; r < n_rings; ++r)
-        if (!(edges_sq[r] > edges_sq[r - 1]) || !(edges_sq[r] <= 1.79769313486231570815e308)) return false;
-    return true;
 }
 
 /* nearest neighbour's identity, error split and bin per query: see include/scp.h */
@@ -178,9 +154,7 @@ extern "C" SCP_API int scp_nn_error_split_f64(const double *a, int64_t na, const
                                               double *comp_out, int32_t *bin_out, uint8_t *flag_out, void *stream) {
     if (!a || !b || !view || !idx_out || !d2_out || !comp_out || !bin_out || !flag_out) return SCP_EINVAL;
     if (na <= 0 || nb <= 0 || na > SCP_DIST_MAX_POINTS || nb > SCP_DIST_MAX_POINTS || n_groups < 1) return SCP_EINVAL;
-    if (!dr_edges_ok(edges_sq, n_rings) || (int64_t)n_groups * n_rings > SCP_DIST_MAX_BINS) return SCP_EINVAL;
-    if (!(fabs(view[0]) <= 1.79769313486231570815e308) || !(fabs(view[1]) <= 1.79769313486231570815e308) || !(fabs(view[2]) <= 1.79769313486231570815e308))
-        return SCP_EINVAL;
+    if (!ring_edges_ok(edges_sq, n_rings) || (int64_t)n_groups * n_rings > SCP_DIST_MAX_BINS || !ring_view_ok(view)) return SCP_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int rc = scp_nn_sqdist_f64(a, na, b, nb, d2_out, stream);       // the minimum: exact and order-free
     if (rc != SCP_OK) return rc;
@@ -192,10 +166,8 @@ extern "C" SCP_API int scp_nn_error_split_f64(const double *a, int64_t na, const
     if (gy > max_y) gy = max_y;
     hipLaunchKernelGGL(dr_nn_index_kernel, dim3(gx, gy), dim3(256), 0, st, a, na, b, nb, d2_out, idx_out);
     LAUNCH_CHECK();
-    dr_edges e;
-    for (int r = 0; r < SCP_DIST_MAX_RINGS; ++r) e.sq[r] = r < n_rings ? edges_sq[r] : 0.0;
-    hipLaunchKernelGGL(dr_split_kernel, dim3(gx), dim3(256), 0, st, a, na, b, nb, view[0], view[1], view[2], e, (int)n_rings, group, (int)n_groups,
-                       idx_out, d2_out, comp_out, bin_out, flag_out);
+    hipLaunchKernelGGL(dr_split_kernel, dim3(gx), dim3(256), 0, st, a, na, b, nb, view[0], view[1], view[2],
+                       ring_edges_arg(edges_sq, n_rings), (int)n_rings, group, (int)n_groups, idx_out, d2_out, comp_out, bin_out, flag_out);
     LAUNCH_CHECK();
     return SCP_OK;
 }
@@ -204,7 +176,7 @@ extern "C" SCP_API int scp_nn_error_split_f64(const double *a, int64_t na, const
 extern "C" SCP_API int scp_dist_segments_f64(const double *d2, const double *comp, const uint8_t *flag, const int64_t *order, int64_t n,
                                              const int64_t *seg_off, int32_t n_bins, scp_dist_seg *out, void *stream) {
     if (!d2 || !comp || !flag || !seg_off || !out || n <= 0 || n > SCP_DIST_MAX_POINTS || n_bins < 1 || n_bins > SCP_DIST_MAX_BINS) return SCP_EINVAL;
-    hipLaunchKernelGGL(dr_segments_kernel, dim3((unsigned)n_bins), dim3(DR_SEG_THREADS), 0, (hipStream_t)stream, d2, comp, flag, order, n, seg_off, out);
+    hipLaunchKernelGGL(dr_segments_kernel, dim3((unsigned)n_bins), dim3(RATE_SEG_THREADS), 0, (hipStream_t)stream, d2, comp, flag, order, n, seg_off, out);
     LAUNCH_CHECK();
     return SCP_OK;
 }

@@ -1,8 +1,10 @@
 // The row and segment contracts of the rate report (csrc/rate.hip) as device functions, shared with the temperature sweep
-// (csrc/temper.hip): whoever evaluates a row's cross-entropy or adds rows up through these gets the same bits.
+// (csrc/temper.hip), the distortion report (csrc/distreport.hip) and the rate per ring (csrc/ringrate.hip): whoever evaluates a row's
+// cross-entropy, adds rows up or bins a point through these gets the same bits.
 //   row:     lane l of the row's wavefront owns columns 4 l .. 4 l + 3 and adds their exponentials in column order, then a fixed xor butterfly
 //            (32, 16, .. 1) across the wavefront;
-//   segment: thread t of the workgroup adds rows t, t + 1024, .. in that order, then a fixed binary tree over the 1024 partial sums.
+//   segment: thread t of the workgroup adds rows t, t + 1024, .. in that order, then a fixed binary tree over the 1024 partial sums;
+//   ring:    one expression for rho2 and one ascending scan of the edges (ring_bin).
 // Every including file is built with -ffp-contract=off.
 #pragma once
 #include "scp_internal.h"
@@ -71,12 +73,55 @@ __device__ __forceinline__ void rate_seg_bounds(const int64_t *__restrict__ seg_
     b = b < a ? a : (b > n ? n : b);
 }
 
-// the fixed binary tree over RATE_SEG_THREADS partial sums per array (shared memory, written by every thread before the call): s[0] holds the sum
+// the fixed binary tree over RATE_SEG_THREADS partials per array (shared memory, written by every thread before the call): s[0] holds the
+// result.  An array of rate_max carries a maximum through the same loop and the same barriers; every other array a sum.
+struct rate_max { double v; };
+template <typename T>
+__device__ __forceinline__ void rate_join(T &a, const T &b) { a += b; }
+__device__ __forceinline__ void rate_join(rate_max &a, const rate_max &b) { a.v = b.v > a.v ? b.v : a.v; }
+
 template <typename... T>
 __device__ __forceinline__ void rate_block_tree(int t, T *...s) {
     __syncthreads();
     for (int h = RATE_SEG_THREADS / 2; h >= 1; h >>= 1) {
-        if (t < h) ((s[t] += s[t + h]), ...);
+        if (t < h) (rate_join(s[t], s[t + h]), ...);
         __syncthreads();
     }
+}
+
+// The ring rule of the distortion report and of the rate per ring: ring = the largest r with rho2 >= edges.sq[r], decided on
+// rho2 = (x*x + y*y) + z*z of (point - view) - no sqrt takes part; bin = group * n_rings + ring.
+struct ring_edges { double sq[SCP_DIST_MAX_RINGS]; };
+
+// (x, y, z) = point - view, g = the point's group.  -> the bin; s2 and rho2 for a caller that goes on with them; a group outside
+// [0, n_groups) never gives an out-of-range bin: it is clamped and SCP_DIST_FLAG_GROUP_CLAMPED is set in f.
+__device__ __forceinline__ int ring_bin(double x, double y, double z, const ring_edges &edges, int n_rings, int g, int n_groups, double &s2,
+                                        double &rho2, int &f) {
+    s2 = x * x + y * y;
+    rho2 = s2 + z * z;
+    int ring = 0;
+    for (int r = 1; r < n_rings; ++r) ring = rho2 >= edges.sq[r] ? r : ring;      // edges ascend: the last hit is the largest r
+    if (g < 0 || g >= n_groups) {
+        f |= SCP_DIST_FLAG_GROUP_CLAMPED;
+        g = g < 0 ? 0 : n_groups - 1;
+    }
+    return g * n_rings + ring;
+}
+
+// host: squared edges 0 = e_0 < e_1 < .. finite, at most SCP_DIST_MAX_RINGS; a finite view
+static inline bool ring_edges_ok(const double *edges_sq, int32_t n_rings) {
+    if (!edges_sq || n_rings < 1 || n_rings > SCP_DIST_MAX_RINGS || edges_sq[0] != 0.0) return false;
+    for (int r = 1; r < n_rings; ++r)
+        if (!(edges_sq[r] > edges_sq[r - 1]) || !(edges_sq[r] <= RATE_DBL_MAX)) return false;
+    return true;
+}
+
+static inline bool ring_view_ok(const double *view) {
+    return fabs(view[0]) <= RATE_DBL_MAX && fabs(view[1]) <= RATE_DBL_MAX && fabs(view[2]) <= RATE_DBL_MAX;
+}
+
+static inline ring_edges ring_edges_arg(const double *edges_sq, int32_t n_rings) {
+    ring_edges e;
+    for (int r = 0; r < SCP_DIST_MAX_RINGS; ++r) e.sq[r] = r < n_rings ? edges_sq[r] : 0.0;
+    return e;
 }

@@ -1,4 +1,5 @@
-// Rate per range ring: every leaf's share of its ancestors' bits, summed per (rho shell, range ring) bin (gfx950, float64).
+// Rate per range ring and depth report: every leaf's share of its ancestors' bits - all of them, or those of the first D - k levels -
+// summed per (rho shell, range ring) bin (gfx950, float64).
 //
 // The rate report (rate.hip) says where the bits go per octree level, the distortion report (distreport.hip) where the error goes per
 // range ring and shell.  A level is not a place: this file attributes the bits of every node to the points below it, so that the two
@@ -8,33 +9,39 @@
 //   cost(p)   = ((share(a_1) + share(a_2)) + ..) + share(a_D), a_l = the ancestor of leaf p at level l   (root first, float64, no fma)
 //   leaf p    = in the order of scp_geom_emit_leaves: level-D node j owns the popcount(occ_j) consecutive leaves that start at the
 //               exclusive prefix sum of the popcounts of the level-D nodes before it
-//   bin       = group * n_rings + ring, ring = the largest r with rho2 >= edges_sq[r], rho2 = (x*x + y*y) + z*z of (point - view): the
-//               rule and the arithmetic of dr_split_kernel (distreport.hip); both files are compiled with -ffp-contract=off.
+//   bin       = group * n_rings + ring, ring = the largest r with rho2 >= edges_sq[r], rho2 = (x*x + y*y) + z*z of (point - view):
+//               ring_bin of rate_common.h, which dr_split_kernel (distreport.hip) calls too.
 //
-// Order contract ("Rate per ring"):
+// The depth report asks the same of a stream cut short: the symbols of levels 1 .. D - k describe the cloud at cell size 2^k, and
+//   cost_k(p) = ((share(a_1) + share(a_2)) + ..) + share(a_{D-k})    for 0 <= k < D: the operations of cost(p), the chain cut short
+//   cost_k(p) = +0.0                                                 for k >= D
+// so cost_0 is cost, and cost_k(p) is the finished sum of p's ancestor at level D - k.  Plane k of the outputs holds cost_k.
+//
+// Order contract ("Rate per ring" and "Depth report"):
 //   leaves:   integer atomics into the parent, one launch per level from the deepest up - exact, hence order-free;
 //   cost:     one launch per level from the root down; a node adds its own share to its parent's finished sum - the order of the sum is
-//             the order of the levels, no thread waits for another inside a launch;
-//   bin:      thread t of the bin's one workgroup adds rows t, t + 1024, .. of the bin in that order, then a fixed binary tree over the
-//             1024 partial sums (the contract of rate.hip / distreport.hip).
-// No floating-point atomics anywhere.  The number of launches depends on the deepest tree alone, never on node or segment counts: all
-// segments of a build go through the same launches (blockIdx.y = segment).
+//             the order of the levels, no thread waits for another inside a launch.  The level-D launch writes plane 0;
+//   planes:   for max_drop >= 1, ONE more launch in which every level-D node climbs up to max_drop parents and writes plane k of the
+//             leaves it owns from the sum of the ancestor it stands on;
+//   bin:      thread t of the (bin, plane)'s one workgroup adds rows t, t + 1024, .. of the bin in that order, then a fixed binary tree
+//             over the 1024 partial sums (rate_common.h: the contract of rate.hip / distreport.hip).
+// No floating-point atomics anywhere.  The number of launches (2 * deepest tree + 1, one more with max_drop >= 1) never depends on node
+// or segment counts: all segments of a build go through the same launches (blockIdx.y = segment).
 //
 // The node table is the caller's, so nothing in it is trusted: a validation launch checks every node before any index is followed
 // (rr_validate_kernel states what a well-formed table is) and the entry point returns SCP_EINVAL when it objects.
-#include "scp_internal.h"
+#include "rate_common.h"
 
 #define RR_THREADS 256
-#define RR_SEG_THREADS 1024
 
 struct rr_seg { int64_t node_base, n_nodes, depth, leaf_base, n_leaves; };
-struct rr_edges { double sq[SCP_DIST_MAX_RINGS]; };
 
 // A well-formed segment: the first node is the root (level 1, parent -1) and the only node of level 1; levels lie in 1 .. D and never
 // fall along the table (BFS order); a node's parent lies inside the segment in front of the node, one level up; parents never fall
 // along a level (siblings are neighbours); no occupancy byte is 0.  status[0] counts the nodes that break a rule, status[1 + s] is the
 // popcount total of segment s's level-D nodes (the host compares it with the segment's leaf count).  With these rules the prefix
-// offsets of rr_cost_kernel are exact and every leaf index it forms lies inside the segment's leaves.
+// offsets of rr_cost_kernel are exact, every leaf index it forms lies inside the segment's leaves, and a level-D node that climbs D - 1
+// parents arrives at its root.
 __global__ __launch_bounds__(RR_THREADS) void rr_validate_kernel(const uint8_t *__restrict__ occ, const uint8_t *__restrict__ level,
                                                                  const int32_t *__restrict__ parent, const rr_seg *__restrict__ segs,
                                                                  unsigned long long *__restrict__ status) {
@@ -126,75 +133,84 @@ __global__ __launch_bounds__(RR_THREADS) void rr_cost_kernel(const uint8_t *__re
     }
 }
 
-// one thread per point: the bin of dr_split_kernel, same expressions
+// one launch after the last level, for max_drop >= 1: a level-D node stands on its ancestor of level D - k after k steps up and writes
+// that node's sum to plane k of its leaves; past the root (k >= D) the plane holds +0.0.  Plane 0 is rr_cost_kernel's.
+__global__ __launch_bounds__(RR_THREADS) void rr_planes_kernel(const uint8_t *__restrict__ occ, const uint8_t *__restrict__ level,
+                                                               const int32_t *__restrict__ parent, const rr_seg *__restrict__ segs,
+                                                               int max_drop, int64_t total_leaves, const int64_t *__restrict__ off,
+                                                               const double *__restrict__ acc_ideal, const double *__restrict__ acc_table,
+                                                               double *__restrict__ cost_ideal, double *__restrict__ cost_table) {
+    const rr_seg sg = segs[blockIdx.y];
+    const int64_t j = (int64_t)blockIdx.x * RR_THREADS + threadIdx.x;
+    if (j >= sg.n_nodes) return;
+    const int64_t i = sg.node_base + j;
+    if ((int64_t)level[i] != sg.depth) return;
+    const int cnt = __popc((int)occ[i]);
+    const int64_t o = off[i];
+    if (o < 0 || o + cnt > sg.n_leaves) return;            // (never for a table the validation launch lets through)
+    int64_t a = i;
+    for (int k = 1; k <= max_drop; ++k) {
+        a = a > sg.node_base ? (int64_t)parent[a] : -1;    // the root is the segment's first node: the climb ends there
+        double vi = 0.0, vt = 0.0;
+        if (a >= sg.node_base) {
+            vi = acc_ideal[a];
+            vt = acc_table[a];
+        }
+        double *pi = cost_ideal + (int64_t)k * total_leaves + sg.leaf_base + o;
+        double *pt = cost_table + (int64_t)k * total_leaves + sg.leaf_base + o;
+        for (int c = 0; c < cnt; ++c) {
+            pi[c] = vi;
+            pt[c] = vt;
+        }
+    }
+}
+
+// one thread per point
 __global__ __launch_bounds__(RR_THREADS) void rr_bins_kernel(const double *__restrict__ a, int64_t n, double vx, double vy, double vz,
-                                                             rr_edges edges, int n_rings, const int *__restrict__ group, int n_groups,
+                                                             ring_edges edges, int n_rings, const int *__restrict__ group, int n_groups,
                                                              int *__restrict__ bin, uint8_t *__restrict__ flag) {
     const int64_t i = (int64_t)blockIdx.x * RR_THREADS + threadIdx.x;
     if (i >= n) return;
-    const double x = a[3 * i] - vx, y = a[3 * i + 1] - vy, z = a[3 * i + 2] - vz;
-    const double s2 = x * x + y * y;
-    const double rho2 = s2 + z * z;
-    int ring = 0;
-    for (int r = 1; r < n_rings; ++r) ring = rho2 >= edges.sq[r] ? r : ring;      // edges ascend: the last hit is the largest r
+    double s2, rho2;
     int f = 0;
-    int g = group ? group[i] : 0;
-    if (g < 0 || g >= n_groups) {                     // never an out-of-range bin: clamped and flagged, as in the distortion report
-        f |= SCP_DIST_FLAG_GROUP_CLAMPED;
-        g = g < 0 ? 0 : n_groups - 1;
-    }
-    bin[i] = g * n_rings + ring;
+    bin[i] = ring_bin(a[3 * i] - vx, a[3 * i + 1] - vy, a[3 * i + 2] - vz, edges, n_rings, group ? group[i] : 0, n_groups, s2, rho2, f);
     if (flag) flag[i] = (uint8_t)f;
 }
 
-// one workgroup per bin
-__global__ __launch_bounds__(RR_SEG_THREADS) void rr_segments_kernel(const double *__restrict__ cost_ideal, const double *__restrict__ cost_table,
-                                                                     const int64_t *__restrict__ order, int64_t n,
-                                                                     const int64_t *__restrict__ seg_off, scp_share_seg *__restrict__ out) {
-    __shared__ double s_ideal[RR_SEG_THREADS], s_table[RR_SEG_THREADS], s_mx[RR_SEG_THREADS];
-    __shared__ int s_rows[RR_SEG_THREADS];
+// one workgroup per (bin, plane): plane blockIdx.y of the costs starts at blockIdx.y * plane_stride
+__global__ __launch_bounds__(RATE_SEG_THREADS) void rr_segments_kernel(const double *__restrict__ cost_ideal, const double *__restrict__ cost_table,
+                                                                       const int64_t *__restrict__ order, int64_t n,
+                                                                       const int64_t *__restrict__ seg_off, int64_t plane_stride,
+                                                                       scp_share_seg *__restrict__ out) {
+    __shared__ double s_ideal[RATE_SEG_THREADS], s_table[RATE_SEG_THREADS];
+    __shared__ rate_max s_mx[RATE_SEG_THREADS];
+    __shared__ int s_rows[RATE_SEG_THREADS];
     const int t = threadIdx.x;
-    // the offsets and the order live in device memory, so nobody has checked them: clamped to the table, a row outside it is skipped
-    int64_t lo = seg_off[blockIdx.x], hi = seg_off[blockIdx.x + 1];
-    lo = lo < 0 ? 0 : (lo > n ? n : lo);
-    hi = hi < lo ? lo : (hi > n ? n : hi);
+    const double *ci = cost_ideal + (int64_t)blockIdx.y * plane_stride, *ct = cost_table + (int64_t)blockIdx.y * plane_stride;
+    // the order lives in device memory like the offsets, so nobody has checked it: a row outside the table is skipped
+    int64_t lo, hi;
+    rate_seg_bounds(seg_off, blockIdx.x, n, lo, hi);
     double ideal = 0.0, table = 0.0, mx = 0.0;
     int rows = 0;
-    for (int64_t p = lo + t; p < hi; p += RR_SEG_THREADS) {
+    for (int64_t p = lo + t; p < hi; p += RATE_SEG_THREADS) {
         const int64_t i = order ? order[p] : p;
         if (i < 0 || i >= n) continue;
-        const double c = cost_ideal[i];
+        const double c = ci[i];
         ++rows;
         ideal += c;
-        table += cost_table[i];
+        table += ct[i];
         mx = c > mx ? c : mx;
     }
-    s_ideal[t] = ideal; s_table[t] = table; s_mx[t] = mx; s_rows[t] = rows;
-    __syncthreads();
-    for (int h = RR_SEG_THREADS / 2; h >= 1; h >>= 1) {
-        if (t < h) {
-            s_ideal[t] += s_ideal[t + h];
-            s_table[t] += s_table[t + h];
-            s_mx[t] = s_mx[t + h] > s_mx[t] ? s_mx[t + h] : s_mx[t];
-            s_rows[t] += s_rows[t + h];
-        }
-        __syncthreads();
-    }
+    s_ideal[t] = ideal; s_table[t] = table; s_mx[t].v = mx; s_rows[t] = rows;
+    rate_block_tree(t, s_ideal, s_table, s_mx, s_rows);
     if (t == 0) {
         scp_share_seg o;
         o.leaves = s_rows[0];
         o.ideal_bits = s_ideal[0];
         o.table_bits = s_table[0];
-        o.max_ideal_bits = s_mx[0];
-        out[blockIdx.x] = o;
+        o.max_ideal_bits = s_mx[0].v;
+        out[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = o;
     }
-}
-
-static bool rr_edges_ok(const double *edges_sq, int32_t n_rings) {
-    if (!edges_sq || n_rings < 1 || n_rings > SCP_DIST_MAX_RINGS || edges_sq[0] != 0.0) return false;
-    for (int r = 1; r < n_rings; ++r)
-        if (!(edges_sq[r] > edges_sq[r - 1]) || !(edges_sq[r] <= 1.79769313486231570815e308)) return false;
-    return true;
 }
 
 static inline int64_t rr_align(int64_t b) { return (b + 255) / 256 * 256; }
@@ -205,14 +221,17 @@ extern "C" SCP_API int64_t scp_rate_leaf_share_workspace_bytes(int64_t total_nod
     return rr_head_bytes(nseg) + 3 * rr_align(8 * total_nodes);      // segment table + status | off | acc_ideal | acc_table
 }
 
-/* leaves per node and every leaf's share of its ancestors' bits: see include/scp.h */
-extern "C" SCP_API int scp_rate_leaf_share(const uint8_t *occ, const uint8_t *level, const int32_t *parent, int64_t total_nodes,
-                                           const double *bits_ideal, const double *bits_table, const int64_t *segs, int32_t nseg,
-                                           int64_t total_leaves, int64_t *leaves, double *cost_ideal, double *cost_table, void *workspace,
-                                           int64_t workspace_bytes, void *stream) {
+extern "C" SCP_API int64_t scp_rate_depth_share_workspace_bytes(int64_t total_nodes, int32_t nseg) {
+    return scp_rate_leaf_share_workspace_bytes(total_nodes, nseg);
+}
+
+// the tree pass of both entry points: planes 0 .. max_drop of cost_ideal / cost_table, total_leaves apart
+static int rr_tree_pass(const uint8_t *occ, const uint8_t *level, const int32_t *parent, int64_t total_nodes, const double *bits_ideal,
+                        const double *bits_table, const int64_t *segs, int32_t nseg, int64_t total_leaves, int32_t max_drop, int64_t *leaves,
+                        double *cost_ideal, double *cost_table, void *workspace, int64_t workspace_bytes, void *stream) {
     if (!occ || !level || !parent || !bits_ideal || !bits_table || !segs || !leaves || !cost_ideal || !cost_table || !workspace) return SCP_EINVAL;
     if (total_nodes < 1 || total_nodes > SCP_SHARE_MAX_NODES || total_leaves < 1 || total_leaves > SCP_SHARE_MAX_NODES) return SCP_EINVAL;
-    if (nseg < 1 || nseg > SCP_MAX_SEGMENTS || (((uintptr_t)workspace) & 7)) return SCP_EINVAL;
+    if (nseg < 1 || nseg > SCP_MAX_SEGMENTS || (((uintptr_t)workspace) & 7) || max_drop < 0 || max_drop > SCP_MAX_DEPTH) return SCP_EINVAL;
     if (workspace_bytes < scp_rate_leaf_share_workspace_bytes(total_nodes, nseg)) return SCP_EINVAL;
     // the segments tile the node table and the leaf table, in this order, each with at least one node and one leaf
     rr_seg host[SCP_MAX_SEGMENTS];
@@ -260,30 +279,57 @@ extern "C" SCP_API int scp_rate_leaf_share(const uint8_t *occ, const uint8_t *le
                            acc_ideal, acc_table, cost_ideal, cost_table);
         LAUNCH_CHECK();
     }
+    if (max_drop >= 1) {
+        hipLaunchKernelGGL(rr_planes_kernel, grid, dim3(RR_THREADS), 0, st, occ, level, parent, d_segs, (int)max_drop, total_leaves, off, acc_ideal,
+                           acc_table, cost_ideal, cost_table);
+        LAUNCH_CHECK();
+    }
     return SCP_OK;
+}
+
+/* leaves per node and every leaf's share of its ancestors' bits: see include/scp.h */
+extern "C" SCP_API int scp_rate_leaf_share(const uint8_t *occ, const uint8_t *level, const int32_t *parent, int64_t total_nodes,
+                                           const double *bits_ideal, const double *bits_table, const int64_t *segs, int32_t nseg,
+                                           int64_t total_leaves, int64_t *leaves, double *cost_ideal, double *cost_table, void *workspace,
+                                           int64_t workspace_bytes, void *stream) {
+    return rr_tree_pass(occ, level, parent, total_nodes, bits_ideal, bits_table, segs, nseg, total_leaves, 0, leaves, cost_ideal, cost_table,
+                        workspace, workspace_bytes, stream);
+}
+
+/* every leaf's share of the bits of levels 1 .. D - k, k = 0 .. max_drop: see include/scp.h */
+extern "C" SCP_API int scp_rate_depth_share(const uint8_t *occ, const uint8_t *level, const int32_t *parent, int64_t total_nodes,
+                                            const double *bits_ideal, const double *bits_table, const int64_t *segs, int32_t nseg,
+                                            int64_t total_leaves, int32_t max_drop, int64_t *leaves, double *cost_ideal, double *cost_table,
+                                            void *workspace, int64_t workspace_bytes, void *stream) {
+    return rr_tree_pass(occ, level, parent, total_nodes, bits_ideal, bits_table, segs, nseg, total_leaves, max_drop, leaves, cost_ideal,
+                        cost_table, workspace, workspace_bytes, stream);
 }
 
 /* (group, ring) bin per point: see include/scp.h */
 extern "C" SCP_API int scp_ring_bins_f64(const double *xyz, int64_t n, const double *view, const double *edges_sq, int32_t n_rings,
                                          const int32_t *group, int32_t n_groups, int32_t *bin_out, uint8_t *flag_out, void *stream) {
     if (!xyz || !view || !bin_out || n <= 0 || n > SCP_DIST_MAX_POINTS || n_groups < 1) return SCP_EINVAL;
-    if (!rr_edges_ok(edges_sq, n_rings) || (int64_t)n_groups * n_rings > SCP_DIST_MAX_BINS) return SCP_EINVAL;
-    if (!(fabs(view[0]) <= 1.79769313486231570815e308) || !(fabs(view[1]) <= 1.79769313486231570815e308) || !(fabs(view[2]) <= 1.79769313486231570815e308))
-        return SCP_EINVAL;
-    rr_edges e;
-    for (int r = 0; r < SCP_DIST_MAX_RINGS; ++r) e.sq[r] = r < n_rings ? edges_sq[r] : 0.0;
+    if (!ring_edges_ok(edges_sq, n_rings) || (int64_t)n_groups * n_rings > SCP_DIST_MAX_BINS || !ring_view_ok(view)) return SCP_EINVAL;
     hipLaunchKernelGGL(rr_bins_kernel, dim3((unsigned)cdiv64(n, RR_THREADS)), dim3(RR_THREADS), 0, (hipStream_t)stream, xyz, n, view[0], view[1], view[2],
-                       e, (int)n_rings, group, (int)n_groups, bin_out, flag_out);
+                       ring_edges_arg(edges_sq, n_rings), (int)n_rings, group, (int)n_groups, bin_out, flag_out);
     LAUNCH_CHECK();
     return SCP_OK;
 }
 
-/* per-bin records of bin-ordered leaf costs: see include/scp.h */
-extern "C" SCP_API int scp_share_segments_f64(const double *cost_ideal, const double *cost_table, const int64_t *order, int64_t n,
-                                              const int64_t *seg_off, int32_t n_bins, scp_share_seg *out, void *stream) {
+/* per-(depth, bin) records of bin-ordered leaf cost planes: see include/scp.h */
+extern "C" SCP_API int scp_share_segments_depth_f64(const double *cost_ideal, const double *cost_table, const int64_t *order, int64_t n,
+                                                    const int64_t *seg_off, int32_t n_bins, int32_t n_depths, int64_t plane_stride,
+                                                    scp_share_seg *out, void *stream) {
     if (!cost_ideal || !cost_table || !seg_off || !out || n <= 0 || n > SCP_DIST_MAX_POINTS || n_bins < 1 || n_bins > SCP_DIST_MAX_BINS) return SCP_EINVAL;
-    hipLaunchKernelGGL(rr_segments_kernel, dim3((unsigned)n_bins), dim3(RR_SEG_THREADS), 0, (hipStream_t)stream, cost_ideal, cost_table, order, n,
-                       seg_off, out);
+    if (n_depths < 1 || n_depths > SCP_MAX_DEPTH + 1 || plane_stride < n || plane_stride > SCP_SHARE_MAX_NODES) return SCP_EINVAL;
+    hipLaunchKernelGGL(rr_segments_kernel, dim3((unsigned)n_bins, (unsigned)n_depths), dim3(RATE_SEG_THREADS), 0, (hipStream_t)stream, cost_ideal,
+                       cost_table, order, n, seg_off, plane_stride, out);
     LAUNCH_CHECK();
     return SCP_OK;
+}
+
+/* per-bin records of bin-ordered leaf costs, the one-plane launch: see include/scp.h */
+extern "C" SCP_API int scp_share_segments_f64(const double *cost_ideal, const double *cost_table, const int64_t *order, int64_t n,
+                                              const int64_t *seg_off, int32_t n_bins, scp_share_seg *out, void *stream) {
+    return scp_share_segments_depth_f64(cost_ideal, cost_table, order, n, seg_off, n_bins, 1, n, out, stream);
 }

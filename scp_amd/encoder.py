@@ -657,6 +657,24 @@ class FrameEncoder(_FrontEnd):
         rep["shell_leaves"] = [int(p.shape[0]) for p in pts]
         return rep
 
+    def _ring_frame(self, who, xyz_dev, edges, infos):
+        """What `ring_rate` and `depth_report` (who) start from: the refusals of an encoder or a call that kept no rows; then the resolved
+        edges, the reconstructed points per shell, the (shell, ring) bin of every one of them in leaf order, and the input points per
+        ring (device int64 [rings])."""
+        from . import metrics
+        if not (self.rate and self.rate_rows):
+            raise native.ScpError(f"{who} needs the per-row bits of the frame: make the encoder with rate=True and rate_rows=True (rate alone "
+                                  "keeps per-level sums only)")
+        if self._rate_rows is None:
+            raise native.ScpError(f"{who}: no frame to report on - call it after a synchronous encode / encode_ints (the asynchronous and "
+                                  "batch calls, and the record files of --preproc_path, leave no geometry and no rows behind)")
+        edges = native.dist_edges(metrics.default_edges(self.data_type) if edges is None else edges)
+        pts = self._reconstructed(infos)
+        group = torch.cat([torch.full((p.shape[0],), g, dtype=torch.int32, device=p.device) for g, p in enumerate(pts)])
+        bins = native.ring_bins(torch.cat(pts), edges, group, len(pts))
+        points = torch.bincount(native.ring_bins(xyz_dev[:, :3], edges), minlength=len(edges))
+        return edges, pts, bins, points
+
     def _share_args(self):
         """The arguments of native.rate_leaf_share for the frame whose rows `_rate_rows` holds: the node columns of the geometry, what
         every node cost (ideal, table), the segment table and the number of leaves."""
@@ -677,19 +695,9 @@ class FrameEncoder(_FrontEnd):
         groups[shell][ring] (leaves, ideal_bits, table_bits, max_ideal_bits, ideal / table bits per leaf), rings[ring] (the shells
         added with math.fsum, and `points`: the input points whose own range lies in the ring), total, shell_leaves."""
         from . import metrics
-        if not (self.rate and self.rate_rows):
-            raise native.ScpError("ring_rate needs the per-row bits of the frame: make the encoder with rate=True and rate_rows=True (rate alone "
-                                  "keeps per-level sums only)")
-        if self._rate_rows is None:
-            raise native.ScpError("ring_rate: no frame to report on - call it after a synchronous encode / encode_ints (the asynchronous and "
-                                  "batch calls, and the record files of --preproc_path, leave no geometry and no rows behind)")
-        edges = native.dist_edges(metrics.default_edges(self.data_type) if edges is None else edges)
+        edges, pts, bins, points = self._ring_frame("ring_rate", xyz_dev, edges, infos)
         share = native.rate_leaf_share(*self._share_args())
-        pts = self._reconstructed(infos)
-        group = torch.cat([torch.full((p.shape[0],), k, dtype=torch.int32, device=p.device) for k, p in enumerate(pts)])
-        bins = native.ring_bins(torch.cat(pts), edges, group, len(pts))
         raw = native.share_segments(share["cost_ideal"], share["cost_table"], bins, len(pts) * len(edges))["raw"]
-        points = torch.bincount(native.ring_bins(xyz_dev[:, :3], edges), minlength=len(edges))
         rep = metrics.ring_rate_dict(edges, raw.cpu().numpy(), points.cpu().tolist(), len(pts))
         rep["shell_leaves"] = [int(p.shape[0]) for p in pts]
         return rep
@@ -716,7 +724,7 @@ class FrameEncoder(_FrontEnd):
 
     def depth_report(self, xyz_dev, max_drop=4, edges=None, infos=None):
         """What every octree level of the frame just encoded costs and buys ("Depth report"): for every truncation depth
-        k = 0 .. max_drop the bits of levels 1 .. D - k per range ring and rho shell (csrc/depthshare.hip: `ring_rate` with every leaf's
+        k = 0 .. max_drop the bits of levels 1 .. D - k per range ring and rho shell (csrc/ringrate.hip: `ring_rate` with every leaf's
         chain of ancestors cut k levels short, on ring_rate's bins - those of the FINEST reconstructed leaf, so that the columns of
         different k compare) and the D1 error of the cloud those levels describe: the centres of the level-(D - k + 1) nodes, through the
         encoder's own dequantiser.  Callable where `ring_rate` is.  max_drop: 0 .. the shallowest shell's depth - 1.  -> plain Python:
@@ -724,25 +732,15 @@ class FrameEncoder(_FrontEnd):
         metrics.distortion_report of the LOD-k points against the input with groups = shells, d1 = metrics.chamfer_psnr of the same
         pair)."""
         from . import metrics
-        if not (self.rate and self.rate_rows):
-            raise native.ScpError("depth_report needs the per-row bits of the frame: make the encoder with rate=True and rate_rows=True (rate "
-                                  "alone keeps per-level sums only)")
-        if self._rate_rows is None:
-            raise native.ScpError("depth_report: no frame to report on - call it after a synchronous encode / encode_ints (the asynchronous and "
-                                  "batch calls, and the record files of --preproc_path, leave no geometry and no rows behind)")
+        edges, pts, bins, points = self._ring_frame("depth_report", xyz_dev, edges, infos)
         depths = [int(i.depth) for i in self.geom.info]
         if isinstance(max_drop, bool) or not isinstance(max_drop, int) or not 0 <= max_drop <= min(depths) - 1:
             raise native.ScpError(f"depth_report: max_drop {max_drop!r} outside 0 .. {min(depths) - 1}: the shells of this frame are {depths} levels "
                                   "deep and a tree keeps at least its root level")
-        edges = native.dist_edges(metrics.default_edges(self.data_type) if edges is None else edges)
         share = native.rate_depth_share(*self._share_args(), max_drop)
-        infos = infos or self._infos
-        pts = self._reconstructed(infos)
-        S = len(pts)
-        group = torch.cat([torch.full((p.shape[0],), g, dtype=torch.int32, device=p.device) for g, p in enumerate(pts)])
-        bins = native.ring_bins(torch.cat(pts), edges, group, S)
+        infos, S = infos or self._infos, len(pts)
         raw = native.share_segments_depth(share["cost_ideal"], share["cost_table"], bins, S * len(edges))["raw"].cpu().numpy()
-        points = torch.bincount(native.ring_bins(xyz_dev[:, :3], edges), minlength=len(edges)).cpu().tolist()
+        points = points.cpu().tolist()
         peak, cells, dist, d1 = metrics.PEAK.get(self.data_type, 1.0), [], [], []
         for k in range(max_drop + 1):
             ck = self.lod_cells(k)

@@ -1892,6 +1892,33 @@ def dist_edges(edges):
     return e
 
 
+def _ring_args(fn, clouds, edges, group, n_groups, view):
+    """The ring arguments of `fn` (nn_error_split, ring_bins), checked: the clouds, of which the first one is binned; the edges and the
+    groups; the group of every point of the first cloud and its extremes (one read-back); the view.  -> (the clouds in float64, the
+    arguments view, edges_sq, n_rings of the C entry point, the contiguous group tensor or None, n_groups)."""
+    e = dist_edges(edges)
+    n_groups = int(n_groups)
+    if n_groups < 1 or n_groups * len(e) > DIST_MAX_BINS:
+        raise ScpError(f"{fn}: {n_groups} groups x {len(e)} rings: between 1 and {DIST_MAX_BINS} bins expected")
+    clouds = [_dev_f64(c) for c in clouds]
+    if any(c.dim() != 2 or c.shape[1] != 3 or c.shape[0] < 1 for c in clouds):
+        raise ScpError(f"{fn}: clouds of shape [n,3] with n >= 1 expected, got " + " and ".join(str(tuple(c.shape)) for c in clouds))
+    n = clouds[0].shape[0]
+    if group is not None:
+        if not group.is_cuda or group.dtype != torch.int32 or tuple(group.shape) != (n,):
+            raise ScpError(f"{fn}: group is a device int32 tensor with one entry per binned point ({n})")
+        group = group.contiguous()
+        lo, hi = int(group.min().item()), int(group.max().item())
+        if lo < 0 or hi >= n_groups:
+            raise ScpError(f"{fn}: group values {lo} .. {hi} outside 0 .. {n_groups - 1}")
+    view = tuple(float(c) for c in view)
+    if len(view) != 3 or not all(abs(c) < float("inf") for c in view):
+        raise ScpError(f"{fn}: view is the sensor position, three finite numbers, got {view}")
+    v = (C.c_double * 3)(*view)
+    esq = (C.c_double * len(e))(*[c * c for c in e])
+    return clouds, (C.cast(v, _vp), C.cast(esq, _vp), len(e)), group, n_groups
+
+
 def nn_error_split(a, b, edges, group=None, n_groups=1, view=(0.0, 0.0, 0.0)):
     """scp_nn_error_split_f64 (csrc/distreport.hip).  a [na,3], b [nb,3] device tensors (compared in float64); edges: host list 0 = E_0 <
     E_1 < ..; group int32 [na] device tensor with 0 <= group < n_groups (None: all 0); view: the sensor, three host numbers.  -> dict of
@@ -1899,36 +1926,25 @@ def nn_error_split(a, b, edges, group=None, n_groups=1, view=(0.0, 0.0, 0.0)):
     e_theta of e = b[idx] - a), bin int32 [na] (group * len(edges) + ring), axis bool [na] (no local frame: on the sensor's axis), flag
     uint8 [na] (the DIST_FLAG_* bits).  Everything is checked before the launch; a group value out of range is refused here (one read-back
     of the group's extremes), and the kernel would clamp and flag it."""
-    e = dist_edges(edges)
-    n_groups = int(n_groups)
-    if n_groups < 1 or n_groups * len(e) > DIST_MAX_BINS:
-        raise ScpError(f"nn_error_split: {n_groups} groups x {len(e)} rings: between 1 and {DIST_MAX_BINS} bins expected")
-    a, b = _dev_f64(a), _dev_f64(b)
-    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != 3 or b.shape[1] != 3 or a.shape[0] < 1 or b.shape[0] < 1:
-        raise ScpError(f"nn_error_split: clouds of shape [n,3] with n >= 1 expected, got {tuple(a.shape)} and {tuple(b.shape)}")
-    na = a.shape[0]
-    if group is not None:
-        if not group.is_cuda or group.dtype != torch.int32 or tuple(group.shape) != (na,):
-            raise ScpError(f"nn_error_split: group is a device int32 tensor with one entry per query ({na})")
-        group = group.contiguous()
-        lo, hi = int(group.min().item()), int(group.max().item())
-        if lo < 0 or hi >= n_groups:
-            raise ScpError(f"nn_error_split: group values {lo} .. {hi} outside 0 .. {n_groups - 1}")
-    view = tuple(float(c) for c in view)
-    if len(view) != 3 or not all(abs(c) < float("inf") for c in view):
-        raise ScpError(f"nn_error_split: view is the sensor position, three finite numbers, got {view}")
-    v = (C.c_double * 3)(*view)
-    esq = (C.c_double * len(e))(*[c * c for c in e])
-    dev = a.device
+    (a, b), ring, group, n_groups = _ring_args("nn_error_split", (a, b), edges, group, n_groups, view)
+    na, dev = a.shape[0], a.device
     idx = torch.empty((na,), dtype=torch.int32, device=dev)
     d2 = torch.empty((na,), dtype=torch.float64, device=dev)
     comp = torch.empty((na, 3), dtype=torch.float64, device=dev)
     bin_ = torch.empty((na,), dtype=torch.int32, device=dev)
     flag = torch.empty((na,), dtype=torch.uint8, device=dev)
-    _check(lib().scp_nn_error_split_f64(a.data_ptr(), na, b.data_ptr(), b.shape[0], C.cast(v, _vp), C.cast(esq, _vp), len(e),
-                                        None if group is None else group.data_ptr(), n_groups, idx.data_ptr(), d2.data_ptr(), comp.data_ptr(),
-                                        bin_.data_ptr(), flag.data_ptr(), _stream()), "scp_nn_error_split_f64")
+    _check(lib().scp_nn_error_split_f64(a.data_ptr(), na, b.data_ptr(), b.shape[0], *ring, None if group is None else group.data_ptr(), n_groups,
+                                        idx.data_ptr(), d2.data_ptr(), comp.data_ptr(), bin_.data_ptr(), flag.data_ptr(), _stream()),
+           "scp_nn_error_split_f64")
     return dict(idx=idx, d2=d2, comp=comp, bin=bin_, axis=(flag & DIST_FLAG_AXIS) != 0, flag=flag)
+
+
+def _bin_order(bins, n_bins):
+    """int32 bins [n] in any order -> (order int64 [n], seg_off int64 [n_bins + 1]): a stable sort brings every bin's rows together in
+    index order, which the summation order contract needs; bin b owns order[seg_off[b] : seg_off[b + 1]]."""
+    ordered, order = torch.sort(bins, stable=True)
+    seg_off = torch.searchsorted(ordered, torch.arange(n_bins + 1, dtype=torch.int32, device=bins.device)).to(torch.int64).contiguous()
+    return order, seg_off
 
 
 def dist_segments(d2, comp, flag, bins, n_bins):
@@ -1948,8 +1964,7 @@ def dist_segments(d2, comp, flag, bins, n_bins):
         raise ScpError(f"dist_segments: d2 [n], comp [n,3], flag [n], bins [n] with n >= 1 expected, got {tuple(d2.shape)}, {tuple(comp.shape)}, "
                        f"{tuple(flag.shape)}, {tuple(bins.shape)}")
     d2, comp, flag = d2.contiguous(), comp.contiguous(), flag.contiguous()
-    ordered, order = torch.sort(bins, stable=True)
-    seg_off = torch.searchsorted(ordered, torch.arange(n_bins + 1, dtype=torch.int32, device=bins.device)).to(torch.int64).contiguous()
+    order, seg_off = _bin_order(bins, n_bins)
     raw = torch.empty((n_bins, len(DIST_FIELDS) + DIST_HIST), dtype=torch.int64, device=d2.device)
     _check(lib().scp_dist_segments_f64(d2.data_ptr(), comp.data_ptr(), flag.data_ptr(), order.data_ptr(), n, seg_off.data_ptr(), n_bins,
                                        raw.data_ptr(), _stream()), "scp_dist_segments_f64")
@@ -1967,7 +1982,7 @@ def dist_record_views(raw):
     return out
 
 
-# ------------------------------------------------------------------------------------------------- rate per ring (csrc/ringrate.hip)
+# ------------------------------------------------------------------------------------------------- rate per ring, depth report (csrc/ringrate.hip)
 SHARE_FIELDS = ("leaves", "ideal_bits", "table_bits", "max_ideal_bits")     # include/scp.h: scp_share_seg, four 8-byte fields
 MAX_SEGMENTS = 62                                                           # include/scp.h: SCP_MAX_SEGMENTS
 
@@ -1998,62 +2013,93 @@ def node_bits(order, node_of_row, row_ideal, row_table, total_nodes):
     return ideal, table
 
 
+def _tree_pass(fn, occ, level, parent, bits_ideal, bits_table, segs, total_leaves, max_drop=None):
+    """The tree pass of rate_leaf_share (max_drop None: scp_rate_leaf_share, costs [total_leaves]) and of rate_depth_share
+    (scp_rate_depth_share, costs [max_drop + 1, total_leaves]): the five node columns and the [S,4] table checked, the workspace and the
+    outputs made, the entry point called.  `fn` names the caller in messages and, behind `scp_`, its C entry point."""
+    N = int(occ.shape[0])
+    for t, dt, name in ((occ, torch.uint8, "occ"), (level, torch.uint8, "level"), (parent, torch.int32, "parent"),
+                        (bits_ideal, torch.float64, "bits_ideal"), (bits_table, torch.float64, "bits_table")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != (N,):
+            raise ScpError(f"{fn}: {name} is a device tensor of {dt} with one entry per node ({N})")
+    segs = np.ascontiguousarray(segs, np.int64)
+    if segs.ndim != 2 or segs.shape[1] != 4:
+        raise ScpError(f"{fn}: the segment table is int64 [S,4] (node_base, n_nodes, depth, leaf_base), got {segs.shape}")
+    planes = ()
+    if max_drop is not None:
+        max_drop = int(max_drop)
+        if max_drop < 0 or max_drop > MAX_DEPTH:
+            raise ScpError(f"{fn}: max_drop {max_drop} outside 0 .. {MAX_DEPTH}")
+        planes = (max_drop + 1,)
+    S, total_leaves = int(segs.shape[0]), int(total_leaves)
+    ws_bytes = int(getattr(lib(), f"scp_{fn}_workspace_bytes")(N, S))
+    if ws_bytes < 0:
+        raise ScpError(f"{fn}: {N} nodes in {S} segments: 1 .. 2^30 nodes in 1 .. {MAX_SEGMENTS} segments expected")
+    dev = occ.device
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    leaves = torch.empty(N, dtype=torch.int64, device=dev)
+    ci = torch.empty(planes + (max(total_leaves, 0),), dtype=torch.float64, device=dev)
+    ct = torch.empty(planes + (max(total_leaves, 0),), dtype=torch.float64, device=dev)
+    rc = getattr(lib(), f"scp_{fn}")(_dev(occ), _dev(level), _dev(parent), N, _dev(bits_ideal), _dev(bits_table), segs.ctypes.data, S, total_leaves,
+                                     *(() if max_drop is None else (max_drop,)), leaves.data_ptr(), ci.data_ptr(), ct.data_ptr(), ws.data_ptr(),
+                                     ws_bytes, _stream())
+    _check(rc, f"scp_{fn}")
+    return dict(leaves=leaves, cost_ideal=ci, cost_table=ct)
+
+
 def rate_leaf_share(occ, level, parent, bits_ideal, bits_table, segs, total_leaves):
     """scp_rate_leaf_share: every leaf's share of its ancestors' bits (include/scp.h states the definition).  occ / level uint8, parent
     int32, bits_ideal / bits_table float64: device tensors [N], the node columns of all segments of a build (Geom.nodes) and what every
     node cost; segs: host int64 [S,4] (node_base, n_nodes, depth, leaf_base) - share_table(geom.info).  -> dict of device tensors: leaves
     int64 [N], cost_ideal / cost_table float64 [total_leaves] (segment-major, the order of Geom.leaves inside a segment).  A table the
     library's validation pass objects to raises ScpError (SCP_EINVAL); the call waits for the stream once."""
-    N = int(occ.shape[0])
-    for t, dt, name in ((occ, torch.uint8, "occ"), (level, torch.uint8, "level"), (parent, torch.int32, "parent"),
-                        (bits_ideal, torch.float64, "bits_ideal"), (bits_table, torch.float64, "bits_table")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != (N,):
-            raise ScpError(f"rate_leaf_share: {name} is a device tensor of {dt} with one entry per node ({N})")
-    segs = np.ascontiguousarray(segs, np.int64)
-    if segs.ndim != 2 or segs.shape[1] != 4:
-        raise ScpError(f"rate_leaf_share: the segment table is int64 [S,4] (node_base, n_nodes, depth, leaf_base), got {segs.shape}")
-    S, total_leaves = int(segs.shape[0]), int(total_leaves)
-    ws_bytes = int(lib().scp_rate_leaf_share_workspace_bytes(N, S))
-    if ws_bytes < 0:
-        raise ScpError(f"rate_leaf_share: {N} nodes in {S} segments: 1 .. 2^30 nodes in 1 .. {MAX_SEGMENTS} segments expected")
-    dev = occ.device
-    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
-    leaves = torch.empty(N, dtype=torch.int64, device=dev)
-    ci = torch.empty(max(total_leaves, 0), dtype=torch.float64, device=dev)
-    ct = torch.empty(max(total_leaves, 0), dtype=torch.float64, device=dev)
-    rc = lib().scp_rate_leaf_share(_dev(occ), _dev(level), _dev(parent), N, _dev(bits_ideal), _dev(bits_table), segs.ctypes.data, S, total_leaves,
-                                   leaves.data_ptr(), ci.data_ptr(), ct.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
-    _check(rc, "scp_rate_leaf_share")
-    return dict(leaves=leaves, cost_ideal=ci, cost_table=ct)
+    return _tree_pass("rate_leaf_share", occ, level, parent, bits_ideal, bits_table, segs, total_leaves)
+
+
+def rate_depth_share(occ, level, parent, bits_ideal, bits_table, segs, total_leaves, max_drop):
+    """scp_rate_depth_share: every leaf's share of the bits of levels 1 .. D - k for k = 0 .. max_drop (include/scp.h states the
+    definition); the arguments of rate_leaf_share plus max_drop (0 .. MAX_DEPTH).  -> dict of device tensors: leaves int64 [N],
+    cost_ideal / cost_table float64 [max_drop + 1, total_leaves] (plane k = cost_k; plane 0 = rate_leaf_share's costs bit for bit; a plane
+    with k >= a segment's depth holds +0.0 there).  A table the library's validation pass objects to raises ScpError (SCP_EINVAL)."""
+    return _tree_pass("rate_depth_share", occ, level, parent, bits_ideal, bits_table, segs, total_leaves, max_drop)
 
 
 def ring_bins(xyz, edges, group=None, n_groups=1, view=(0.0, 0.0, 0.0)):
     """scp_ring_bins_f64: the (group, ring) bin of every point of a cloud [n,3] (device, compared in float64) - the bins nn_error_split
     gives its queries, integer for integer; edges / group / n_groups / view as there.  -> device int32 [n]."""
-    e = dist_edges(edges)
-    n_groups = int(n_groups)
-    if n_groups < 1 or n_groups * len(e) > DIST_MAX_BINS:
-        raise ScpError(f"ring_bins: {n_groups} groups x {len(e)} rings: between 1 and {DIST_MAX_BINS} bins expected")
-    a = _dev_f64(xyz)
-    if a.dim() != 2 or a.shape[1] != 3 or a.shape[0] < 1:
-        raise ScpError(f"ring_bins: a cloud of shape [n,3] with n >= 1 expected, got {tuple(a.shape)}")
+    (a,), ring, group, n_groups = _ring_args("ring_bins", (xyz,), edges, group, n_groups, view)
     n = a.shape[0]
-    if group is not None:
-        if not group.is_cuda or group.dtype != torch.int32 or tuple(group.shape) != (n,):
-            raise ScpError(f"ring_bins: group is a device int32 tensor with one entry per point ({n})")
-        group = group.contiguous()
-        lo, hi = int(group.min().item()), int(group.max().item())
-        if lo < 0 or hi >= n_groups:
-            raise ScpError(f"ring_bins: group values {lo} .. {hi} outside 0 .. {n_groups - 1}")
-    view = tuple(float(c) for c in view)
-    if len(view) != 3 or not all(abs(c) < float("inf") for c in view):
-        raise ScpError(f"ring_bins: view is the sensor position, three finite numbers, got {view}")
-    v = (C.c_double * 3)(*view)
-    esq = (C.c_double * len(e))(*[c * c for c in e])
     bin_ = torch.empty((n,), dtype=torch.int32, device=a.device)
-    _check(lib().scp_ring_bins_f64(a.data_ptr(), n, C.cast(v, _vp), C.cast(esq, _vp), len(e), None if group is None else group.data_ptr(), n_groups,
-                                   bin_.data_ptr(), None, _stream()), "scp_ring_bins_f64")
+    _check(lib().scp_ring_bins_f64(a.data_ptr(), n, *ring, None if group is None else group.data_ptr(), n_groups, bin_.data_ptr(), None, _stream()),
+           "scp_ring_bins_f64")
     return bin_
+
+
+def _share_segments(fn, cost_ideal, cost_table, bins, n_bins, planes):
+    """share_segments (planes False: costs [n], scp_share_segments_f64) and share_segments_depth (costs [K, n], one launch of
+    scp_share_segments_depth_f64) -> dict of views of `raw` int64 [n_bins, 4] / [K, n_bins, 4], and raw."""
+    n_bins = int(n_bins)
+    if n_bins < 1 or n_bins > DIST_MAX_BINS:
+        raise ScpError(f"{fn}: between 1 and {DIST_MAX_BINS} bins expected, got {n_bins}")
+    for t, dt, name in ((cost_ideal, torch.float64, "cost_ideal"), (cost_table, torch.float64, "cost_table"), (bins, torch.int32, "bins")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
+            raise ScpError(f"{fn}: {name} is a device tensor of {dt} (there is no CPU path in the product)")
+    want = "[K, n]" if planes else "[n]"
+    if cost_ideal.dim() != 1 + planes or cost_ideal.shape[-1] < 1 or cost_table.shape != cost_ideal.shape or tuple(bins.shape) != (cost_ideal.shape[-1],):
+        raise ScpError(f"{fn}: cost_ideal {want}, cost_table {want}, bins [n] with n >= 1 expected, got {tuple(cost_ideal.shape)}, "
+                       f"{tuple(cost_table.shape)}, {tuple(bins.shape)}")
+    n = int(cost_ideal.shape[-1])
+    if planes and not 1 <= cost_ideal.shape[0] <= MAX_DEPTH + 1:
+        raise ScpError(f"{fn}: between 1 and {MAX_DEPTH + 1} planes expected, got {cost_ideal.shape[0]}")
+    cost_ideal, cost_table = cost_ideal.contiguous(), cost_table.contiguous()
+    order, seg_off = _bin_order(bins, n_bins)
+    raw = torch.empty(tuple(cost_ideal.shape[:-1]) + (n_bins, len(SHARE_FIELDS)), dtype=torch.int64, device=cost_ideal.device)
+    args = (cost_ideal.data_ptr(), cost_table.data_ptr(), order.data_ptr(), n, seg_off.data_ptr(), n_bins)
+    if planes:
+        _check(lib().scp_share_segments_depth_f64(*args, int(cost_ideal.shape[0]), n, raw.data_ptr(), _stream()), "scp_share_segments_depth_f64")
+    else:
+        _check(lib().scp_share_segments_f64(*args, raw.data_ptr(), _stream()), "scp_share_segments_f64")
+    return dict(share_record_views(raw), raw=raw)
 
 
 def share_segments(cost_ideal, cost_table, bins, n_bins):
@@ -2062,87 +2108,20 @@ def share_segments(cost_ideal, cost_table, bins, n_bins):
     views of `raw` int64 [n_bins, 4] (the scp_share_seg records: one copy brings them all to the host): leaves int64, ideal_bits,
     table_bits, max_ideal_bits float64 [n_bins].  A bin without rows is all zeros; a row whose bin lies outside 0 .. n_bins - 1 belongs to
     no record."""
-    n_bins = int(n_bins)
-    if n_bins < 1 or n_bins > DIST_MAX_BINS:
-        raise ScpError(f"share_segments: between 1 and {DIST_MAX_BINS} bins expected, got {n_bins}")
-    for t, dt, name in ((cost_ideal, torch.float64, "cost_ideal"), (cost_table, torch.float64, "cost_table"), (bins, torch.int32, "bins")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
-            raise ScpError(f"share_segments: {name} is a device tensor of {dt} (there is no CPU path in the product)")
-    n = cost_ideal.shape[0]
-    if n < 1 or tuple(cost_ideal.shape) != (n,) or tuple(cost_table.shape) != (n,) or tuple(bins.shape) != (n,):
-        raise ScpError(f"share_segments: cost_ideal [n], cost_table [n], bins [n] with n >= 1 expected, got {tuple(cost_ideal.shape)}, "
-                       f"{tuple(cost_table.shape)}, {tuple(bins.shape)}")
-    cost_ideal, cost_table = cost_ideal.contiguous(), cost_table.contiguous()
-    ordered, order = torch.sort(bins, stable=True)
-    seg_off = torch.searchsorted(ordered, torch.arange(n_bins + 1, dtype=torch.int32, device=bins.device)).to(torch.int64).contiguous()
-    raw = torch.empty((n_bins, len(SHARE_FIELDS)), dtype=torch.int64, device=cost_ideal.device)
-    _check(lib().scp_share_segments_f64(cost_ideal.data_ptr(), cost_table.data_ptr(), order.data_ptr(), n, seg_off.data_ptr(), n_bins, raw.data_ptr(),
-                                        _stream()), "scp_share_segments_f64")
-    return dict(share_record_views(raw), raw=raw)
+    return _share_segments("share_segments", cost_ideal, cost_table, bins, n_bins, False)
 
 
 def share_record_views(raw):
-    """The fields of scp_share_seg records held as int64 [n_bins, 4] (a torch tensor or a numpy array, device or host) -> dict of views."""
+    """The fields of scp_share_seg records held as int64 [.., n_bins, 4] (a torch tensor or a numpy array, device or host) -> dict of views."""
     f64 = (lambda c: c.view(torch.float64)) if isinstance(raw, torch.Tensor) else (lambda c: c.view(np.float64))
-    return {name: (raw[:, k] if name == "leaves" else f64(raw[:, k])) for k, name in enumerate(SHARE_FIELDS)}
-
-
-# ------------------------------------------------------------------------------------------------- depth report (csrc/depthshare.hip)
-def rate_depth_share(occ, level, parent, bits_ideal, bits_table, segs, total_leaves, max_drop):
-    """scp_rate_depth_share: every leaf's share of the bits of levels 1 .. D - k for k = 0 .. max_drop (include/scp.h states the
-    definition); the arguments of rate_leaf_share plus max_drop (0 .. MAX_DEPTH).  -> dict of device tensors: leaves int64 [N],
-    cost_ideal / cost_table float64 [max_drop + 1, total_leaves] (plane k = cost_k; plane 0 = rate_leaf_share's costs bit for bit; a plane
-    with k >= a segment's depth holds +0.0 there).  A table the library's validation pass objects to raises ScpError (SCP_EINVAL)."""
-    N = int(occ.shape[0])
-    for t, dt, name in ((occ, torch.uint8, "occ"), (level, torch.uint8, "level"), (parent, torch.int32, "parent"),
-                        (bits_ideal, torch.float64, "bits_ideal"), (bits_table, torch.float64, "bits_table")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != (N,):
-            raise ScpError(f"rate_depth_share: {name} is a device tensor of {dt} with one entry per node ({N})")
-    segs = np.ascontiguousarray(segs, np.int64)
-    if segs.ndim != 2 or segs.shape[1] != 4:
-        raise ScpError(f"rate_depth_share: the segment table is int64 [S,4] (node_base, n_nodes, depth, leaf_base), got {segs.shape}")
-    max_drop = int(max_drop)
-    if max_drop < 0 or max_drop > MAX_DEPTH:
-        raise ScpError(f"rate_depth_share: max_drop {max_drop} outside 0 .. {MAX_DEPTH}")
-    S, total_leaves = int(segs.shape[0]), int(total_leaves)
-    ws_bytes = int(lib().scp_rate_depth_share_workspace_bytes(N, S))
-    if ws_bytes < 0:
-        raise ScpError(f"rate_depth_share: {N} nodes in {S} segments: 1 .. 2^30 nodes in 1 .. {MAX_SEGMENTS} segments expected")
-    dev = occ.device
-    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
-    leaves = torch.empty(N, dtype=torch.int64, device=dev)
-    ci = torch.empty((max_drop + 1, max(total_leaves, 0)), dtype=torch.float64, device=dev)
-    ct = torch.empty((max_drop + 1, max(total_leaves, 0)), dtype=torch.float64, device=dev)
-    rc = lib().scp_rate_depth_share(_dev(occ), _dev(level), _dev(parent), N, _dev(bits_ideal), _dev(bits_table), segs.ctypes.data, S, total_leaves,
-                                    max_drop, leaves.data_ptr(), ci.data_ptr(), ct.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
-    _check(rc, "scp_rate_depth_share")
-    return dict(leaves=leaves, cost_ideal=ci, cost_table=ct)
+    return {name: (raw[..., k] if name == "leaves" else f64(raw[..., k])) for k, name in enumerate(SHARE_FIELDS)}
 
 
 def share_segments_depth(cost_ideal, cost_table, bins, n_bins):
     """scp_share_segments_depth_f64: share_segments on every plane of cost_ideal / cost_table [K, n] (rate_depth_share) in one launch; the
     leaves' bins (int32 [n]) are the same for every plane.  -> dict of device tensors, views of `raw` int64 [K, n_bins, 4]: leaves int64,
     ideal_bits, table_bits, max_ideal_bits float64 [K, n_bins]; raw[0] is share_segments' raw on plane 0, field for field."""
-    n_bins = int(n_bins)
-    if n_bins < 1 or n_bins > DIST_MAX_BINS:
-        raise ScpError(f"share_segments_depth: between 1 and {DIST_MAX_BINS} bins expected, got {n_bins}")
-    for t, dt, name in ((cost_ideal, torch.float64, "cost_ideal"), (cost_table, torch.float64, "cost_table"), (bins, torch.int32, "bins")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
-            raise ScpError(f"share_segments_depth: {name} is a device tensor of {dt} (there is no CPU path in the product)")
-    if cost_ideal.dim() != 2 or cost_ideal.shape[1] < 1 or cost_table.shape != cost_ideal.shape or tuple(bins.shape) != (cost_ideal.shape[1],):
-        raise ScpError(f"share_segments_depth: cost_ideal [K, n], cost_table [K, n], bins [n] with n >= 1 expected, got {tuple(cost_ideal.shape)}, "
-                       f"{tuple(cost_table.shape)}, {tuple(bins.shape)}")
-    K, n = int(cost_ideal.shape[0]), int(cost_ideal.shape[1])
-    if K < 1 or K > MAX_DEPTH + 1:
-        raise ScpError(f"share_segments_depth: between 1 and {MAX_DEPTH + 1} planes expected, got {K}")
-    cost_ideal, cost_table = cost_ideal.contiguous(), cost_table.contiguous()
-    ordered, order = torch.sort(bins, stable=True)
-    seg_off = torch.searchsorted(ordered, torch.arange(n_bins + 1, dtype=torch.int32, device=bins.device)).to(torch.int64).contiguous()
-    raw = torch.empty((K, n_bins, len(SHARE_FIELDS)), dtype=torch.int64, device=cost_ideal.device)
-    _check(lib().scp_share_segments_depth_f64(cost_ideal.data_ptr(), cost_table.data_ptr(), order.data_ptr(), n, seg_off.data_ptr(), n_bins, K, n,
-                                              raw.data_ptr(), _stream()), "scp_share_segments_depth_f64")
-    views = {name: (raw[..., k] if name == "leaves" else raw[..., k].view(torch.float64)) for k, name in enumerate(SHARE_FIELDS)}
-    return dict(views, raw=raw)
+    return _share_segments("share_segments_depth", cost_ideal, cost_table, bins, n_bins, True)
 
 
 # ------------------------------------------------------------------------------------------------- range coder (host)

@@ -1,4 +1,4 @@
-"""Reference of the depth report (csrc/depthshare.hip, DESIGN.md 6 "Depth report") in numpy float64, built on ringrate_ref - shared by
+"""Reference of the depth report (csrc/ringrate.hip, DESIGN.md 6 "Depth report") in numpy float64, built on ringrate_ref - shared by
 test_depth_ref.py and test_gpu_depth.py.  Plain loops over parents.
 
 One tree of depth D (nodes in BFS order, occ / level / parent as in ringrate_ref), leaves in the order of the tree's leaves:

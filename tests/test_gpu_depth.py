@@ -1,4 +1,4 @@
-"""Depth report on the device (csrc/depthshare.hip, scp_amd/native.py, metrics.py, encoder.py, decoder.py, cli.py) against the numpy
+"""Depth report on the device (csrc/ringrate.hip, scp_amd/native.py, metrics.py, encoder.py, decoder.py, cli.py) against the numpy
 statement of its definitions (tests/depth_ref.py), and the decoders' --lod against the encoder's cells.
 
 Bounds.  leaves and every plane of both leaf costs (a fixed sequence of IEEE float64 operations) are exact: equality.  A bin's leaf

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Cost of the depth report (csrc/depthshare.hip) and of the decoders' --lod on full frames: synth_frame(0) at level 12 --spher and as the
+"""Cost of the depth report (csrc/ringrate.hip) and of the decoders' --lod on full frames: synth_frame(0) at level 12 --spher and as the
 level-16 multi-level workload.
 
 Per workload the frame is encoded once (synchronously, rate=True, rate_rows=True); then, with device events over --reps calls after a
 warm-up - microseconds per call:
     depth_share           scp_rate_depth_share with max_drop = --max_drop: validation, leaves bottom-up, sums top-down, one plane launch
-                          (2 * depth + 2 kernels, one small read-back); next to leaf_share (scp_rate_leaf_share) on the same inputs
+                          for max_drop >= 1 (2 * depth + 2 kernels, one small read-back); next to leaf_share (scp_rate_leaf_share) on the
+                          same inputs
     share_segments_depth  the stable sort of the bins (torch) + scp_share_segments_depth_f64 on the max_drop + 1 planes; next to
                           share_segments on plane 0
     depth_report          the whole method - the max_drop + 1 distortion reports and PSNRs, read-backs and host work included (wall clock
@@ -96,7 +97,7 @@ def workload(model, dev, level, mullevel, args, tmp):
         decode.append(dict(lod=lod, wall_ms=ms, points=int(got["points"].shape[0]), levels_decoded=int(got.get("levels_decoded", res["n_levels"]))))
     depths = [int(i.depth) for i in g.info]
     return dict(level=level, mullevel=mullevel, points=int(x.shape[0]), nodes=int(g.total_nodes), leaves=sum(int(i.n_leaves) for i in g.info),
-                segments=len(g.info), shell_depths=depths, max_drop=K, depth_share_kernels=2 * max(depths) + 2, depth_report_wall_ms=wall, **t,
+                segments=len(g.info), shell_depths=depths, max_drop=K, depth_share_kernels=2 * max(depths) + (2 if K >= 1 else 1), depth_report_wall_ms=wall, **t,
                 decode=decode,
                 report=[dict(drop=lv["drop"], cells=lv["cells"], ideal_bits=lv["rate"]["total"]["ideal_bits"],
                              ideal_bits_per_point=lv["rate"]["total"]["ideal_bits_per_point"], psnr_d1=lv["d1"]["psnr"],
