@@ -13,6 +13,7 @@ the reference do not exist here.  The returned dict carries the same scalars the
 """
 import math
 import time
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 import os
@@ -144,23 +145,54 @@ def _upload_ints(hq, device):
     return qs
 
 
-def _result(stream, meta, times, debug=None, rate=None, temper=None, ring_lod=None):
-    """The dict every entry point of both encoders returns: the coded stream and its size, the frame's `meta` fields (what the reference
-    prints, what its file names and the side-info file carry), the wall times; `_debug` (device tensors) from the synchronous calls only.
-    rate: (host scp_rate_seg records, the frame's levels in `_rate_layout` form) of an encoder made with rate=True -> the `rate` entry.
-    temper: the frame's `temper` entry (`_temper_entry`) of an encoder made with temper="report" / "code".
-    ring_lod: the frame's `ring_lod` entry (`FrameEncoder._ring_entries`) of an encoder made with ring_lod=(edges, drops)."""
-    bits = 8 * len(stream)
-    res = dict(bytes=stream, bits=bits, bpp=bits / meta["n_points"], times=times, **meta)
-    if debug is not None:
-        res["_debug"] = debug
-    if rate is not None:
-        res["rate"] = _rate_report(rate[0], rate[1], bits, meta["n_points"])
-    if temper is not None:
-        res["temper"] = temper
-    if ring_lod is not None:
-        res["ring_lod"] = ring_lod
-    return res
+# What an option that is on (key: `rate`, `temper`, `ring_lod` - its entry in the result dict) leaves in a frame's coding tail: dev - its device
+# buffer, which has to reach the host; keep - what its launches use, referenced until they have run; entries(the buffer's host image, the
+# frames' result dicts so far, the frames' cuts in the list of levels) -> every frame's entry; check(host image) - None, or what refuses a
+# frame by raising: the synchronous calls run it in front of the range coder
+_Record = namedtuple("_Record", "key dev keep entries check", defaults=(None,))
+
+
+class _Tail:
+    """A frame's or a batch's coding tail as `_FrontEnd._code_table` enqueued it: the table that is coded, its symbols, the (c_low, c_high)
+    pairs, the `_Record`s in the order their buffers travel to the host and their entries appear in the result, cuts (a batch: the row
+    bounds of its frames), implied (ring LOD: the mask of the forced rows), rows (the per-row bits, when kept); host: the records' host
+    images once made, by `_CoderPipeline.submit` or by `_code_now`.  Whoever holds the tail holds everything its launches use."""
+
+    def __init__(self, table, sym_coded, lohi, records, cuts, implied, rows):
+        self.table, self.sym_coded, self.lohi, self.records, self.cuts, self.implied, self.rows = table, sym_coded, lohi, records, cuts, implied, rows
+        self.host = None
+
+
+def _code_now(tail):
+    """The synchronous calls: the pairs to the host, then the records that can refuse the frame, then the range coder, then the other
+    records.  -> (stream, the time in front of the coder, the time behind it)."""
+    lohi = tail.lohi.cpu().numpy()
+    early = [r.dev.cpu() if r.check else None for r in tail.records]
+    for r, h in zip(tail.records, early):
+        if r.check:
+            r.check(h.numpy())
+    t3 = time.perf_counter()
+    stream = native.ac_encode_lohi(lohi)
+    t4 = time.perf_counter()
+    tail.host = [r.dev.cpu() if h is None else h for r, h in zip(tail.records, early)]
+    return stream, t3, t4
+
+
+def _finish(tail, metas, streams, times, debug=None):
+    """The end of every entry point of both encoders: a tail whose host images are complete, per frame its `meta` fields (what the
+    reference prints, what its file names and the side-info file carry) and its coded stream, the wall times -> per frame the result
+    dict: the stream and its size, the meta fields, the times, `_debug` (device tensors: the synchronous calls only), every record's entry."""
+    out = []
+    for stream, meta in zip(streams, metas):
+        bits = 8 * len(stream)
+        out.append(dict(bytes=stream, bits=bits, bpp=bits / meta["n_points"], times=dict(times), **meta))
+        if debug is not None:
+            out[-1]["_debug"] = debug
+    cuts = np.concatenate(([0], np.cumsum([len(m["level_sizes"]) for m in metas])))     # a batch's levels: the frames' level lists one after the other
+    for r, h in zip(tail.records, tail.host):
+        for res, entry in zip(out, r.entries(h.numpy(), out, cuts)):
+            res[r.key] = entry
+    return out
 
 
 def parse_ring_lod(ring_lod):
@@ -277,6 +309,12 @@ def _temper_groups(raw, info):
     return out
 
 
+def _temper_entries(raw, info, cuts):
+    """Every frame's `temper` entry from the launch's host buffer: info["per_level"] groups per level, the frames' levels `cuts`."""
+    groups, k = _temper_groups(raw, info), info["per_level"]
+    return [_temper_entry(groups[k * a:k * b], info, level0=int(a)) for a, b in zip(cuts[:-1], cuts[1:])]
+
+
 def _temper_entry(groups, info, level0=0):
     """The `temper` entry of a result dict from the frame's groups (a batch: its slice of the launch's, its first level `level0`)."""
     grid = info["grid"]
@@ -315,39 +353,26 @@ class _CoderPipeline:
         main.wait_stream(caller)
         return main
 
-    def submit(self, main, lohi, fills0, cuts=None, rate=None, temper=None, ring=None):
-        """lohi: the frame's pairs, enqueued on `main` (the last thing of its model part).  -> (future of the coded stream, or - cuts: row
-        bounds of the frames of a batch - of the list of every frame's own stream; None).  fills0: native.CACHE_FILLS before the frame began.
-        rate: the device records of the frame's rate report (native.rate_segments, enqueued on `main` behind the pairs): they ride to a pinned
-        host tensor on the copy stream next to the pairs - no wait on this thread - and that tensor takes the place of the None; it is
-        complete once the future is.  temper: the device buffer of the frame's temperature choice (`_temper_launch`), which travels the same
-        way -> third entry.  ring: the device counters of a ring-LOD frame (`FrameEncoder._ring_force`), likewise -> fourth entry."""
+    def submit(self, main, tail, fills0):
+        """tail: the frame's `_Tail`, enqueued on `main` (the last thing of its model part).  -> future of the coded stream, or - tail.cuts:
+        row bounds of the frames of a batch - of the list of every frame's own stream.  fills0: native.CACHE_FILLS before the frame began.
+        The pairs and, in the tail's order, the buffer of every record ride to pinned host tensors (one per call: the worker reads them
+        after this returns) on the copy stream - no wait on this thread; the records' images are left in `tail.host` and are complete
+        once the future is."""
         done = torch.cuda.Event()
         done.record(main)
-        if native.CACHE_FILLS != fills0:               # device-side caches were built during this call (first frames only):
+        if native.CACHE_FILLS != fills0:               # device-side caches were built while this call ran (first frames only):
             main.synchronize()                         # finish them before anything is enqueued on another lane
-        host = torch.empty(lohi.shape, dtype=lohi.dtype, pin_memory=True)     # one per call: the worker reads it after this returns
+        images = []
         with torch.cuda.stream(self.copy_stream):
             self.copy_stream.wait_event(done)
-            host.copy_(lohi, non_blocking=True)
-            lohi.record_stream(self.copy_stream)
-            rate_host = None
-            if rate is not None:
-                rate_host = torch.empty(rate.shape, dtype=rate.dtype, pin_memory=True)
-                rate_host.copy_(rate, non_blocking=True)
-                rate.record_stream(self.copy_stream)
-            temper_host = None
-            if temper is not None:
-                temper_host = torch.empty(temper.shape, dtype=temper.dtype, pin_memory=True)
-                temper_host.copy_(temper, non_blocking=True)
-                temper.record_stream(self.copy_stream)
-            ring_host = None
-            if ring is not None:
-                ring_host = torch.empty(ring.shape, dtype=ring.dtype, pin_memory=True)
-                ring_host.copy_(ring, non_blocking=True)
-                ring.record_stream(self.copy_stream)
+            for dev in [tail.lohi] + [r.dev for r in tail.records]:
+                images.append(torch.empty(dev.shape, dtype=dev.dtype, pin_memory=True))
+                images[-1].copy_(dev, non_blocking=True)
+                dev.record_stream(self.copy_stream)
             copied = torch.cuda.Event(blocking=True)      # the coder thread SLEEPS until the pairs have landed (a default event spins a core)
             copied.record()
+        host, tail.host, cuts = images[0], images[1:], tail.cuts
 
         def work():
             _wait_event(copied)
@@ -356,13 +381,15 @@ class _CoderPipeline:
                 return native.ac_encode_lohi(h)
             return [native.ac_encode_lohi(h[a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
 
-        return self.pool.submit(work), rate_host, temper_host, ring_host
+        return self.pool.submit(work)
 
 
 class _FrontEnd:
     """What both encoders do alike in front of their models: the quantiser's parameters per rho shell, stage G's segment list, the
     device quantiser, and the lazily created coding pipeline of the asynchronous calls."""
     LANES_ENV = None                      # the environment variable that sets the number of lanes (read at the first asynchronous call)
+    RATE_PHASES = False                   # EHEM: the report's segments follow the two-phase coding order of the windows
+    ring_lod = None                       # off until __init__ says otherwise (`outfile` is also asked of encoders made without it)
 
     def __init__(self, model, data_type, lidar_level, spher, cylin, mullevel, max_batch, device, host_transform, rate=False, rate_rows=False,
                  temper=None, temper_grid=None, ring_lod=None):
@@ -441,24 +468,38 @@ class _FrontEnd:
             self._pipe = _CoderPipeline(self.device, self.LANES_ENV)
         return self._pipe
 
-    RATE_PHASES = False                   # EHEM: the report's segments follow the two-phase coding order of the windows
+    def _begin_async(self):
+        """-> (now, the caller's stream, the lane of this frame's model part, native.CACHE_FILLS before the frame began)."""
+        caller = torch.cuda.current_stream(self.device)
+        return time.perf_counter(), caller, self._pipeline().lane(caller), native.CACHE_FILLS
 
-    def _rate_launch(self, table, sym_coded, lohi, level_sizes, keep_rows=False):
-        """rate=True: the rate kernels on the current stream, right behind the CDF launch that wrote `lohi` -> (device records and what
-        their launches use - to be held until they have run -, the levels' segment lists); (None, None) when the report is off.
-        keep_rows: also the per-row bits, as a third entry (row_ideal, row_table)."""
+    def _code_table(self, table, sym_coded, level_sizes, ring=None, plan=None, cuts=None, keep_rows=False):
+        """The coding tail of a frame, the one place that states its order ("The coding tail"; the decoders force and scale in
+        the same order): on the current stream 1. the implied rows forced, 2. the temperatures swept, chosen and - "code" - applied,
+        3. the CDF kernel, 4. the rate kernels - each reads the table its predecessors left, so what is reported is what is coded.
+        table: the logits in coding order; sym_coded: the coded symbols; level_sizes: the levels of the frame, or of a batch's frames one
+        after the other; ring, plan: EHEM's ring state of `pre` (None: the option is off) and its plan; cuts: the row bounds of a batch's
+        frames; keep_rows: the per-row bits are kept.  An option that is off launches and allocates nothing.  -> the frame's `_Tail`."""
+        forced, implied = self._ring_force(table, sym_coded, ring, plan, cuts) if ring is not None else (None, None)
+        temper = self._temper_launch(table, sym_coded, level_sizes)
+        lohi = native.softmax_cdf(table, sym_coded)["lohi"]
+        rate, rows = self._rate_launch(table, sym_coded, lohi, level_sizes, keep_rows)
+        return _Tail(table, sym_coded, lohi, [r for r in (rate, temper, forced) if r is not None], cuts, implied, rows)
+
+    def _rate_launch(self, table, sym_coded, lohi, level_sizes, keep_rows):
+        """rate=True: the rate kernels, right behind the CDF launch that wrote `lohi` -> (the `rate` record: the device records
+        of native.rate_segments; keep_rows: the per-row bits (row_ideal, row_table), else None); (None, None) when the report is off."""
         if not self.rate:
             return None, None
         off, levels = _rate_layout(level_sizes, self.context_size if self.RATE_PHASES else None)
         r = native.rate_segments(table, sym_coded, lohi, off, want_rows=keep_rows)
-        return ((r["raw"], r["keep"], (r["row_ideal"], r["row_table"])) if keep_rows else (r["raw"], r["keep"])), levels
-
+        entries = lambda raw, frames, cuts: [_rate_report(raw, levels[a:b], f["bits"], f["n_points"]) for f, a, b in zip(frames, cuts[:-1], cuts[1:])]
+        return _Record("rate", r["raw"], r["keep"], entries), ((r["row_ideal"], r["row_table"]) if keep_rows else None)
 
     def _temper_launch(self, table, sym_coded, level_sizes):
-        """temper="report" / "code": sweep and choice on the current stream, between the model and the CDF launch; "code" then scales the
-        table in place, so that everything behind this call sees the table that is coded.  -> (device buffer int64: the sweep's segment
-        bits, the groups' bits at unit and at the choice, the choices - one copy brings them to the host -, what the launches use, the
-        layout for `_temper_groups`); None when the option is off."""
+        """temper="report" / "code": sweep and choice between the model and the CDF launch; "code" then scales the table in place, so
+        that everything behind this call sees the table that is coded.  -> the `temper` record (device buffer int64: the sweep's segment
+        bits, the groups' bits at unit and at the choice, the choices - one copy brings them to the host); None when the option is off."""
         if not self.temper:
             return None
         off, group, meta = _temper_layout(level_sizes, self.context_size if self.RATE_PHASES else None)
@@ -472,16 +513,8 @@ class _FrontEnd:
         if self.temper == "code":
             native.scale_rows(table, sw["seg_off"], ch["seg_beta"])
         info = dict(S=S, G=G, nt=nt, meta=meta, group=group, mode=self.temper, grid=self.temper_grid, unit=self.temper_unit,
-                    sums=self.temper_sums)
-        return raw, (sw["keep"], ch["keep"], ch["seg_beta"]), info
-
-    @staticmethod
-    def _temper_result(temper, host=None):
-        """`_temper_launch`'s triple (host: the buffer's pinned image of the asynchronous calls; None: copied here) -> the `temper` entry."""
-        if temper is None:
-            return None
-        raw = temper[0].cpu().numpy() if host is None else host.numpy()
-        return _temper_entry(_temper_groups(raw, temper[2]), temper[2])
+                    sums=self.temper_sums, per_level=2 if self.RATE_PHASES else 1)
+        return _Record("temper", raw, (sw["keep"], ch["keep"], ch["seg_beta"]), lambda h, frames, cuts: _temper_entries(h, info, cuts))
 
     def _temper_token(self, base):
         """The file-name token of a tempered stream, in front of the coordinate token (decoder.stream_temper looks for it)."""
@@ -489,7 +522,7 @@ class _FrontEnd:
 
     def _ring_token(self, base):
         """The file-name token of a ring-LOD stream, in front of `temper` / the coordinate token (decoder.stream_ringlod looks for it)."""
-        return base + "_ringlod" if getattr(self, "ring_lod", None) is not None else base
+        return base + "_ringlod" if self.ring_lod is not None else base
 
 
 class FrameEncoder(_FrontEnd):
@@ -609,13 +642,11 @@ class FrameEncoder(_FrontEnd):
         self._ring_thr = ring["thr"]
         return ring
 
-    def _ring_force(self, table, sym_coded, pre, plan, row_cuts=None):
+    def _ring_force(self, table, sym_coded, ring, plan, row_cuts=None):
         """ring_lod: the implied rows of the coding-order table forced to symbol 0, directly behind the model and in front of everything
-        that reads the table (temper, CDF, rate).  -> (device int64 counters: [0] the implied rows whose symbol is NOT 0 - the encoder's
-        check of its own tree -, then per frame its implied rows and its points per j = 0 .. RINGLOD_MAX; the state); None when off."""
-        ring = pre.get("ring")
-        if ring is None:
-            return None
+        that reads the table (temper, CDF, rate).  ring: the state of `pre`.  -> (the `ring_lod` record - device int64 counters: [0] the
+        implied rows whose symbol is NOT 0, the encoder's check of its own tree, then per frame its implied rows and its points per
+        j = 0 .. RINGLOD_MAX -, the mask of the implied rows in coding order)."""
         F, K1 = ring["n_frames"], native.RINGLOD_MAX + 1
         mask = ring["mask_rows"][plan.coding_order_device(self.device)].contiguous()
         buf = torch.zeros(1 + F + F * K1, dtype=torch.int64, device=self.device)
@@ -625,19 +656,19 @@ class FrameEncoder(_FrontEnd):
         for f in range(F):
             buf[1 + f] = mask[row_cuts[f]:row_cuts[f + 1]].sum()
             buf[1 + F + f * K1:1 + F + (f + 1) * K1] = torch.bincount(torch.cat(ring["j_own"][f * ns:(f + 1) * ns]).long(), minlength=K1)[:K1]
-        return buf, ring, mask
+        return _Record("ring_lod", buf, (mask, ring), lambda h, frames, cuts: self._ring_entries(h, ring), self._ring_check), mask
 
-    def _ring_entries(self, forced, host=None):
-        """`_ring_force`'s result (host: the counters' pinned image of the asynchronous calls; None: copied here) -> the `ring_lod` entry of
-        every frame: edges, drops, thresholds and leaves per shell, snapped (points per j), implied_rows.  An implied row with a symbol
-        other than 0 means that the tree is not the one the rule describes: nothing of the frame is handed out."""
-        if forced is None:
-            return None
-        buf, ring, _ = forced
-        h = (buf.cpu() if host is None else host).numpy()
+    @staticmethod
+    def _ring_check(h):
+        """An implied row with a symbol other than 0: the tree is not the one the rule describes, and nothing of the frame is handed out."""
         if int(h[0]) != 0:
             raise native.ScpError(f"ring_lod: {int(h[0])} implied rows of the octree carry a symbol other than 0: the tree that was built is not "
                                   "the tree of the snapped points (internal error: nothing was written)")
+
+    def _ring_entries(self, h, ring):
+        """The host image of `_ring_force`'s counters and the state -> the `ring_lod` entry of every frame: edges, drops, thresholds and
+        leaves per shell, snapped (points per j), implied_rows."""
+        self._ring_check(h)
         edges, drops = self.ring_lod
         F, K1 = ring["n_frames"], native.RINGLOD_MAX + 1
         ns = len(ring["thr"]) // F
@@ -940,20 +971,15 @@ class FrameEncoder(_FrontEnd):
         return self._front_pool.submit(self._front, xyz, ints, caller)
 
     def _model_async(self, front, main, fills0, t0, cuts=None):
-        """The model part and the CDF launch of a front part on the lane `main`, the range coder behind them -> the handle.  The handle
-        keeps the front part (everything allocated on the front stream: frames, tables, plans), the logits table and the pairs referenced
-        until finish(), i.e. past their last use on `main`, so the caching allocator cannot hand them out again early."""
+        """The model part and the coding tail of a front part on the lane `main`, the range coder behind them -> the handle.  The handle
+        keeps the front part (everything allocated on the front stream: frames, tables, plans) and the tail (the logits table, the pairs,
+        the options' buffers) referenced until finish(), i.e. past their last use on `main`, so the caching allocator cannot hand them
+        out again early."""
+        pre, plan = front["pre"], front["plan"]
         main.wait_event(front["ready"])
         with torch.cuda.stream(main):
-            table = self.logits_in_coding_order(front["pre"], front["plan"])
-            forced = self._ring_force(table, front["sym_coded"], front["pre"], front["plan"], cuts)
-            temper = self._temper_launch(table, front["sym_coded"], front["plan"].level_sizes)
-            lohi = native.softmax_cdf(table, front["sym_coded"])["lohi"]
-            rate, levels = self._rate_launch(table, front["sym_coded"], lohi, front["plan"].level_sizes)
-        future, rate_host, temper_host, ring_host = self._pipeline().submit(main, lohi, fills0, cuts, rate[0] if rate else None,
-                                                                            temper[0] if temper else None, forced[0] if forced else None)
-        return dict(future=future, t0=t0, front=front, keep=(table, lohi, rate, temper, forced), rate=(rate_host, levels),
-                    temper=(temper, temper_host), ring=(forced, ring_host))
+            tail = self._code_table(self.logits_in_coding_order(pre, plan), front["sym_coded"], plan.level_sizes, pre.get("ring"), plan, cuts)
+        return dict(future=self._pipeline().submit(main, tail, fills0), t0=t0, front=front, tail=tail)
 
     def encode_async(self, xyz, ints=None, front=None):
         """Like encode(), but the front part runs on the front stream, the model part on the next lane, and the D2H copy of the
@@ -961,10 +987,7 @@ class FrameEncoder(_FrontEnd):
         frame while this one is being coded.  Returns a handle; `finish(handle)` blocks and returns the usual result dict.
         ints: the result of `host_ints(xyz)` when the caller has already computed it (strict-identity mode, CLI reader thread).
         front: the future `front_async(xyz, ints)` returned for this frame (then xyz / ints are not looked at again)."""
-        t0 = time.perf_counter()
-        caller = torch.cuda.current_stream(self.device)
-        main = self._pipeline().lane(caller)
-        fills0 = native.CACHE_FILLS
+        t0, caller, main, fills0 = self._begin_async()
         return self._model_async(front.result() if front is not None else self._front(xyz, ints, caller), main, fills0, t0)
 
     # ------------------------------------------------------------------------------------------ batches of small frames
@@ -1020,10 +1043,7 @@ class FrameEncoder(_FrontEnd):
         22 windows, far too few for an MI355X - BASELINE.json configs[1] is a batch of 16 of them), on the same streams as encode_async.
         The streams are byte-identical to the per-frame path (every kernel is per window / per row).  Returns a handle for finish_batch().
         ints: [host_ints(frame) for every frame] when the caller has them already (strict-identity mode)."""
-        t0 = time.perf_counter()
-        caller = torch.cuda.current_stream(self.device)
-        main = self._pipeline().lane(caller)
-        fills0 = native.CACHE_FILLS
+        t0, caller, main, fills0 = self._begin_async()
         front = self._front(frames, ints, caller, batch=True)
         cuts = np.concatenate(([0], np.cumsum([m["n_nodes"] for m in front["metas"]])))
         return self._model_async(front, main, fills0, t0, cuts)
@@ -1045,26 +1065,12 @@ class FrameEncoder(_FrontEnd):
     def finish_batch(self, h):
         metas = h["front"]["metas"]
         streams = h["future"].result()
-        rates, (rate_host, levels) = [None] * len(metas), h["rate"]
-        if rate_host is not None:              # the batch's levels are the frames' level lists one after the other
-            cuts = np.concatenate(([0], np.cumsum([len(m["level_sizes"]) for m in metas])))
-            rates = [(rate_host.numpy(), levels[a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
-        tempers, (temper, temper_host) = [None] * len(metas), h["temper"]
-        if temper is not None:                 # two groups per level, the frames' levels one after the other
-            cuts = np.concatenate(([0], np.cumsum([len(m["level_sizes"]) for m in metas])))
-            groups = _temper_groups(temper_host.numpy(), temper[2])
-            tempers = [_temper_entry(groups[2 * a:2 * b], temper[2], level0=int(a)) for a, b in zip(cuts[:-1], cuts[1:])]
-        rings = self._ring_entries(*h["ring"]) or [None] * len(metas)
-        return [_result(stream, self._meta(m, m["n_nodes"]), dict(total=(time.perf_counter() - h["t0"]) / len(metas)), rate=r, temper=tp, ring_lod=rg)
-                for stream, m, r, tp, rg in zip(streams, metas, rates, tempers, rings)]
+        return _finish(h["tail"], [self._meta(m, m["n_nodes"]) for m in metas], streams, dict(total=(time.perf_counter() - h["t0"]) / len(metas)))
 
     def finish(self, h):
         stream = h["future"].result()
-        rate_host, levels = h["rate"]
-        ring = self._ring_entries(*h["ring"])
-        return _result(stream, self._meta(h["front"]["pre"], h["front"]["plan"].n_rows), dict(total=time.perf_counter() - h["t0"]),
-                       rate=None if rate_host is None else (rate_host.numpy(), levels), temper=self._temper_result(*h["temper"]),
-                       ring_lod=ring and ring[0])
+        meta = self._meta(h["front"]["pre"], h["front"]["plan"].n_rows)
+        return _finish(h["tail"], [meta], [stream], dict(total=time.perf_counter() - h["t0"]))[0]
 
     def _encode_pre(self, pre, t0, timing):
         if timing:
@@ -1073,26 +1079,18 @@ class FrameEncoder(_FrontEnd):
         plan = EncodePlan(pre["level_sizes"], self.context_size)
         table = self.logits_in_coding_order(pre, plan)
         sym_coded = self._sym_coded(pre, plan)
-        forced = self._ring_force(table, sym_coded, pre, plan)
         if timing:
             torch.cuda.synchronize()
         t2 = time.perf_counter()
-        temper = self._temper_launch(table, sym_coded, plan.level_sizes)
-        lohi_dev = native.softmax_cdf(table, sym_coded)["lohi"]
         keep_rows = self.rate and self.rate_rows and pre.get("sym_coded") is not None      # (record files: no geometry to join the rows with)
-        rate, levels = self._rate_launch(table, sym_coded, lohi_dev, plan.level_sizes, keep_rows=keep_rows)
-        self._rate_rows = (*rate[2], plan) if keep_rows else None
-        lohi = lohi_dev.cpu().numpy()
-        ring = self._ring_entries(forced)           # (raises before anything is coded when an implied row carries a symbol other than 0)
-        t3 = time.perf_counter()
-        stream = native.ac_encode_lohi(lohi)
-        t4 = time.perf_counter()
+        tail = self._code_table(table, sym_coded, plan.level_sizes, pre.get("ring"), plan, keep_rows=keep_rows)
+        self._rate_rows = (*tail.rows, plan) if keep_rows else None
+        stream, t3, t4 = _code_now(tail)            # (raises before anything is coded when an implied row carries a symbol other than 0)
         debug = dict(table=table, sym_coded=sym_coded, pre=pre)
-        if forced is not None:
-            debug["implied"] = forced[2]
-        return _result(stream, self._meta(pre, plan.n_rows), dict(geom=t1 - t0, model=t2 - t1, cdf=t3 - t2, coder=t4 - t3, total=t4 - t0),
-                       debug=debug, rate=rate and (rate[0].cpu().numpy(), levels), temper=self._temper_result(temper),
-                       ring_lod=ring and ring[0])
+        if tail.implied is not None:
+            debug["implied"] = tail.implied
+        return _finish(tail, [self._meta(pre, plan.n_rows)], [stream], dict(geom=t1 - t0, model=t2 - t1, cdf=t3 - t2, coder=t4 - t3, total=t4 - t0),
+                       debug)[0]
 
     def outfile(self, base, res):
         """encode.py:140-144 file name; a ring-LOD and a tempered stream say so in front of the coordinate token
@@ -1267,18 +1265,8 @@ class OctAttnFrameEncoder(_FrontEnd):
                 table[r0:r0 + rows] = out[i * cs + skip:i * cs + skip + rows]
                 i = j
 
-    def encode_ints(self, q, bin_num, n_points, t0=None, sequential=False, defer=False, front=None, quant=None):
-        """q: integer cloud (numpy / tensor int32 [P,3]) or the list of per-shell clouds of the multi-level form.  quant: per shell
-        dict(qs, offset) the integers were made with (`quant_info()`), kept in the result - `z_offset` is its cylindrical z offset - for
-        the side-info file; None: unknown (z offset 0)."""
-        t0 = t0 or time.perf_counter()
-        if front is None:
-            qs = q if isinstance(q, (list, tuple)) else [q]
-            qs = [_as_tensor(x, np.int32).to(self.device) for x in qs]
-            front = self._front(qs)
-        chunks, sym, N = front
-        if sequential and self.decodable:
-            raise native.ScpError("--decodable with --sequential: each node's window slides, so a decoder has no cache to keep")
+    def _logits(self, chunks, N, sequential=False):
+        """The frame's logits table [N,255] in coding order (plain BFS, chunk after chunk) on the current stream."""
         table = torch.empty((N, 255), dtype=torch.float32, device=self.device)
         prev = self.model.decodable
         self.model.decodable = self.decodable
@@ -1292,28 +1280,39 @@ class OctAttnFrameEncoder(_FrontEnd):
                 self._chunk_rows(chunks, table)
         finally:
             self.model.decodable = prev
-        temper = self._temper_launch(table, sym, [c[2] for c in chunks])
-        lohi = native.softmax_cdf(table, sym)["lohi"]
+        return table
+
+    def _code_front(self, front, bin_num, n_points, quant, sequential=False):
+        """What the synchronous and the asynchronous call share behind `_front`: the table, its coding tail on the current stream, and
+        the frame's meta fields.  -> (tail, meta)."""
+        chunks, sym, N = front
+        sizes = [c[2] for c in chunks]
+        tail = self._code_table(self._logits(chunks, N, sequential), sym, sizes)
         z_off = float(quant[0]["offset"][2]) if (quant and self.cylin) else 0.0
-        meta = dict(n_nodes=N, n_points=n_points, bin_num=bin_num, z_offset=z_off, quant=quant, n_levels=len(chunks), pos_mm=np.zeros((0, 2)),
-                    level_sizes=[c[2] for c in chunks], depth=int(self.geom.info[0].depth), sequential=bool(sequential))
-        rate, levels = self._rate_launch(table, sym, lohi, meta["level_sizes"])
-        if defer:
-            return lohi, meta, (table, sym, chunks), (rate, levels), temper
-        stream = native.ac_encode_lohi(lohi.cpu().numpy())
-        return _result(stream, meta, dict(total=time.perf_counter() - t0), debug=dict(table=table, sym_coded=sym),
-                       rate=rate and (rate[0].cpu().numpy(), levels), temper=self._temper_result(temper))
+        return tail, dict(n_nodes=N, n_points=n_points, bin_num=bin_num, z_offset=z_off, quant=quant, n_levels=len(chunks), pos_mm=np.zeros((0, 2)),
+                          level_sizes=sizes, depth=int(self.geom.info[0].depth), sequential=bool(sequential))
+
+    def encode_ints(self, q, bin_num, n_points, t0=None, sequential=False, front=None, quant=None):
+        """q: integer cloud (numpy / tensor int32 [P,3]) or the list of per-shell clouds of the multi-level form.  quant: per shell
+        dict(qs, offset) the integers were made with (`quant_info()`), kept in the result - `z_offset` is its cylindrical z offset - for
+        the side-info file; None: unknown (z offset 0)."""
+        t0 = t0 or time.perf_counter()
+        if front is None:
+            qs = q if isinstance(q, (list, tuple)) else [q]
+            qs = [_as_tensor(x, np.int32).to(self.device) for x in qs]
+            front = self._front(qs)
+        if sequential and self.decodable:
+            raise native.ScpError("--decodable with --sequential: each node's window slides, so a decoder has no cache to keep")
+        tail, meta = self._code_front(front, bin_num, n_points, quant, sequential)
+        stream = _code_now(tail)[0]
+        return _finish(tail, [meta], [stream], dict(total=time.perf_counter() - t0), dict(table=tail.table, sym_coded=tail.sym_coded))[0]
 
     def encode_async(self, xyz):
         """Like encode(), but stage G runs on the front stream, the model part on the next lane, and the D2H copy of the (c_low, c_high)
         pairs and the serial host range coder on a worker thread (_CoderPipeline): the caller can enqueue the next frame while this
         one is being coded.  `finish(handle)` blocks and returns the usual result dict."""
-        t0 = time.perf_counter()
-        xyz = _as_tensor(xyz, np.float32)
-        pipe = self._pipeline()
-        caller = torch.cuda.current_stream(self.device)
-        main = pipe.lane(caller)
-        fills0 = native.CACHE_FILLS
+        t0, caller, main, fills0 = self._begin_async()
+        xyz, pipe = _as_tensor(xyz, np.float32), self._pipeline()
         with torch.cuda.stream(pipe.front_stream):
             pipe.front_stream.wait_stream(caller)
             xyz_dev = xyz.to(self.device, non_blocking=True)
@@ -1326,19 +1325,13 @@ class OctAttnFrameEncoder(_FrontEnd):
             ready.record()
         main.wait_event(ready)
         with torch.cuda.stream(main):
-            lohi, meta, keep, (rate, levels), temper = self.encode_ints(q, bin_num, xyz_dev.shape[0], t0, defer=True, front=front,
-                                                                        quant=self.quant_info())
-        # (the handle keeps what the front stream allocated - the frame, its integers, the context sequences - and the table referenced
+            tail, meta = self._code_front(front, bin_num, xyz_dev.shape[0], self.quant_info())
+        # (the handle keeps what the front stream allocated - the frame, its integers, the context sequences - and the tail referenced
         # until finish(): see FrameEncoder._model_async)
-        future, rate_host, temper_host, _ = pipe.submit(main, lohi, fills0, rate=rate[0] if rate else None, temper=temper[0] if temper else None)
-        return dict(future=future, meta=meta, t0=t0, keep=(keep, lohi, q, xyz_dev, rate, temper), rate=(rate_host, levels),
-                    temper=(temper, temper_host))
+        return dict(future=pipe.submit(main, tail, fills0), meta=meta, t0=t0, front=(xyz_dev, q, front), tail=tail)
 
     def finish(self, h):
-        stream = h["future"].result()
-        rate_host, levels = h["rate"]
-        return _result(stream, h["meta"], dict(total=time.perf_counter() - h["t0"]), rate=None if rate_host is None else (rate_host.numpy(), levels),
-                       temper=self._temper_result(*h["temper"]))
+        return _finish(h["tail"], [h["meta"]], [h["future"].result()], dict(total=time.perf_counter() - h["t0"]))[0]
 
     def outfile(self, base, res):
         """encode.py:24 (`<base>.bin`) / encode_mullevel.py:68-72 (`<base>[_spher|_cylin]_<chunks>_<bin_num>_0.bin`)."""
