@@ -509,6 +509,44 @@ SCP_API int scp_force_rows(float *table, int64_t ld, int64_t n, int32_t nsym, co
                            void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Reflectance layer (csrc/attr.hip; DESIGN.md 6, "Reflectance"): an integer lifting transform on the octree of one shell.  Additive.
+ * LEAVES are int32 [U][3] (DEVICE) in the order of scp_geom_emit_leaves, strictly ascending in the D-digit Morton key (digit = 4 bx +
+ * 2 by + bz, axis 0 first); other orders give unspecified values, but no access leaves the buffers.  "//" is floor division.
+ * scp_attr_leaf_values: q int32 [P][3], r float32 [P] (DEVICE).  v_p = clamp(floor(double(r_p) * scale + 0.5), 0, 255), 0 for a
+ *   non-finite r_p; a point whose cell is a leaf adds (v_p, 1) to that leaf's (sum, cnt) with integer atomics, any other point (a
+ *   coordinate outside 0 .. 2^D - 1 included) adds nothing.  Outputs (DEVICE): a uint8 [U] = (2 sum + cnt) // (2 cnt), 0 where cnt == 0;
+ *   cnt int32 [U].  scale in 1 .. 2^20 (the product is then exact in a double).
+ * scp_attr_forward: a uint8 [U] -> k int16 [U - 1] and ctx uint8 [U - 1] in coding order, root int32 [1], hist int32 [D][511],
+ *   level_counts int64 [D + 1] (all DEVICE; hist and root are zeroed by the call).  Level-0 entries are the leaves (weight 1), the
+ *   level-j entries the distinct key >> 3 j; a parent's children sit in the slots (key >> 3 (j - 1)) & 7.  A parent runs three stages,
+ *   bit = 1, 2, 4: for every lo with lo & bit == 0 and lo & (bit - 1) == 0, hi = lo | bit: both present - d = v[hi] - v[lo], W = w[lo] +
+ *   w[hi], m = v[lo] + (w[hi] d) // W, s = max(1, isqrt((Q Q W) // (w[lo] w[hi]))), k = sign(d) ((|d| + (s >> 1)) // s), then v[lo] = m,
+ *   w[lo] = W; only hi present - it moves to lo.  Coding order: levels j = D .. 1, parents in Morton order, inside a parent stage 3, 2, 1
+ *   with lo ascending; parent p of level j starts at (n_j - 1) + first[p] - p.  ctx = j - 1; hist[j - 1][z] counts z = 2 |k| - (k > 0);
+ *   level_counts[j] = n_j.  U == 0 writes zeros only; U == 1 has no coefficient (k and ctx may be NULL for U <= 1).
+ * scp_attr_inverse: the same tree from the weights alone, then per pair d^ = k s, v[lo] = m - (w[hi] d^) // W, v[hi] = v[lo] + d^ in int32;
+ *   a uint8 [U] = the leaf values clamped to 0 .. 255.  root in 0 .. 255.
+ * scp_attr_level_counts: level_counts int64 [D + 1] (DEVICE) of the same tree, nothing else (workspace of scp_attr_inverse): the
+ *   coefficients of level j are (n_j - 1) .. (n_(j-1) - 2) of the coding order, so a decoder knows every context from the leaves alone.
+ * scp_attr_pairs: lohi[i] = c[z_i] | c[z_i + 1] << 16 of row ctx[i] of tables uint16 [D][512] (DEVICE; entry 511 holds 65536 as 0), the
+ *   pairs scp_ac_encode_lohi takes.  |k| is clamped to 255 and ctx to D - 1, so every table read is in range.
+ * The workspaces are device memory, 8-byte aligned.  SCP_EINVAL before any launch for: U < 0 or U - 1 > 2^31, P outside 0 .. 2^31, D
+ * outside 1 .. SCP_MAX_DEPTH, Q outside 1 .. 255, scale outside 1 .. 2^20, root outside 0 .. 255, a NULL pointer that the sizes make
+ * necessary, a workspace that is NULL, misaligned or short.  Every entry enqueues on `stream` and waits for nothing. */
+SCP_API int64_t scp_attr_leaf_values_workspace_bytes(int64_t U);              /* bytes, or SCP_EINVAL */
+SCP_API int64_t scp_attr_forward_workspace_bytes(int64_t U, int32_t D);       /* bytes, or SCP_EINVAL */
+SCP_API int64_t scp_attr_inverse_workspace_bytes(int64_t U, int32_t D);       /* bytes, or SCP_EINVAL */
+SCP_API int scp_attr_leaf_values(const int32_t *q, const float *r, int64_t P, const int32_t *leaves, int64_t U, int32_t D, int32_t scale,
+                                 uint8_t *a, int32_t *cnt, void *workspace, int64_t workspace_bytes, void *stream);
+SCP_API int scp_attr_forward(const int32_t *leaves, const uint8_t *a, int64_t U, int32_t D, int32_t Q, int16_t *k, uint8_t *ctx, int32_t *root,
+                             int32_t *hist, int64_t *level_counts, void *workspace, int64_t workspace_bytes, void *stream);
+SCP_API int scp_attr_inverse(const int32_t *leaves, int64_t U, int32_t D, int32_t Q, int32_t root, const int16_t *k, uint8_t *a, void *workspace,
+                             int64_t workspace_bytes, void *stream);
+SCP_API int scp_attr_level_counts(const int32_t *leaves, int64_t U, int32_t D, int64_t *level_counts, void *workspace, int64_t workspace_bytes,
+                                  void *stream);
+SCP_API int scp_attr_pairs(const int16_t *k, const uint8_t *ctx, int64_t n, const uint16_t *tables, int32_t D, uint32_t *lohi, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Range coder (host, serial) - replaces numpyAc/backend/numpyAc_backend.cpp
  *   encode_cdf :327-334 / encode :245-323  ->  scp_ac_encode_cdf, scp_ac_encode_lohi
  *   class decode :134-217                  ->  scp_ac_dec_*
@@ -520,6 +558,8 @@ typedef struct scp_ac_dec scp_ac_dec;
 SCP_API int scp_ac_dec_new(scp_ac_dec **d, const uint8_t *stream, size_t len, int32_t Lp);
 SCP_API int scp_ac_dec_next(scp_ac_dec *d, const uint16_t *cdf_row); /* returns the symbol (>= 0) */
 SCP_API int scp_ac_dec_run(scp_ac_dec *d, const uint16_t *cdf, int64_t n, int16_t *out); /* n symbols, row i = CDF of symbol i */
+/* n symbols, symbol i against row ctx[i] of tables [nctx][Lp] (HOST); a ctx[i] >= nctx is refused (SCP_EINVAL) before anything is decoded */
+SCP_API int scp_ac_dec_run_ctx(scp_ac_dec *d, const uint16_t *tables, int32_t nctx, const uint8_t *ctx, int64_t n, int16_t *out);
 SCP_API int scp_ac_dec_free(scp_ac_dec *d);
 
 /* ------------------------------------------------------------------------------------------------

@@ -1,0 +1,231 @@
+"""Reflectance layer ("Reflectance"): the host side of csrc/attr.hip - the 16 fixed tables, the table choice, the
+`<stream>.attr` file, and the two drivers `encode_shells` / `decode_shells` that FrameEncoder.encode_attr and decode_file(attr=True) call.
+
+The transform itself (leaf values, lifting, inverse, the coder's pairs) runs on the device in exact integers; what happens here is the
+choice of one table per octree level (transmitted, so its float arithmetic need not be reproducible), the serial range coder, and bytes."""
+import struct
+
+import numpy as np
+import torch
+
+from . import native
+
+MAGIC, VERSION = b"SCPA", 1
+ALPHABET = native.ATTR_ALPHABET
+RATIOS = (32, 64, 96, 128, 152, 176, 192, 208, 216, 224, 232, 238, 243, 247, 250, 253)
+_TABLES = None
+
+
+def tables():
+    """uint16 [16, 512]: cdf rows of the 16 geometric tables over z = 2 |k| - (k > 0), built from integers only.  Row g: b_0 = 2^24,
+    b_m = (b_(m-1) R[g]) >> 8, u[z] = b_((z+1)>>1), c[z] = 1 + ((65536 - 511) u[z]) // sum(u), the rest of 65536 to c[0];
+    cdf = [0, cumsum(c)] with the last entry (65536) wrapped to 0."""
+    global _TABLES
+    if _TABLES is None:
+        out = np.zeros((len(RATIOS), ALPHABET + 1), np.uint16)
+        for g, R in enumerate(RATIOS):
+            b = [1 << 24]
+            for _ in range(256):
+                b.append((b[-1] * R) >> 8)
+            u = [b[(z + 1) >> 1] for z in range(ALPHABET)]
+            su = sum(u)
+            c = [1 + ((65536 - ALPHABET) * v) // su for v in u]
+            c[0] += 65536 - sum(c)
+            acc, row = 0, [0]
+            for v in c:
+                acc += v
+                row.append(acc)
+            out[g] = np.array(row, np.int64).astype(np.uint16)          # 65536 -> 0
+        out.setflags(write=False)
+        _TABLES = out
+    return _TABLES
+
+
+def table_counts():
+    """int64 [16, 511]: the counts c[z] of every table (they sum to 65536 per row)."""
+    t = tables().astype(np.int64)
+    hi = t[:, 1:].copy()
+    hi[:, -1] = 65536
+    return hi - t[:, :-1]
+
+
+def choose_tables(hist):
+    """hist int [D, 511] -> (choice int [D]: per context the table with the fewest bits sum_z hist[z] (16 - log2 c[z]), the lower index on a
+    tie; bits float64 [D] under the choice)."""
+    hist = np.asarray(hist, np.float64).reshape(-1, ALPHABET)
+    cost = hist @ (16.0 - np.log2(table_counts().astype(np.float64))).T           # [D, 16]
+    choice = np.argmin(cost, axis=1)                                               # (the first minimum: the lower g)
+    return choice.astype(np.int64), cost[np.arange(len(choice)), choice]
+
+
+def pack(Q, scale, shells):
+    """shells: per shell dict(D, U, root, tables (D indices for j = D .. 1), payload bytes) -> the bytes of `<stream>.attr`."""
+    if not 1 <= int(Q) <= 255 or not 1 <= int(scale) <= 1 << 20 or len(shells) > 255:
+        raise native.ScpError(f"attr.pack: Q {Q} outside 1 .. 255, scale {scale} outside 1 .. 2^20 or {len(shells)} shells")
+    head, body = [MAGIC + struct.pack("<BBIB", VERSION, int(Q), int(scale), len(shells))], []
+    for s in shells:
+        D, U = int(s["D"]), int(s["U"])
+        head.append(struct.pack("<BI", D, U))
+        if U >= 1:
+            head.append(struct.pack("<B", int(s["root"])))
+        if U >= 2:
+            idx = [int(t) for t in s["tables"]]
+            if len(idx) != D or not all(0 <= t < len(RATIOS) for t in idx):
+                raise native.ScpError(f"attr.pack: {D} table indices below {len(RATIOS)} expected, got {idx}")
+            head.append(bytes(idx) + struct.pack("<I", len(s["payload"])))
+            body.append(bytes(s["payload"]))
+    return b"".join(head + body)
+
+
+def unpack(data):
+    """The bytes of `<stream>.attr` -> (Q, scale, shells as `pack` takes them); anything else is refused with the reason."""
+    data = bytes(data)
+    pos = [0]
+
+    def take(n, what):
+        if pos[0] + n > len(data):
+            raise native.ScpError(f"attribute file: truncated in {what} ({len(data)} bytes)")
+        b = data[pos[0]:pos[0] + n]
+        pos[0] += n
+        return b
+
+    if take(4, "the magic") != MAGIC:
+        raise native.ScpError("attribute file: no 'SCPA' magic - not written by encode*.py --attr")
+    version, Q, scale, n = struct.unpack("<BBIB", take(7, "the header"))
+    if version != VERSION:
+        raise native.ScpError(f"attribute file: version {version}, this library reads version {VERSION}")
+    if not 1 <= Q <= 255 or not 1 <= scale <= 1 << 20:
+        raise native.ScpError(f"attribute file: Q {Q} outside 1 .. 255 or scale {scale} outside 1 .. 2^20")
+    shells = []
+    for k in range(n):
+        D, U = struct.unpack("<BI", take(5, f"shell {k}"))
+        s = dict(D=D, U=U, root=None, tables=[], payload=b"", length=0)
+        if U >= 1:
+            s["root"] = take(1, f"shell {k}'s root value")[0]
+        if U >= 2:
+            if not 1 <= D <= native.MAX_DEPTH:
+                raise native.ScpError(f"attribute file: shell {k} of depth {D}")
+            s["tables"] = list(take(D, f"shell {k}'s table indices"))
+            if any(t >= len(RATIOS) for t in s["tables"]):
+                raise native.ScpError(f"attribute file: shell {k} names table {max(s['tables'])} of {len(RATIOS)}")
+            s["length"] = struct.unpack("<I", take(4, f"shell {k}'s payload length"))[0]
+        shells.append(s)
+    for k, s in enumerate(shells):
+        s["payload"] = take(s.pop("length"), f"shell {k}'s payload")
+    if pos[0] != len(data):
+        raise native.ScpError(f"attribute file: {len(data) - pos[0]} bytes behind the last payload")
+    return Q, scale, shells
+
+
+def level_contexts(counts):
+    """level_counts [D + 1] (n_0 = U .. n_D = 1) -> uint8 [U - 1]: the context (level - 1) of every coefficient in coding order."""
+    counts = [int(c) for c in counts]
+    D = len(counts) - 1
+    return np.concatenate([np.full(counts[j - 1] - counts[j], j - 1, np.uint8) for j in range(D, 0, -1)] + [np.zeros(0, np.uint8)])
+
+
+def symbols_to_coefficients(z):
+    """z = 2 |k| - (k > 0) -> k (int16)."""
+    z = np.asarray(z, np.int32)
+    return np.where(z & 1, (z + 1) >> 1, -(z >> 1)).astype(np.int16)
+
+
+def default_scale(data_type):
+    """255 for KITTI (reflectance in [0, 1]), 1 for Ford (0 .. 255 already)."""
+    return 1 if data_type == "ford" else 255
+
+
+def encode_shells(leaves, depths, qs, refl, Q=1, scale=255):
+    """leaves: per shell device int32 [U_s,3] in Morton order (Geom.leaves, a multi-level shell's unknown leaves dropped); depths: per
+    shell; qs: per shell the quantised points, device int32 [P,3]; refl device float32 [P].  -> (bytes of the attribute file, report):
+    report = dict(Q, scale, shells = [dict(U, depth, bits, level_bits (ideal bits under the chosen table, levels D .. 1), tables, root)],
+    bits, values (per shell device uint8 [U]: the leaf values that were coded), counts (int32 [U]: points per leaf), decoded (uint8 [U]:
+    what a decoder gets back - `values` itself at Q = 1))."""
+    Q, scale = int(Q), int(scale)
+    if not 1 <= Q <= 255:
+        raise native.ScpError(f"attribute step Q = {Q} outside 1 .. 255")
+    if not 1 <= scale <= 1 << 20:
+        raise native.ScpError(f"attribute scale {scale} outside 1 .. 2^20")
+    tabs = tables()
+    packed, rep, values, counts, decoded = [], [], [], [], []
+    for lv, D, q in zip(leaves, depths, qs):
+        U, D = int(lv.shape[0]), int(D)
+        a, cnt = native.attr_leaf_values(q, refl, lv, D, scale)
+        values.append(a)
+        counts.append(cnt)
+        if U == 0:
+            packed.append(dict(D=D, U=0))
+            rep.append(dict(U=0, depth=D, bits=0, level_bits=[], tables=[], root=None))
+            decoded.append(a)
+            continue
+        f = native.attr_forward(lv, a, D, Q)
+        root = int(f["root"].item())
+        if U == 1:
+            packed.append(dict(D=D, U=1, root=root))
+            rep.append(dict(U=1, depth=D, bits=0, level_bits=[], tables=[], root=root))
+            decoded.append(a)
+            continue
+        choice, bits = choose_tables(f["hist"].cpu().numpy())
+        dev_tabs = torch.from_numpy(tabs[choice].view(np.int16).copy()).to(lv.device)
+        lohi = native.attr_pairs(f["k"], f["ctx"], dev_tabs)
+        payload = native.ac_encode_lohi(lohi.cpu().numpy())
+        order = list(range(D - 1, -1, -1))                                       # the file lists j = D .. 1
+        packed.append(dict(D=D, U=U, root=root, tables=[int(choice[c]) for c in order], payload=payload))
+        rep.append(dict(U=U, depth=D, bits=8 * len(payload), level_bits=[float(bits[c]) for c in order],
+                        tables=[int(choice[c]) for c in order], root=root))
+        decoded.append(a if Q == 1 else native.attr_inverse(lv, D, Q, root, f["k"]))
+    data = pack(Q, scale, packed)
+    return data, dict(Q=Q, scale=scale, shells=rep, bits=8 * len(data), values=values, counts=counts, decoded=decoded)
+
+
+def decode_shells(data, leaves, depths, info=None):
+    """The bytes of an attribute file + the decoded geometry (per shell device int32 / int64 [U,3] leaves in the decoder's order, and the
+    depths) -> per shell the device uint8 [U] leaf values.  D and U of every shell must be the geometry's.  info: a dict that receives
+    the file's Q and scale."""
+    Q, scale, shells = unpack(data)
+    if info is not None:
+        info.update(Q=Q, scale=scale)
+    if len(shells) != len(leaves):
+        raise native.ScpError(f"attribute file: {len(shells)} shells, the geometry stream has {len(leaves)}")
+    tabs, out = tables(), []
+    for k, (s, lv, D) in enumerate(zip(shells, leaves, depths)):
+        U = int(lv.shape[0])
+        if s["D"] != int(D) or s["U"] != U:
+            raise native.ScpError(f"attribute file: shell {k} was coded on {s['U']} leaves of depth {s['D']}, the geometry stream decodes to "
+                                  f"{U} leaves of depth {int(D)} - it belongs to another stream")
+        lv = lv.to(torch.int32).contiguous()
+        if U == 0:
+            out.append(torch.empty(0, dtype=torch.uint8, device=lv.device))
+            continue
+        if U == 1:
+            out.append(torch.full((1,), s["root"], dtype=torch.uint8, device=lv.device))
+            continue
+        ctx = level_contexts(native.attr_level_counts(lv, D).cpu().numpy())
+        if ctx.shape[0] != U - 1:
+            raise native.ScpError(f"attribute file: shell {k}'s leaves are not a Morton-ordered set ({ctx.shape[0]} coefficients for {U} leaves)")
+        rows = tabs[[s["tables"][D - 1 - c] for c in range(D)]]                  # row c = the table of context c (level c + 1)
+        z = native.AcDecoder(s["payload"], Lp=ALPHABET + 1).run_ctx(rows, ctx)
+        coef = torch.from_numpy(symbols_to_coefficients(z)).to(lv.device)
+        out.append(native.attr_inverse(lv, D, Q, s["root"], coef))
+    return out
+
+
+def point_values(refl, scale):
+    """The 8-bit value of every reflectance (device float32 [P]) as scp_attr_leaf_values takes it: int64 [P]."""
+    r = refl.double()
+    v = torch.floor(r * float(scale) + 0.5).clamp(0.0, 255.0)
+    return torch.where(torch.isfinite(r), v, torch.zeros_like(v)).to(torch.int64)
+
+
+def reflectance_psnr(xyz, refl, points, values, scale):
+    """The reflectance PSNR of a decoded frame: xyz [P,3] / refl [P] the input, points [U,3] / values uint8 [U] the decoded cloud (device
+    tensors).  Both directions through native.nn_error_split's indices (the lowest index among equally near points), errors in 8-bit
+    units, PSNR = 10 log10(255^2 / max(mse_ab, mse_ba)); the sums are over int64 squares, hence exact.  -> dict(psnr, mse_ab, mse_ba)."""
+    v = point_values(refl.to(torch.float32), scale)
+    w = values.to(torch.int64)
+    ab = native.nn_error_split(xyz[:, :3], points, (0.0,))["idx"].long()
+    ba = native.nn_error_split(points, xyz[:, :3], (0.0,))["idx"].long()
+    mse_ab = float(torch.sum((v - w[ab]) ** 2).item()) / v.shape[0]
+    mse_ba = float(torch.sum((w - v[ba]) ** 2).item()) / w.shape[0]
+    worst = max(mse_ab, mse_ba)
+    return dict(psnr=float("inf") if worst == 0 else 10.0 * float(np.log10(255.0 ** 2 / worst)), mse_ab=mse_ab, mse_ba=mse_ba)

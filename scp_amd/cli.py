@@ -35,6 +35,11 @@ same stdout block per frame, same summary file.  Differences, all additive:
     the decoder writes the cells' centres.  The stream's name gains `_ringlod` in front of `_temper` / the coordinate token and the
     side-info file the drops and the integer thresholds, which `decode_ehem*.py` require for such a name (not with `--lod` / `--streams`).
     One more line per frame; `--metrics` and the reports then describe the tree that was coded.  All drops 0: the streams of today.
+  * `--attr [Q]` (EHEM, `--type kitti` / `ford`) / `--attr_scale S`: the reflectance of every frame, one 8-bit value per leaf of the octree, through an
+    integer lifting transform on that octree (csrc/attr.hip) with step Q (default 1: lossless on the leaf values) into `<stream>.attr` next
+    to the stream, which `decode_ehem*.py --attr` turns into `<stem>.attr.bin` (x y z r).  S = 8-bit units per unit of reflectance (default
+    255 for kitti, 1 for ford).  One more line per frame (bits, bits per point, with `--metrics` the reflectance PSNR); the streams and
+    every other file keep their bytes.
   * `--normals estimate|DIR` (with `--metrics`, EHEM): the D2 (point-to-plane) PSNR as well, on normals estimated on the device or
     read from the `<DIR>/<sequence>/<frame>.ply` files `gene_normals.py` writes; one more line per frame, `PSNR_D2:` in the summary.
 """
@@ -157,6 +162,18 @@ def ring_lod_request(args):
     return getattr(args, "ring_lod", None)
 
 
+def attr_request(args):
+    """--attr [Q] / --attr_scale S -> (Q or None without the flag, S or None for the data type's default)."""
+    q, s = getattr(args, "attr", None), getattr(args, "attr_scale", None)
+    if q is None and s is not None:
+        raise native.ScpError("--attr_scale sets the scale of the reflectance layer: give --attr as well")
+    if q is not None and not 1 <= int(q) <= 255:
+        raise native.ScpError(f"--attr {q}: the step Q is 1 (lossless) .. 255")
+    if s is not None and not 1 <= int(s) <= 1 << 20:
+        raise native.ScpError(f"--attr_scale {s}: 1 .. 2^20 8-bit units per unit of reflectance expected")
+    return (None if q is None else int(q)), (None if s is None else int(s))
+
+
 def get_args(argv=None, mullevel=False):
     p = argparse.ArgumentParser()
     p.add_argument("--ckpt_path", type=str, default="", help="example: outputs/obj/2023-04-28/10-43-45/ckpt/epoch=7-step=64088.ckpt")
@@ -218,6 +235,14 @@ def get_args(argv=None, mullevel=False):
                         "--distortion_report (the last ring open), DROPS one integer 0 .. 8 per ring, e.g. 0,10,25:2,1,0; the stream's name gains "
                         "`_ringlod`, its side-info file the drops and the integer thresholds, and decode_ehem*.py writes the centres of the "
                         "cells; one more line per frame (points snapped per drop, implied rows, leaves)")
+    # (absent from the namespace unless given: read them with attr_request(args))
+    p.add_argument("--attr", nargs="?", const=1, type=int, default=argparse.SUPPRESS, metavar="Q",
+                   help="EHEM, --type kitti / ford: code the frame's reflectance as well - one 8-bit value per octree leaf, integer lifting "
+                        "transform with step Q (1 .. 255, default 1: lossless on the leaf values) - into <stream>.attr next to the stream, "
+                        "which decode_ehem*.py --attr reads; one more line per frame (bits, bits per point, with --metrics the reflectance "
+                        "PSNR); the streams do not change")
+    p.add_argument("--attr_scale", type=int, default=argparse.SUPPRESS, metavar="S",
+                   help="with --attr: 8-bit units per unit of reflectance (default 255 for kitti, whose files hold 0 .. 1, and 1 for ford)")
     p.add_argument("--host_transform", action="store_true",
                    help="strict identity with the reference from the frame on: the coordinate transform + quantiser run in numpy float32 on the "
                         "host exactly as data_preprocess.py:42-70 does (the device transform is more accurate, hence not bit-identical); "
@@ -279,6 +304,18 @@ def refuse_unsupported(args, name, mullevel):
         if args.preproc_path:
             raise native.ScpError("--ring_lod with --preproc_path: the record files hold a finished octree, and the option snaps the points "
                                   "before the tree is built")
+    if attr_request(args)[0] is not None:
+        if name == "OctAttention":
+            raise native.ScpError("--attr is available for the EHEM encoders only: the OctAttention readers keep no reflectance and their "
+                                  "decoders return no leaf list to hang it on")
+        if args.type == "obj":
+            raise native.ScpError("--attr codes a LiDAR frame's reflectance: --type obj files have points only")
+        if args.preproc_path:
+            raise native.ScpError("--attr with --preproc_path: the record files hold a finished octree and no points, so there is nothing to "
+                                  "average per leaf")
+        if ring_lod_request(args) is not None:
+            raise native.ScpError("--attr with --ring_lod: the leaves of such a tree are snapped cells of mixed sizes, and an attribute layer "
+                                  "for them is not part of this library")
     want_dist, dist_edges = distortion_request(args)
     if want_dist:
         if name == "OctAttention":
@@ -394,6 +431,27 @@ def gene_normals_main(argv=None):
     return written
 
 
+def frame_attr(enc, path, xyz, res, dev, Q, scale, want_psnr):
+    """--attr: the reflectance column of the frame file `path` through FrameEncoder.encode_attr, on the octree `enc` has just coded ->
+    encode_attr's report with `bytes` (the attribute file) and, with want_psnr, `psnr` / `mse_ab` / `mse_ba` (attr.reflectance_psnr
+    of the cloud decode_ehem*.py --attr will write: the kept leaves through the decoder's own de-quantiser, with the decoded values)."""
+    from . import attr
+    from .decoder import dequantise_leaves, shell_qs
+    refl = pointCloud.pcread(path)[1]
+    if refl is None or len(refl) != len(xyz):
+        raise native.ScpError(f"--attr: {path} has no reflectance column (KITTI / Ford .bin frames hold x y z r)")
+    x_dev = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], np.float32)).to(dev)
+    r_dev = torch.from_numpy(np.ascontiguousarray(refl, np.float32).reshape(-1)).to(dev)
+    data, rep = enc.encode_attr(x_dev, r_dev, Q, scale)
+    rep["bytes"] = data
+    if want_psnr:
+        qs = shell_qs(enc.data_type, enc.lidar_level, enc.mullevel)
+        pts = [dequantise_leaves(lv.long(), q, b, float(res["z_offset"]), enc.spher, enc.cylin, enc.data_type)
+               for lv, q, b in zip(enc.attr_leaves(), qs, res.get("bin_nums", [res["bin_num"]]))]
+        rep.update(attr.reflectance_psnr(x_dev, r_dev, torch.cat(pts), torch.cat(rep["decoded"]), rep["scale"]))
+    return rep
+
+
 class Prefetch:
     """File reads (and the ascii PLY parse) one frame ahead on a reader thread, so the launch thread only enqueues GPU work.
     `post` (strict-identity mode: the host transform + quantiser) runs on the reader thread too; get() then returns (xyz, post(xyz))."""
@@ -442,6 +500,7 @@ def main(argv=None, mullevel=False):
     want_dist, dist_edges = distortion_request(args)
     want_rings, ring_edges = rings_request(args)
     want_depth, depth_drop, depth_edges = depth_request(args)
+    attr_q, attr_scale = attr_request(args)
     cls = OctAttention if name == "OctAttention" else EHEM
     if args.random_weights is not None or not args.ckpt_path:
         from .weights import fill_weights
@@ -477,7 +536,7 @@ def main(argv=None, mullevel=False):
     # and finished three frames later - what bench.py measures.  Flows that need the frame's octree after the encode (--metrics, --distortion_report,
     # --rate_rings, --depth_report),
     # come from record files, or run the one-window-per-node mode stay on the synchronous call.
-    pipelined = not (args.preproc_path or args.metrics or want_dist or want_rings or want_depth or args.sequential or obj)
+    pipelined = not (args.preproc_path or args.metrics or want_dist or want_rings or want_depth or args.sequential or obj or attr_q is not None)
     DEPTH = 3
     host_ints = enc.host_ints if (pipelined and name != "OctAttention" and enc.host_transform) else None
     reader = Prefetch(mine, post=host_ints)
@@ -490,7 +549,7 @@ def main(argv=None, mullevel=False):
         return (cur.split("/")[-2] + Path(cur).stem) if (args.type == "kitti" and name != "OctAttention" and "/" in cur.rstrip("/")
                                                           and len(cur.split("/")) >= 2) else Path(cur).stem
 
-    def report(cur, res, t_submit, dist=None, drep=None, rrep=None, lrep=None):
+    def report(cur, res, t_submit, dist=None, drep=None, rrep=None, lrep=None, arep=None):
         now = time.time()
         elapsed = now - max(last_done[0], t_submit)      # wall time this frame added to the run (frames overlap in the pipeline)
         last_done[0] = now
@@ -533,6 +592,11 @@ def main(argv=None, mullevel=False):
         if res.get("ring_lod"):
             rl = res["ring_lod"]
             print("ring LOD snapped per drop, implied rows, leaves :", rl["snapped"], rl["implied_rows"], sum(rl["leaves"]))
+        if arep:
+            with open(outfile + ".attr", "wb") as f:
+                f.write(arep["bytes"])
+            print("attr bits, bits per point" + (", PSNR (refl) :" if "psnr" in arep else "  :"), arep["bits"], arep["bits_per_point"],
+                  *([arep["psnr"]] if "psnr" in arep else []))
         if drep:
             worse = max((drep["a_to_b"]["total"], drep["b_to_a"]["total"]), key=lambda e: e["mse"])     # the direction D1's mseF takes
             share = [worse[k] / worse["mse"] if worse["mse"] > 0 else 0.0 for k in ("mse_r", "mse_phi", "mse_theta")]
@@ -579,7 +643,7 @@ def main(argv=None, mullevel=False):
                 c0, h0, ts = pending.pop(0)
                 report(c0, enc.finish(h0), ts)
             continue
-        dist = drep = rrep = lrep = None
+        dist = drep = rrep = lrep = arep = None
         if args.preproc_path:
             # encode_dataset_ehem.py:149-157 / ..._mullevel.py:147-155: records + meta written by the test-set generator
             pp = args.preproc_path + ((cur.split("/")[-2] + Path(cur).stem) if args.type == "kitti" else Path(cur).stem)
@@ -604,7 +668,9 @@ def main(argv=None, mullevel=False):
                 rrep = enc.ring_rate(x_dev, ring_edges)
             if want_depth:
                 lrep = enc.depth_report(x_dev, depth_drop, depth_edges)
-        report(cur, res, t0, dist, drep, rrep, lrep)
+            if attr_q is not None:
+                arep = frame_attr(enc, cur, xyz, res, dev, attr_q, attr_scale, args.metrics)
+        report(cur, res, t0, dist, drep, rrep, lrep, arep)
     for c0, h0, ts in pending:
         report(c0, enc.finish(h0), ts)
     total = D.reduce_summary(sums, dev)
@@ -643,6 +709,10 @@ def get_decode_args(argv=None):
     p.add_argument("--streams", type=_streams_arg, default=1,
                    help="decode this many files at a time in lockstep, one packed forward serving one level of each (1 .. 64; default 1: one "
                         "file after the other).  With more than one, the time printed per file is the total over the number of files")
+    p.add_argument("--attr", action="store_true",
+                   help="also decode <stream>.attr (written by encode*.py --attr) and write <stem>.attr.bin next to the .ply: float32 [U,4], "
+                        "x y z r in the KITTI layout, rows in the order of the .ply; works with --streams (the attribute stage runs per file "
+                        "after the geometry), not with --lod above 0")
     p.add_argument("--lod", type=int, default=0, metavar="K",
                    help="preview: stop every tree after its level D - K and write the centres of the cells of size 2^K those levels describe "
                         "(what encode*.py --depth_report measures at k = K); 0 (default): the full decode.  A multi-level stream codes its "
@@ -797,6 +867,8 @@ def decode_main(argv=None, mullevel=False):
         raise native.ScpError("decode_ehem*.py decode EHEM streams; OctAttention streams written with --decodable: decode.py")
     if args.lod < 0:
         raise native.ScpError(f"--lod {args.lod}: 0 (the full decode) or the number of levels to leave out expected")
+    if args.attr and args.lod:
+        raise native.ScpError(f"--attr with --lod {args.lod}: a preview has cells, not leaves, and the attribute layer codes one value per leaf")
     if args.lod and args.streams > 1:
         raise native.ScpError("--lod with --streams above 1: the lockstep decoder decodes every level of every stream; decode previews one "
                               "file after the other (--streams 1)")
@@ -831,11 +903,14 @@ def decode_main(argv=None, mullevel=False):
         print(f"{i}/{len(files)}")
         if outs is not None:
             (name, stem), out, t = found[i], outs[i], each
+            if args.attr:
+                from .decoder import decode_attr
+                decode_attr(out_root + name, out, mullevel)
         else:
             name, stem = find_stream(out_root, ori)            # the stem that matched, not string surgery on the stream name
             binfile = out_root + name
             t0 = time.time()
-            out = decode_file(binfile, model, args.lidar_level, args.type, mullevel, dev, lod=args.lod)
+            out = decode_file(binfile, model, args.lidar_level, args.type, mullevel, dev, lod=args.lod, attr=args.attr)
             torch.cuda.synchronize()
             t = time.time() - t0
         elapsed += t
@@ -859,6 +934,10 @@ def decode_main(argv=None, mullevel=False):
         ply = out_root + stem + ".ply"
         pointCloud.write_ply_data(ply, out["points"].cpu().numpy())
         print(ply)
+        if args.attr:
+            rows = np.concatenate([out["points"].cpu().numpy().astype(np.float32), out["reflectance"].cpu().numpy().reshape(-1, 1)], 1)
+            rows.astype(np.float32).tofile(out_root + stem + ".attr.bin")
+            print(out_root + stem + ".attr.bin")
         results.append((ply, out))
     print(elapsed / max(len(files), 1))
     return results

@@ -273,6 +273,16 @@ extern "C" int scp_ac_dec_run(scp_ac_dec *d, const uint16_t *cdf, int64_t n, int
     return SCP_OK;
 }
 
+// decode n symbols against a few shared rows: symbol i uses row ctx[i] of the [nctx][Lp] table (nothing of size [n][Lp] is built)
+extern "C" int scp_ac_dec_run_ctx(scp_ac_dec *d, const uint16_t *tables, int32_t nctx, const uint8_t *ctx, int64_t n, int16_t *out) {
+    if (!d || !tables || nctx < 1 || n < 0 || (n > 0 && (!ctx || !out))) return SCP_EINVAL;
+    for (int64_t i = 0; i < n; ++i)
+        if ((int32_t)ctx[i] >= nctx) return SCP_EINVAL;
+    const int Lp = d->Lp, max_symbol = Lp - 2;
+    for (int64_t i = 0; i < n; ++i) out[i] = (int16_t)ac_dec_step<false>(d, tables + (int64_t)ctx[i] * Lp, max_symbol);
+    return SCP_OK;
+}
+
 extern "C" int scp_ac_dec_free(scp_ac_dec *d) {
     if (!d) return SCP_EINVAL;
     free(d->in);

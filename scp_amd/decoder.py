@@ -637,7 +637,31 @@ def _refuse_ringlod_mode(job, what):
                               "previews of such trees are not part of this library - decode it alone, in full (--streams 1, --lod 0)")
 
 
-def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False, device=None, profile=None, lod=0):
+def decode_attr(binfile, out, mullevel=False):
+    """--attr: the reflectance layer of a decoded stream ("Reflectance").  Reads `<stream>.attr`, checks it against the decoded
+    geometry and adds to `out` (decode_file's dict): attr_values (per shell device uint8 [U_s], in the order of `leaves`), reflectance
+    (float32 [U], float32(value / scale), in the order of `points`), attr_Q and attr_scale.  Runs per file, after the geometry."""
+    import os
+    from . import attr
+    if out.get("lod"):
+        raise native.ScpError(f"--attr with --lod {out['lod']}: a preview has cells, not leaves, and the attribute layer codes one value per leaf")
+    if out.get("ring_lod") is not None:
+        raise native.ScpError(f"--attr: {binfile} is a ring-LOD stream, whose cells have mixed sizes - such streams carry no attribute layer")
+    path = binfile + ".attr"
+    if not os.path.exists(path):
+        raise native.ScpError(f"--attr: {path} is missing - encode with encode*.py --attr to write it next to the stream")
+    with open(path, "rb") as f:
+        data = f.read()
+    info = {}
+    try:
+        values = attr.decode_shells(data, out["leaves"], shell_depths(out["n_levels"], mullevel), info)
+    except native.ScpError as e:
+        raise native.ScpError(f"--attr: {path}: {e}") from None
+    out.update(attr_values=values, attr_Q=info["Q"], attr_scale=info["scale"], reflectance=(torch.cat(values).double() / float(info["scale"])).float())
+    return out
+
+
+def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False, device=None, profile=None, lod=0, attr=False):
     """A stream file written by the encode CLIs -> dict(codes per shell, leaves per shell, points [U,3] float64 Cartesian).
     Side information exactly as the reference's decoders take it (`extract_info`); the `.scp.json` written next to the stream
     supplies what that cannot carry.  Without it the reference's own rules apply: lidar level = the level count (decode_ehem.py:218),
@@ -645,12 +669,17 @@ def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False
     lod = K >= 1 (at most the shallowest shell's depth - 1): a preview - the tree stops after level D - K and `points` holds the centres
     of the cells of size 2^K those levels describe ("Depth report"); a multi-level stream decodes its first two shells in
     full, since the range decoder has to pass them, and stops the last one early.  The dict gains lod, cells (int64 origins per shell)
-    and levels_decoded (over all shells: D - K for one tree); `leaves` holds None for the shell that stopped.  lod = 0 is the path without the option."""
+    and levels_decoded (over all shells: D - K for one tree); `leaves` holds None for the shell that stopped.  lod = 0 is the path without the option.
+    attr: also decode `<stream>.attr` (`decode_attr`): the dict gains reflectance (float32 [U], in the order of `points`) and attr_values
+    (uint8 per shell); not with lod >= 1.  Without it nothing of the attribute layer is read, launched or allocated."""
+    if attr and lod:
+        raise native.ScpError(f"--attr with --lod {lod}: a preview has cells, not leaves, and the attribute layer codes one value per leaf")
     job = _ehem_job(binfile, lidar_level, data_type, mullevel, profile)
     if lod:
         _refuse_ringlod_mode(job, f"--lod {lod}")
     dec = FrameDecoder(model, job["lidar_level"], mullevel=mullevel, polar=job["polar"], device=device, profile=profile)
-    return _ehem_result(job, dec.decode(job["stream"], job["n_levels"], job["pos_mm"], lod, temper=job["temper"], ring_lod=job["ring_lod"]), lod)
+    out = _ehem_result(job, dec.decode(job["stream"], job["n_levels"], job["pos_mm"], lod, temper=job["temper"], ring_lod=job["ring_lod"]), lod)
+    return decode_attr(binfile, out, mullevel) if attr else out
 
 
 def shell_depths(n_levels, mullevel):

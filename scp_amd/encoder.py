@@ -797,6 +797,50 @@ class FrameEncoder(_FrontEnd):
             d.update(psnr_d2=p2["psnr_d2"], mse_ab_d2=p2["mse_ab"], mse_ba_d2=p2["mse_ba"])
         return d
 
+    # ------------------------------------------------------------------------------------------ reflectance
+    def attr_leaves(self):
+        """Per shell the leaves of the geometry just built that a decoder will know (device int32 [U_s,3], Morton order): a multi-level
+        shell's last BFS node is never coded, so its children - the last popcount(occ) leaves - are left out."""
+        g, occ, out = self.geom, None, []
+        for s, i in enumerate(g.info):
+            lv = g.leaves(s)
+            if g.segments[s][3] and int(i.n_nodes) > 0:
+                if occ is None:
+                    occ = g.nodes(("occ",))["occ"]
+                last = int(occ[int(i.node_base) + int(i.n_nodes) - 1].item())
+                lv = lv[:lv.shape[0] - bin(last).count("1")].contiguous()
+            out.append(lv)
+        return out
+
+    def encode_attr(self, xyz_dev, refl_dev, Q=1, scale=None, ints=None):
+        """The reflectance of the frame just encoded ("Reflectance"): codes one 8-bit value per leaf of the octree of the last
+        `encode` / `preprocess` call, as `distortion` measures that octree - callable after a synchronous call.  xyz_dev device float32
+        [P,>=3] and refl_dev device float32 [P] are the frame; Q = 1 .. 255 the step (1: lossless on the leaf values); scale: 8-bit units
+        per unit of reflectance (None: 255 for KITTI, 1 for Ford); ints: the host integers of the frame where the encoder was given them.
+        -> (the bytes of `<stream>.attr`, report): attr.encode_shells' report plus n_points, bits_per_point, bits_per_leaf."""
+        from . import attr
+        if self.ring_lod is not None:
+            raise native.ScpError("encode_attr with ring_lod: the leaves of such a tree are snapped cells of mixed sizes, and an attribute "
+                                  "layer for them is not part of this library")
+        if not self.geom.info:
+            raise native.ScpError("encode_attr: no frame to code - call it after a synchronous encode / preprocess")
+        xyz_dev = xyz_dev[:, :3].to(torch.float32).contiguous()
+        refl_dev = refl_dev.reshape(-1).to(torch.float32).contiguous()
+        if refl_dev.shape[0] != xyz_dev.shape[0]:
+            raise native.ScpError(f"encode_attr: {refl_dev.shape[0]} reflectances for {xyz_dev.shape[0]} points")
+        infos = self._infos
+        try:
+            qs = self.quantize(xyz_dev, ints)[0]         # the integers the tree was built from (the same quantiser, the same input)
+        finally:
+            self._infos = infos
+        leaves = self.attr_leaves()
+        data, rep = attr.encode_shells(leaves, [int(i.depth) for i in self.geom.info], [q.contiguous() for q in qs], refl_dev, Q,
+                                       attr.default_scale(self.data_type) if scale is None else scale)
+        n_leaves = sum(int(lv.shape[0]) for lv in leaves)
+        rep.update(n_points=int(xyz_dev.shape[0]), bits_per_point=rep["bits"] / max(int(xyz_dev.shape[0]), 1),
+                   bits_per_leaf=rep["bits"] / max(n_leaves, 1))
+        return data, rep
+
     def preprocess(self, xyz_dev, ints=None):
         # (ring_lod snaps the integers between the quantiser and the build: the route of the integer inputs)
         if ints is None and not self.host_transform and self.ring_lod is None:

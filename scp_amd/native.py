@@ -172,6 +172,15 @@ def lib():
         "scp_ac_dec_next": (C.c_int, [_vp, _vp]),
         "scp_ac_dec_run": (C.c_int, [_vp, _vp, i64, _vp]),
         "scp_ac_dec_free": (C.c_int, [_vp]),
+        "scp_ac_dec_run_ctx": (C.c_int, [_vp, _vp, i32, _vp, i64, _vp]),
+        "scp_attr_leaf_values_workspace_bytes": (C.c_int64, [i64]),
+        "scp_attr_forward_workspace_bytes": (C.c_int64, [i64, i32]),
+        "scp_attr_inverse_workspace_bytes": (C.c_int64, [i64, i32]),
+        "scp_attr_leaf_values": (C.c_int, [_vp, _vp, i64, _vp, i64, i32, i32, _vp, _vp, _vp, i64, _vp]),
+        "scp_attr_forward": (C.c_int, [_vp, _vp, i64, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp]),
+        "scp_attr_inverse": (C.c_int, [_vp, i64, i32, i32, i32, _vp, _vp, _vp, i64, _vp]),
+        "scp_attr_level_counts": (C.c_int, [_vp, i64, i32, _vp, _vp, i64, _vp]),
+        "scp_attr_pairs": (C.c_int, [_vp, _vp, i64, _vp, i32, _vp, _vp]),
     }
     for name, (res, args) in sig.items():
         if hasattr(L, name):
@@ -2124,6 +2133,93 @@ def share_segments_depth(cost_ideal, cost_table, bins, n_bins):
     return _share_segments("share_segments_depth", cost_ideal, cost_table, bins, n_bins, True)
 
 
+# ------------------------------------------------------------------------------------------------- reflectance layer (csrc/attr.hip)
+ATTR_ALPHABET = 511                                                        # z = 2 |k| - (k > 0), |k| <= 255
+
+
+def _attr_workspace(fn, dev, *args):
+    n = _check(getattr(lib(), fn)(*args), fn)
+    return torch.empty(max(int(n), 8) // 8 + 1, dtype=torch.int64, device=dev), int(n)
+
+
+def _attr_leaves(leaves, who):
+    if leaves.dim() != 2 or leaves.shape[1] != 3:
+        raise ScpError(f"{who}: leaves of shape [U,3] expected, got {tuple(leaves.shape)}")
+    _dev(leaves, torch.int32)
+    return leaves
+
+
+def attr_leaf_values(q, refl, leaves, depth, scale):
+    """scp_attr_leaf_values: q device int32 [P,3] (the quantised points of the shell), refl device float32 [P], leaves device int32 [U,3]
+    in the order of Geom.leaves -> (a uint8 [U], cnt int32 [U]): the rounded mean of the 8-bit point values that fall on every leaf."""
+    leaves = _attr_leaves(leaves, "attr_leaf_values")
+    if q.dim() != 2 or q.shape[1] != 3 or refl.dim() != 1 or refl.shape[0] != q.shape[0]:
+        raise ScpError(f"attr_leaf_values: q [P,3] and refl [P] expected, got {tuple(q.shape)} and {tuple(refl.shape)}")
+    U, dev = leaves.shape[0], leaves.device
+    a = torch.empty(U, dtype=torch.uint8, device=dev)
+    cnt = torch.empty(U, dtype=torch.int32, device=dev)
+    ws, nb = _attr_workspace("scp_attr_leaf_values_workspace_bytes", dev, U)
+    _check(lib().scp_attr_leaf_values(_dev(q, torch.int32), _dev(refl, torch.float32), q.shape[0], leaves.data_ptr(), U, int(depth), int(scale),
+                                      a.data_ptr(), cnt.data_ptr(), ws.data_ptr(), nb, _stream()), "scp_attr_leaf_values")
+    return a, cnt
+
+
+def attr_forward(leaves, a, depth, Q):
+    """scp_attr_forward: leaves device int32 [U,3], a device uint8 [U] -> dict of device tensors: k int16 [U - 1] and ctx uint8 [U - 1] in
+    coding order (ctx = level - 1), root int32 [1], hist int32 [depth, 511], level_counts int64 [depth + 1]."""
+    leaves = _attr_leaves(leaves, "attr_forward")
+    U, dev, depth = leaves.shape[0], leaves.device, int(depth)
+    if a.shape != (U,):
+        raise ScpError(f"attr_forward: one value per leaf expected, got {tuple(a.shape)} for {U} leaves")
+    if not 1 <= depth <= MAX_DEPTH:
+        raise ScpError(f"attr_forward: depth {depth} outside 1 .. {MAX_DEPTH}")
+    k = torch.empty(max(U - 1, 0), dtype=torch.int16, device=dev)
+    ctx = torch.empty(max(U - 1, 0), dtype=torch.uint8, device=dev)
+    root = torch.empty(1, dtype=torch.int32, device=dev)
+    hist = torch.empty((depth, ATTR_ALPHABET), dtype=torch.int32, device=dev)
+    counts = torch.empty(depth + 1, dtype=torch.int64, device=dev)
+    ws, nb = _attr_workspace("scp_attr_forward_workspace_bytes", dev, U, depth)
+    _check(lib().scp_attr_forward(leaves.data_ptr(), _dev(a, torch.uint8), U, depth, int(Q), k.data_ptr(), ctx.data_ptr(), root.data_ptr(),
+                                  hist.data_ptr(), counts.data_ptr(), ws.data_ptr(), nb, _stream()), "scp_attr_forward")
+    return dict(k=k, ctx=ctx, root=root, hist=hist, level_counts=counts)
+
+
+def attr_pairs(k, ctx, tables):
+    """scp_attr_pairs: k int16 [n], ctx uint8 [n], tables uint16 [depth, 512] (all device; torch has the rows as int16) -> lohi int32 [n],
+    the (c_low, c_high) pairs ac_encode_lohi takes."""
+    if tables.dim() != 2 or tables.shape[1] != ATTR_ALPHABET + 1 or not 1 <= tables.shape[0] <= MAX_DEPTH:
+        raise ScpError(f"attr_pairs: tables of shape [depth, {ATTR_ALPHABET + 1}] expected, got {tuple(tables.shape)}")
+    if k.shape != ctx.shape or k.dim() != 1:
+        raise ScpError("attr_pairs: one context per coefficient expected")
+    lohi = torch.empty(k.shape[0], dtype=torch.int32, device=k.device)
+    _check(lib().scp_attr_pairs(_dev(k, torch.int16), _dev(ctx, torch.uint8), k.shape[0], _dev(tables, torch.int16), tables.shape[0],
+                                lohi.data_ptr(), _stream()), "scp_attr_pairs")
+    return lohi
+
+
+def attr_level_counts(leaves, depth):
+    """scp_attr_level_counts: leaves device int32 [U,3] -> level_counts device int64 [depth + 1] (n_0 = U .. n_depth = 1)."""
+    leaves = _attr_leaves(leaves, "attr_level_counts")
+    U, dev, depth = leaves.shape[0], leaves.device, int(depth)
+    counts = torch.empty(max(depth, 0) + 1, dtype=torch.int64, device=dev)
+    ws, nb = _attr_workspace("scp_attr_inverse_workspace_bytes", dev, U, depth)
+    _check(lib().scp_attr_level_counts(leaves.data_ptr(), U, depth, counts.data_ptr(), ws.data_ptr(), nb, _stream()), "scp_attr_level_counts")
+    return counts
+
+
+def attr_inverse(leaves, depth, Q, root, k):
+    """scp_attr_inverse: leaves device int32 [U,3], the root value (host int) and k device int16 [U - 1] in coding order -> a uint8 [U]."""
+    leaves = _attr_leaves(leaves, "attr_inverse")
+    U, dev, depth = leaves.shape[0], leaves.device, int(depth)
+    if k.shape != (max(U - 1, 0),):
+        raise ScpError(f"attr_inverse: {max(U - 1, 0)} coefficients expected for {U} leaves, got {tuple(k.shape)}")
+    a = torch.empty(U, dtype=torch.uint8, device=dev)
+    ws, nb = _attr_workspace("scp_attr_inverse_workspace_bytes", dev, U, depth)
+    _check(lib().scp_attr_inverse(leaves.data_ptr(), U, depth, int(Q), int(root), _dev(k, torch.int16), a.data_ptr(), ws.data_ptr(), nb, _stream()),
+           "scp_attr_inverse")
+    return a
+
+
 # ------------------------------------------------------------------------------------------------- range coder (host)
 def ac_encode_cdf(cdf, sym):
     """cdf uint16/int16 numpy [n,Lp], sym int16 numpy [n] -> bytes."""
@@ -2159,6 +2255,7 @@ def ac_encode_lohi(lohi):
 
 class AcDecoder:
     def __init__(self, byte_stream, Lp=256):
+        self.Lp = Lp
         self._buf = np.frombuffer(byte_stream, np.uint8).copy()
         self._h = _vp()
         _check(lib().scp_ac_dec_new(C.byref(self._h), self._buf.ctypes.data, len(self._buf), Lp), "scp_ac_dec_new")
@@ -2172,6 +2269,17 @@ class AcDecoder:
         cdf = np.ascontiguousarray(cdf).view(np.uint16)
         out = np.empty(cdf.shape[0], np.int16)
         _check(lib().scp_ac_dec_run(self._h, cdf.ctypes.data, cdf.shape[0], out.ctypes.data), "scp_ac_dec_run")
+        return out
+
+    def run_ctx(self, tables, ctx):
+        """tables uint16/int16 numpy [nctx,Lp], ctx uint8 numpy [n] -> int16 numpy [n]: symbol i decoded against row ctx[i]."""
+        tables = np.ascontiguousarray(tables).view(np.uint16)
+        ctx = np.ascontiguousarray(ctx, np.uint8)
+        if tables.ndim != 2 or tables.shape[1] != self.Lp:
+            raise ScpError(f"run_ctx: tables of shape [nctx, {self.Lp}] expected, got {tables.shape}")
+        out = np.empty(ctx.shape[0], np.int16)
+        _check(lib().scp_ac_dec_run_ctx(self._h, tables.ctypes.data, tables.shape[0], ctx.ctypes.data, ctx.shape[0], out.ctypes.data),
+               "scp_ac_dec_run_ctx")
         return out
 
     def __del__(self):

@@ -32,3 +32,19 @@ def write_kitti_bin(path, xyz):
 def ford_like(xyz):
     """Ford-like frame: same cloud in integer millimetres (float32 values)."""
     return np.round(xyz.astype(np.float64) * 1000).astype(np.float32)
+
+
+def synth_reflectance(xyz, seed=0):
+    """A reflectance for the points of a frame, float32 [P] in [0, 1]: smooth in azimuth, an offset on the ground plane, noise of sigma
+    0.03; rounded to multiples of 1/255, as KITTI files hold them.  It says nothing about the statistics of a real sensor."""
+    rng = np.random.default_rng(seed)
+    x, y, z = (xyz[:, i].astype(np.float64) for i in range(3))
+    phi = np.arctan2(y, x)
+    r = 0.35 + 0.15 * np.sin(2.0 * phi) + 0.08 * np.cos(5.0 * phi + 0.7) + np.where(z < -1.5, 0.2, 0.0) + rng.normal(0, 0.03, size=len(xyz))
+    return (np.round(np.clip(r, 0.0, 1.0) * 255.0) / 255.0).astype(np.float32)
+
+
+def write_kitti_bin4(path, xyz, refl):
+    """KITTI .bin layout with the reflectance kept: float32 [P,4] (x, y, z, r)."""
+    p = np.concatenate([np.asarray(xyz, np.float32)[:, :3], np.asarray(refl, np.float32).reshape(-1, 1)], 1).astype(np.float32)
+    p.tofile(path)
