@@ -547,6 +547,39 @@ SCP_API int scp_attr_level_counts(const int32_t *leaves, int64_t U, int32_t D, i
 SCP_API int scp_attr_pairs(const int16_t *k, const uint8_t *ctx, int64_t n, const uint16_t *tables, int32_t D, uint32_t *lohi, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Colour layer (csrc/color.hip; DESIGN.md 6, "Colour"): the RGB of an object cloud on the octree of one shell.  Additive.  LEAVES, "//",
+ * the tree, the three stages of a parent, the weights, m, the step s and k are the reflectance layer's, word for word; what differs:
+ * Point colour: c8 = clamp(floor(c + 0.5), 0, 255) per channel of the reader's float32 value, 0 for a non-finite one (made by the caller).
+ * Leaf colour: per channel (2 sum + cnt) // (2 cnt) over the c8 of the points whose cell the leaf is, 0 where cnt == 0.
+ * YCoCg-R on the leaf means, int32: Co = R - B, t = B + (Co >> 1), Cg = G - t, Y = t + (Cg >> 1); inverse t = Y - (Cg >> 1), G = Cg + t,
+ *   B = t - (Co >> 1), R = B + Co (">>" arithmetic).  Y lies in 0 .. 255, Co and Cg in -255 .. 255, and the inverse is exact.
+ * Lifting: the three planes Y, Co, Cg run through the same pairs with the same weights and the same step (one Q); values are int32 and
+ *   are not clamped between levels; after the inverse lifting comes the inverse colour transform, and only the final R, G, B are clamped
+ *   to 0 .. 255.  Q = 1 returns the leaf means exactly.  A weighted mean stays between its inputs, so |d| <= 255 for Y and <= 510 for
+ *   Co / Cg: z = 2 |k| - (k > 0) <= 1020, one alphabet of 1021 symbols for the three channels.
+ * scp_color_leaf_values: q int32 [P][3], rgb uint8 [P][3] (DEVICE) -> rgb_mean uint8 [U][3], ycc int16 [3][U] (planar: Y, Co, Cg), cnt
+ *   int32 [U] (DEVICE); integer atomics; a point that hits no leaf (a coordinate outside 0 .. 2^D - 1 included) adds nothing.
+ * scp_color_forward: ycc int16 [3][U] -> k int16 [3][U - 1] (planar, every plane in the reflectance layer's coding order), ctx uint8
+ *   [U - 1] = level - 1 (shared by the planes), root int32 [3], hist int32 [3 D][1021] (row channel * D + (level - 1)), level_counts
+ *   int64 [D + 1] (all DEVICE; hist and root are zeroed by the call).  U == 0 writes zeros only; k and ctx may be NULL for U <= 1.
+ * scp_color_inverse: root int32 [3] (HOST: Y in 0 .. 255, Co and Cg in -255 .. 255), k as scp_color_forward writes it -> rgb uint8 [U][3].
+ * scp_color_pairs: lohi uint32 [3 n] in payload order (the Y block, then Co, then Cg; n = U - 1 coefficients each): lohi[c n + i] =
+ *   c[z] | c[z + 1] << 16 of row c * D + ctx[i] of tables uint16 [3 D][1022] (DEVICE; entry 1021 holds 65536 as 0).  |k| is clamped to
+ *   510 and ctx to D - 1, so every table read is in range.
+ * scp_attr_level_counts serves the decoder unchanged.  Workspaces, SCP_EINVAL and streams as for the reflectance layer; on unsorted or
+ * repeated leaves the values are unspecified, but no access leaves the buffers (every level's count is clamped to its host bound). */
+SCP_API int64_t scp_color_leaf_values_workspace_bytes(int64_t U);             /* bytes, or SCP_EINVAL */
+SCP_API int64_t scp_color_forward_workspace_bytes(int64_t U, int32_t D);      /* bytes, or SCP_EINVAL */
+SCP_API int64_t scp_color_inverse_workspace_bytes(int64_t U, int32_t D);      /* bytes, or SCP_EINVAL */
+SCP_API int scp_color_leaf_values(const int32_t *q, const uint8_t *rgb, int64_t P, const int32_t *leaves, int64_t U, int32_t D, uint8_t *rgb_mean,
+                                  int16_t *ycc, int32_t *cnt, void *workspace, int64_t workspace_bytes, void *stream);
+SCP_API int scp_color_forward(const int32_t *leaves, const int16_t *ycc, int64_t U, int32_t D, int32_t Q, int16_t *k, uint8_t *ctx, int32_t *root,
+                              int32_t *hist, int64_t *level_counts, void *workspace, int64_t workspace_bytes, void *stream);
+SCP_API int scp_color_inverse(const int32_t *leaves, int64_t U, int32_t D, int32_t Q, const int32_t *root, const int16_t *k, uint8_t *rgb,
+                              void *workspace, int64_t workspace_bytes, void *stream);
+SCP_API int scp_color_pairs(const int16_t *k, const uint8_t *ctx, int64_t n, const uint16_t *tables, int32_t D, uint32_t *lohi, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Range coder (host, serial) - replaces numpyAc/backend/numpyAc_backend.cpp
  *   encode_cdf :327-334 / encode :245-323  ->  scp_ac_encode_cdf, scp_ac_encode_lohi
  *   class decode :134-217                  ->  scp_ac_dec_*

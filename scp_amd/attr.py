@@ -13,23 +13,26 @@ from . import native
 MAGIC, VERSION = b"SCPA", 1
 ALPHABET = native.ATTR_ALPHABET
 RATIOS = (32, 64, 96, 128, 152, 176, 192, 208, 216, 224, 232, 238, 243, 247, 250, 253)
-_TABLES = None
+_TABLES = {}
 
 
-def tables():
-    """uint16 [16, 512]: cdf rows of the 16 geometric tables over z = 2 |k| - (k > 0), built from integers only.  Row g: b_0 = 2^24,
-    b_m = (b_(m-1) R[g]) >> 8, u[z] = b_((z+1)>>1), c[z] = 1 + ((65536 - 511) u[z]) // sum(u), the rest of 65536 to c[0];
-    cdf = [0, cumsum(c)] with the last entry (65536) wrapped to 0."""
-    global _TABLES
-    if _TABLES is None:
-        out = np.zeros((len(RATIOS), ALPHABET + 1), np.uint16)
+def tables(alphabet=ALPHABET):
+    """uint16 [16, alphabet + 1]: cdf rows of the 16 geometric tables over z = 2 |k| - (k > 0), built from integers only.  Row g: b_0 = 2^24,
+    b_m = (b_(m-1) R[g]) >> 8, u[z] = b_((z+1)>>1), c[z] = 1 + ((65536 - alphabet) u[z]) // sum(u), the rest of 65536 to c[0];
+    cdf = [0, cumsum(c)] with the last entry (65536) wrapped to 0.  alphabet: 511 (the reflectance layer, |k| <= 255) or 1021 (the colour
+    layer, |k| <= 510: b_0 .. b_510)."""
+    alphabet = int(alphabet)
+    if alphabet not in (ALPHABET, native.COLOR_ALPHABET):
+        raise native.ScpError(f"attr.tables: an alphabet of {ALPHABET} or {native.COLOR_ALPHABET} symbols expected, got {alphabet}")
+    if alphabet not in _TABLES:
+        out = np.zeros((len(RATIOS), alphabet + 1), np.uint16)
         for g, R in enumerate(RATIOS):
             b = [1 << 24]
-            for _ in range(256):
+            for _ in range((alphabet + 1) >> 1):
                 b.append((b[-1] * R) >> 8)
-            u = [b[(z + 1) >> 1] for z in range(ALPHABET)]
+            u = [b[(z + 1) >> 1] for z in range(alphabet)]
             su = sum(u)
-            c = [1 + ((65536 - ALPHABET) * v) // su for v in u]
+            c = [1 + ((65536 - alphabet) * v) // su for v in u]
             c[0] += 65536 - sum(c)
             acc, row = 0, [0]
             for v in c:
@@ -37,23 +40,23 @@ def tables():
                 row.append(acc)
             out[g] = np.array(row, np.int64).astype(np.uint16)          # 65536 -> 0
         out.setflags(write=False)
-        _TABLES = out
-    return _TABLES
+        _TABLES[alphabet] = out
+    return _TABLES[alphabet]
 
 
-def table_counts():
-    """int64 [16, 511]: the counts c[z] of every table (they sum to 65536 per row)."""
-    t = tables().astype(np.int64)
+def table_counts(alphabet=ALPHABET):
+    """int64 [16, alphabet]: the counts c[z] of every table (they sum to 65536 per row)."""
+    t = tables(alphabet).astype(np.int64)
     hi = t[:, 1:].copy()
     hi[:, -1] = 65536
     return hi - t[:, :-1]
 
 
-def choose_tables(hist):
-    """hist int [D, 511] -> (choice int [D]: per context the table with the fewest bits sum_z hist[z] (16 - log2 c[z]), the lower index on a
+def choose_tables(hist, alphabet=ALPHABET):
+    """hist int [D, alphabet] -> (choice int [D]: per context the table with the fewest bits sum_z hist[z] (16 - log2 c[z]), the lower index on a
     tie; bits float64 [D] under the choice)."""
-    hist = np.asarray(hist, np.float64).reshape(-1, ALPHABET)
-    cost = hist @ (16.0 - np.log2(table_counts().astype(np.float64))).T           # [D, 16]
+    hist = np.asarray(hist, np.float64).reshape(-1, alphabet)
+    cost = hist @ (16.0 - np.log2(table_counts(alphabet).astype(np.float64))).T   # [D, 16]
     choice = np.argmin(cost, axis=1)                                               # (the first minimum: the lower g)
     return choice.astype(np.int64), cost[np.arange(len(choice)), choice]
 

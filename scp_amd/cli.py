@@ -40,6 +40,11 @@ same stdout block per frame, same summary file.  Differences, all additive:
     to the stream, which `decode_ehem*.py --attr` turns into `<stem>.attr.bin` (x y z r).  S = 8-bit units per unit of reflectance (default
     255 for kitti, 1 for ford).  One more line per frame (bits, bits per point, with `--metrics` the reflectance PSNR); the streams and
     every other file keep their bytes.
+  * `--color [Q]` (EHEM, `--type obj`): the RGB of an object cloud, one colour per leaf of the octree - per-leaf means, a reversible YCoCg-R
+    transform and the reflectance layer's integer lifting on the three planes at once (csrc/color.hip), one step Q for all channels
+    (default 1: lossless on the leaf means) - into `<stream>.color` next to the stream, which `decode_ehem.py --color` turns into
+    `<stem>.color.ply` (x y z red green blue).  One more line per frame (bits, bits per point, with `--metrics` the luma and RGB PSNR); the
+    stream and every other file keep their bytes.
   * `--normals estimate|DIR` (with `--metrics`, EHEM): the D2 (point-to-plane) PSNR as well, on normals estimated on the device or
     read from the `<DIR>/<sequence>/<frame>.ply` files `gene_normals.py` writes; one more line per frame, `PSNR_D2:` in the summary.
 """
@@ -174,6 +179,33 @@ def attr_request(args):
     return (None if q is None else int(q)), (None if s is None else int(s))
 
 
+def color_request(args):
+    """--color [Q] -> Q, or None without the flag."""
+    q = getattr(args, "color", None)
+    if q is not None and not 1 <= int(q) <= 255:
+        raise native.ScpError(f"--color {q}: the step Q is 1 (lossless on the leaf means) .. 255")
+    return None if q is None else int(q)
+
+
+def ply_has_colors(path):
+    """Whether the first point line of an ascii PLY holds six tokens that parse (x y z and three colour columns)."""
+    if not str(path).endswith(".ply") or not os.path.exists(path):
+        return False
+    with open(path) as f:
+        for line in f:
+            w = line.split(" ")
+            try:
+                float(w[0]), float(w[1]), float(w[2])
+            except (ValueError, IndexError):
+                continue
+            try:
+                float(w[3]), float(w[4]), float(w[5])
+            except (ValueError, IndexError):
+                return False
+            return True
+    return False
+
+
 def get_args(argv=None, mullevel=False):
     p = argparse.ArgumentParser()
     p.add_argument("--ckpt_path", type=str, default="", help="example: outputs/obj/2023-04-28/10-43-45/ckpt/epoch=7-step=64088.ckpt")
@@ -243,6 +275,12 @@ def get_args(argv=None, mullevel=False):
                         "PSNR); the streams do not change")
     p.add_argument("--attr_scale", type=int, default=argparse.SUPPRESS, metavar="S",
                    help="with --attr: 8-bit units per unit of reflectance (default 255 for kitti, whose files hold 0 .. 1, and 1 for ford)")
+    # (absent from the namespace unless given: read it with color_request(args))
+    p.add_argument("--color", nargs="?", const=1, type=int, default=argparse.SUPPRESS, metavar="Q",
+                   help="EHEM, --type obj: code the cloud's RGB as well - one colour per octree leaf, YCoCg-R and the integer lifting transform "
+                        "of --attr on the three planes with step Q (1 .. 255, default 1: lossless on the leaf means) - into <stream>.color next "
+                        "to the stream, which decode_ehem.py --color reads; one more line per frame (bits, bits per point, with --metrics "
+                        "the luma and RGB PSNR); the streams do not change")
     p.add_argument("--host_transform", action="store_true",
                    help="strict identity with the reference from the frame on: the coordinate transform + quantiser run in numpy float32 on the "
                         "host exactly as data_preprocess.py:42-70 does (the device transform is more accurate, hence not bit-identical); "
@@ -316,6 +354,20 @@ def refuse_unsupported(args, name, mullevel):
         if ring_lod_request(args) is not None:
             raise native.ScpError("--attr with --ring_lod: the leaves of such a tree are snapped cells of mixed sizes, and an attribute layer "
                                   "for them is not part of this library")
+    if color_request(args) is not None:
+        if name == "OctAttention":
+            raise native.ScpError("--color is available for the EHEM encoders only: the OctAttention decoders return no leaf list to hang "
+                                  "a colour on")
+        if args.type != "obj":
+            raise native.ScpError(f"--color codes the RGB of an object cloud: --type {args.type} frames have no colour - their reflectance is "
+                                  "what --attr codes")
+        if args.preproc_path:
+            raise native.ScpError("--color with --preproc_path: the record files hold a finished octree and no points, so there is nothing to "
+                                  "average per leaf")
+        if not mullevel:
+            for f in expand_files(args.test_files):
+                if not ply_has_colors(f):
+                    raise native.ScpError(f"--color: {f} has no colour columns (an ascii PLY with x y z red green blue per point is expected)")
     want_dist, dist_edges = distortion_request(args)
     if want_dist:
         if name == "OctAttention":
@@ -452,6 +504,28 @@ def frame_attr(enc, path, xyz, res, dev, Q, scale, want_psnr):
     return rep
 
 
+def frame_color(enc, path, xyz, q, res, dev, Q, want_psnr):
+    """--color: the colour columns of the object file `path` through FrameEncoder.encode_color, on the octree `enc` has just coded from the
+    integers q -> encode_color's report with `bytes` (the colour file) and, with want_psnr, color.color_psnr of the cloud
+    decode_ehem.py --color will write (the leaves through the decoder's own de-quantiser, with the decoded colours) against the
+    file's points (MVUB files: in the swapped axes the stream is coded in)."""
+    from . import color, metrics
+    rgb = pointCloud.pcread(path, "rgb")[1]
+    if rgb is None or len(rgb) != len(xyz):
+        raise native.ScpError(f"--color: {path} has no colour columns (an ascii PLY with x y z red green blue per point is expected)")
+    c_dev = color.point_colors(torch.from_numpy(np.ascontiguousarray(rgb, np.float32)).to(dev))
+    data, rep = enc.encode_color(q, c_dev, Q)
+    rep["bytes"] = data
+    if want_psnr:
+        x = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], np.float32)).to(dev)
+        if any(m in path for m in MVUB_NAMES):
+            x = torch.stack((x[:, 0], x[:, 2], -x[:, 1]), 1).contiguous()
+        qd = res["quant"][0]
+        pts = metrics.dequantize(enc.attr_leaves()[0].long(), qd["qs"], qd["offset"], spher=False, cylin=False)
+        rep.update(color.color_psnr(x, c_dev, pts, rep["decoded"][0]))
+    return rep
+
+
 class Prefetch:
     """File reads (and the ascii PLY parse) one frame ahead on a reader thread, so the launch thread only enqueues GPU work.
     `post` (strict-identity mode: the host transform + quantiser) runs on the reader thread too; get() then returns (xyz, post(xyz))."""
@@ -501,6 +575,7 @@ def main(argv=None, mullevel=False):
     want_rings, ring_edges = rings_request(args)
     want_depth, depth_drop, depth_edges = depth_request(args)
     attr_q, attr_scale = attr_request(args)
+    color_q = color_request(args)
     cls = OctAttention if name == "OctAttention" else EHEM
     if args.random_weights is not None or not args.ckpt_path:
         from .weights import fill_weights
@@ -549,7 +624,7 @@ def main(argv=None, mullevel=False):
         return (cur.split("/")[-2] + Path(cur).stem) if (args.type == "kitti" and name != "OctAttention" and "/" in cur.rstrip("/")
                                                           and len(cur.split("/")) >= 2) else Path(cur).stem
 
-    def report(cur, res, t_submit, dist=None, drep=None, rrep=None, lrep=None, arep=None):
+    def report(cur, res, t_submit, dist=None, drep=None, rrep=None, lrep=None, arep=None, crep=None):
         now = time.time()
         elapsed = now - max(last_done[0], t_submit)      # wall time this frame added to the run (frames overlap in the pipeline)
         last_done[0] = now
@@ -597,6 +672,11 @@ def main(argv=None, mullevel=False):
                 f.write(arep["bytes"])
             print("attr bits, bits per point" + (", PSNR (refl) :" if "psnr" in arep else "  :"), arep["bits"], arep["bits_per_point"],
                   *([arep["psnr"]] if "psnr" in arep else []))
+        if crep:
+            with open(outfile + ".color", "wb") as f:
+                f.write(crep["bytes"])
+            print("color bits, bits per point" + (", PSNR (Y), PSNR (RGB) :" if "psnr_y" in crep else "  :"), crep["bits"], crep["bits_per_point"],
+                  *([crep["psnr_y"], crep["psnr_rgb"]] if "psnr_y" in crep else []))
         if drep:
             worse = max((drep["a_to_b"]["total"], drep["b_to_a"]["total"]), key=lambda e: e["mse"])     # the direction D1's mseF takes
             share = [worse[k] / worse["mse"] if worse["mse"] > 0 else 0.0 for k in ("mse_r", "mse_phi", "mse_theta")]
@@ -643,7 +723,7 @@ def main(argv=None, mullevel=False):
                 c0, h0, ts = pending.pop(0)
                 report(c0, enc.finish(h0), ts)
             continue
-        dist = drep = rrep = lrep = arep = None
+        dist = drep = rrep = lrep = arep = crep = None
         if args.preproc_path:
             # encode_dataset_ehem.py:149-157 / ..._mullevel.py:147-155: records + meta written by the test-set generator
             pp = args.preproc_path + ((cur.split("/")[-2] + Path(cur).stem) if args.type == "kitti" else Path(cur).stem)
@@ -654,6 +734,8 @@ def main(argv=None, mullevel=False):
             q, off = obj_ints(xyz, cur, dev)
             res = enc.encode_ints(q, 0, len(xyz), sequential=args.sequential) if name == "OctAttention" else enc.encode_ints([q], 0, 0.0, len(xyz))
             res["quant"] = [dict(qs=[1.0, 1.0, 1.0], offset=off)]     # the sidecar is the only carrier of the per-axis minimum
+            if color_q is not None:
+                crep = frame_color(enc, cur, xyz, q, res, dev, color_q, args.metrics)
         elif name == "OctAttention":
             res = enc.encode(xyz, sequential=args.sequential)
         else:
@@ -670,7 +752,7 @@ def main(argv=None, mullevel=False):
                 lrep = enc.depth_report(x_dev, depth_drop, depth_edges)
             if attr_q is not None:
                 arep = frame_attr(enc, cur, xyz, res, dev, attr_q, attr_scale, args.metrics)
-        report(cur, res, t0, dist, drep, rrep, lrep, arep)
+        report(cur, res, t0, dist, drep, rrep, lrep, arep, crep)
     for c0, h0, ts in pending:
         report(c0, enc.finish(h0), ts)
     total = D.reduce_summary(sums, dev)
@@ -713,6 +795,10 @@ def get_decode_args(argv=None):
                    help="also decode <stream>.attr (written by encode*.py --attr) and write <stem>.attr.bin next to the .ply: float32 [U,4], "
                         "x y z r in the KITTI layout, rows in the order of the .ply; works with --streams (the attribute stage runs per file "
                         "after the geometry), not with --lod above 0")
+    p.add_argument("--color", action="store_true",
+                   help="also decode <stream>.color (written by encode.py --type obj --color) and write <stem>.color.ply next to the .ply: "
+                        "x y z red green blue, rows in the order of the .ply; works with --streams (the colour stage runs per file after the "
+                        "geometry), not with --lod above 0")
     p.add_argument("--lod", type=int, default=0, metavar="K",
                    help="preview: stop every tree after its level D - K and write the centres of the cells of size 2^K those levels describe "
                         "(what encode*.py --depth_report measures at k = K); 0 (default): the full decode.  A multi-level stream codes its "
@@ -869,6 +955,8 @@ def decode_main(argv=None, mullevel=False):
         raise native.ScpError(f"--lod {args.lod}: 0 (the full decode) or the number of levels to leave out expected")
     if args.attr and args.lod:
         raise native.ScpError(f"--attr with --lod {args.lod}: a preview has cells, not leaves, and the attribute layer codes one value per leaf")
+    if args.color and args.lod:
+        raise native.ScpError(f"--color with --lod {args.lod}: a preview has cells, not leaves, and the weights of a cut tree are unknown to the decoder")
     if args.lod and args.streams > 1:
         raise native.ScpError("--lod with --streams above 1: the lockstep decoder decodes every level of every stream; decode previews one "
                               "file after the other (--streams 1)")
@@ -906,11 +994,14 @@ def decode_main(argv=None, mullevel=False):
             if args.attr:
                 from .decoder import decode_attr
                 decode_attr(out_root + name, out, mullevel)
+            if args.color:
+                from .decoder import decode_color
+                decode_color(out_root + name, out, mullevel)
         else:
             name, stem = find_stream(out_root, ori)            # the stem that matched, not string surgery on the stream name
             binfile = out_root + name
             t0 = time.time()
-            out = decode_file(binfile, model, args.lidar_level, args.type, mullevel, dev, lod=args.lod, attr=args.attr)
+            out = decode_file(binfile, model, args.lidar_level, args.type, mullevel, dev, lod=args.lod, attr=args.attr, color=args.color)
             torch.cuda.synchronize()
             t = time.time() - t0
         elapsed += t
@@ -938,6 +1029,9 @@ def decode_main(argv=None, mullevel=False):
             rows = np.concatenate([out["points"].cpu().numpy().astype(np.float32), out["reflectance"].cpu().numpy().reshape(-1, 1)], 1)
             rows.astype(np.float32).tofile(out_root + stem + ".attr.bin")
             print(out_root + stem + ".attr.bin")
+        if args.color:
+            pointCloud.write_ply_colors(out_root + stem + ".color.ply", out["points"].cpu().numpy(), out["colors"].cpu().numpy())
+            print(out_root + stem + ".color.ply")
         results.append((ply, out))
     print(elapsed / max(len(files), 1))
     return results

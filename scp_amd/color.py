@@ -1,0 +1,204 @@
+"""Colour layer ("Colour"): the host side of csrc/color.hip - the `<stream>.color` file, the two drivers `encode_shells` /
+`decode_shells` that FrameEncoder.encode_color and decode_file(color=True) call, and the colour PSNR.
+
+Leaf means, the YCoCg-R transform, the lifting of the three planes, its inverse and the coder's pairs run on the device in exact integers;
+here are the 8-bit value of a reader's float colour, the choice of one of attr.py's 16 tables (its 1021-symbol form) per context channel * D
++ (level - 1), which is transmitted, the serial range coder, and bytes."""
+import struct
+
+import numpy as np
+import torch
+
+from . import attr, native
+
+MAGIC, VERSION, TRANSFORM_YCOCG_R = b"SCPC", 1, 1
+ALPHABET = native.COLOR_ALPHABET
+
+
+def point_colors(rgb):
+    """The 8-bit colour of every point: float [P,3] (device or host tensor) -> uint8 [P,3], clamp(floor(c + 0.5), 0, 255), 0 where c is not
+    finite.  float32 + 0.5 is exact up to 2^23, far beyond the clamp."""
+    c = rgb.to(torch.float32)
+    v = torch.floor(c.double() + 0.5).clamp(0.0, 255.0)
+    return torch.where(torch.isfinite(c), v, torch.zeros_like(v)).to(torch.uint8).contiguous()
+
+
+def pack(Q, shells):
+    """shells: per shell dict(D, U, root (Y, Co, Cg), tables (3 D indices, channel-major, levels D .. 1), payload bytes) -> the bytes of
+    `<stream>.color`."""
+    if not 1 <= int(Q) <= 255 or len(shells) > 255:
+        raise native.ScpError(f"color.pack: Q {Q} outside 1 .. 255 or {len(shells)} shells")
+    head, body = [MAGIC + struct.pack("<BBBB", VERSION, int(Q), TRANSFORM_YCOCG_R, len(shells))], []
+    for s in shells:
+        D, U = int(s["D"]), int(s["U"])
+        head.append(struct.pack("<BI", D, U))
+        if U >= 1:
+            y, co, cg = (int(v) for v in s["root"])
+            if not (0 <= y <= 255 and -255 <= co <= 255 and -255 <= cg <= 255):
+                raise native.ScpError(f"color.pack: roots {(y, co, cg)} outside Y 0 .. 255, Co / Cg -255 .. 255")
+            head.append(struct.pack("<Bhh", y, co, cg))
+        if U >= 2:
+            idx = [int(t) for t in s["tables"]]
+            if len(idx) != 3 * D or not all(0 <= t < len(attr.RATIOS) for t in idx):
+                raise native.ScpError(f"color.pack: {3 * D} table indices below {len(attr.RATIOS)} expected, got {idx}")
+            head.append(bytes(idx) + struct.pack("<I", len(s["payload"])))
+            body.append(bytes(s["payload"]))
+    return b"".join(head + body)
+
+
+def unpack(data):
+    """The bytes of `<stream>.color` -> (Q, shells as `pack` takes them); anything else is refused with the reason."""
+    data = bytes(data)
+    pos = [0]
+
+    def take(n, what):
+        if pos[0] + n > len(data):
+            raise native.ScpError(f"colour file: truncated in {what} ({len(data)} bytes)")
+        b = data[pos[0]:pos[0] + n]
+        pos[0] += n
+        return b
+
+    if take(4, "the magic") != MAGIC:
+        raise native.ScpError("colour file: no 'SCPC' magic - not written by encode.py --color")
+    version, Q, transform, n = struct.unpack("<BBBB", take(4, "the header"))
+    if version != VERSION:
+        raise native.ScpError(f"colour file: version {version}, this library reads version {VERSION}")
+    if transform != TRANSFORM_YCOCG_R:
+        raise native.ScpError(f"colour file: unknown colour transform {transform}, this library knows {TRANSFORM_YCOCG_R} (YCoCg-R)")
+    if not 1 <= Q <= 255:
+        raise native.ScpError(f"colour file: Q {Q} outside 1 .. 255")
+    shells = []
+    for k in range(n):
+        D, U = struct.unpack("<BI", take(5, f"shell {k}"))
+        s = dict(D=D, U=U, root=None, tables=[], payload=b"", length=0)
+        if U >= 1:
+            s["root"] = struct.unpack("<Bhh", take(5, f"shell {k}'s root values"))
+            if not all(-255 <= v <= 255 for v in s["root"]):
+                raise native.ScpError(f"colour file: shell {k}'s roots {s['root']} outside Y 0 .. 255, Co / Cg -255 .. 255")
+        if U >= 2:
+            if not 1 <= D <= native.MAX_DEPTH:
+                raise native.ScpError(f"colour file: shell {k} of depth {D}")
+            s["tables"] = list(take(3 * D, f"shell {k}'s table indices"))
+            if any(t >= len(attr.RATIOS) for t in s["tables"]):
+                raise native.ScpError(f"colour file: shell {k} names table {max(s['tables'])} of {len(attr.RATIOS)}")
+            s["length"] = struct.unpack("<I", take(4, f"shell {k}'s payload length"))[0]
+        shells.append(s)
+    for k, s in enumerate(shells):
+        s["payload"] = take(s.pop("length"), f"shell {k}'s payload")
+    if pos[0] != len(data):
+        raise native.ScpError(f"colour file: {len(data) - pos[0]} bytes behind the last payload")
+    return Q, shells
+
+
+def _file_order(D):
+    """The contexts channel * D + (level - 1) in the order the file lists them: channel-major, levels D .. 1."""
+    return [c * D + j for c in range(3) for j in range(D - 1, -1, -1)]
+
+
+def encode_shells(leaves, depths, qs, rgb, Q=1):
+    """leaves: per shell device int32 [U_s,3] in Morton order; depths: per shell; qs: per shell the integer points, device int32 [P,3];
+    rgb device uint8 [P,3].  -> (bytes of the colour file, report): report = dict(Q, shells = [dict(U, depth, bits, level_bits ([3][D]:
+    ideal bits under the chosen table per channel, levels D .. 1), tables (likewise), roots)], bits, values (per shell device uint8 [U,3]:
+    the leaf means that were coded), counts (int32 [U]), decoded (uint8 [U,3]: what a decoder gets back - `values` itself at Q = 1))."""
+    Q = int(Q)
+    if not 1 <= Q <= 255:
+        raise native.ScpError(f"colour step Q = {Q} outside 1 .. 255")
+    tabs = attr.tables(ALPHABET)
+    packed, rep, values, counts, decoded = [], [], [], [], []
+    for lv, D, q in zip(leaves, depths, qs):
+        U, D = int(lv.shape[0]), int(D)
+        mean, ycc, cnt = native.color_leaf_values(q, rgb, lv, D)
+        values.append(mean)
+        counts.append(cnt)
+        decoded.append(mean)
+        if U == 0:
+            packed.append(dict(D=D, U=0))
+            rep.append(dict(U=0, depth=D, bits=0, level_bits=[], tables=[], roots=None))
+            continue
+        f = native.color_forward(lv, ycc, D, Q)
+        roots = [int(v) for v in f["root"].cpu().tolist()]
+        if U == 1:
+            packed.append(dict(D=D, U=1, root=roots))
+            rep.append(dict(U=1, depth=D, bits=0, level_bits=[], tables=[], roots=roots))
+            continue
+        choice, bits = attr.choose_tables(f["hist"].cpu().numpy(), ALPHABET)          # [3 D], by context
+        dev_tabs = torch.from_numpy(tabs[choice].view(np.int16).copy()).to(lv.device)
+        lohi = native.color_pairs(f["k"], f["ctx"], dev_tabs)
+        payload = native.ac_encode_lohi(lohi.cpu().numpy())
+        order = _file_order(D)
+        packed.append(dict(D=D, U=U, root=roots, tables=[int(choice[c]) for c in order], payload=payload))
+        rep.append(dict(U=U, depth=D, bits=8 * len(payload), level_bits=[[float(bits[c]) for c in order[ch * D:(ch + 1) * D]] for ch in range(3)],
+                        tables=[[int(choice[c]) for c in order[ch * D:(ch + 1) * D]] for ch in range(3)], roots=roots))
+        if Q != 1:
+            decoded[-1] = native.color_inverse(lv, D, Q, roots, f["k"])
+    data = pack(Q, packed)
+    return data, dict(Q=Q, shells=rep, bits=8 * len(data), values=values, counts=counts, decoded=decoded)
+
+
+def decode_shells(data, leaves, depths, info=None):
+    """The bytes of a colour file + the decoded geometry (per shell device int32 / int64 [U,3] leaves in the decoder's order, and the
+    depths) -> per shell the device uint8 [U,3] leaf colours.  D and U of every shell must be the geometry's.  info: a dict that
+    receives the file's Q."""
+    Q, shells = unpack(data)
+    if info is not None:
+        info.update(Q=Q)
+    if len(shells) != len(leaves):
+        raise native.ScpError(f"colour file: {len(shells)} shells, the geometry stream has {len(leaves)}")
+    tabs, out = attr.tables(ALPHABET), []
+    for k, (s, lv, D) in enumerate(zip(shells, leaves, depths)):
+        U, D = int(lv.shape[0]), int(D)
+        if s["D"] != D or s["U"] != U:
+            raise native.ScpError(f"colour file: shell {k} was coded on {s['U']} leaves of depth {s['D']}, the geometry stream decodes to "
+                                  f"{U} leaves of depth {D} - it belongs to another stream")
+        lv = lv.to(torch.int32).contiguous()
+        if U == 0:
+            out.append(torch.empty((0, 3), dtype=torch.uint8, device=lv.device))
+            continue
+        coef = torch.empty((3, 0), dtype=torch.int16, device=lv.device)
+        if U >= 2:
+            level = attr.level_contexts(native.attr_level_counts(lv, D).cpu().numpy())
+            if level.shape[0] != U - 1:
+                raise native.ScpError(f"colour file: shell {k}'s leaves are not a Morton-ordered set ({level.shape[0]} coefficients for {U} leaves)")
+            ctx = np.concatenate([level + np.uint8(c * D) for c in range(3)])
+            by_ctx = dict(zip(_file_order(D), s["tables"]))
+            rows = tabs[[by_ctx[c] for c in range(3 * D)]]                        # row c = the table of context c
+            z = native.AcDecoder(s["payload"], Lp=ALPHABET + 1).run_ctx(rows, ctx)
+            coef = torch.from_numpy(attr.symbols_to_coefficients(z).reshape(3, U - 1)).to(lv.device)
+        out.append(native.color_inverse(lv, D, Q, s["root"], coef))
+    return out
+
+
+Y4 = (2126, 7152, 722)                     # BT.709 luma in units of 1 / 10000
+CHUNK = 1 << 20
+
+
+def _sums(a, b):
+    """uint8 [n,3] colours a and b -> the exact sums of squared differences (R, G, B, y4) as Python integers; chunks of at most 2^20 points
+    keep every int64 partial sum below 2^63 (a y4 difference is at most 2 550 000)."""
+    tot = [0, 0, 0, 0]
+    w = torch.tensor(Y4, dtype=torch.int64, device=a.device)
+    for i in range(0, a.shape[0], CHUNK):
+        d = a[i:i + CHUNK].to(torch.int64) - b[i:i + CHUNK].to(torch.int64)
+        part = torch.cat([(d * d).sum(0), ((d * w).sum(1) ** 2).sum().reshape(1)]).cpu().tolist()
+        tot = [t + int(p) for t, p in zip(tot, part)]
+    return tot
+
+
+def color_psnr(xyz, rgb, points, decoded):
+    """The colour PSNR of a decoded cloud: xyz [P,3] / rgb [P,3] the input (rgb as the reader returns it, or its uint8 point colours), points
+    [U,3] / decoded uint8 [U,3] the decoded cloud (device tensors).  Both directions through native.nn_error_split's indices (the lowest
+    index among equally near points).  -> dict(psnr_y, psnr_rgb, sse_ab / sse_ba (R, G, B, y4 as exact integers), n_ab, n_ba): mse =
+    sum / n (/ 1e8 for luma), PSNR = 10 log10(255^2 / max(mse_ab, mse_ba)), inf at zero error; psnr_rgb over the mean of the channels."""
+    v = rgb if rgb.dtype == torch.uint8 else point_colors(rgb)
+    w = decoded
+    ab = native.nn_error_split(xyz[:, :3], points, (0.0,))["idx"].long()
+    ba = native.nn_error_split(points, xyz[:, :3], (0.0,))["idx"].long()
+    s_ab, s_ba = _sums(v, w[ab]), _sums(w, v[ba])
+    n_ab, n_ba = int(v.shape[0]), int(w.shape[0])
+
+    def psnr(mse_ab, mse_ba):
+        worst = max(mse_ab, mse_ba)
+        return float("inf") if worst == 0 else 10.0 * float(np.log10(255.0 ** 2 / worst))
+
+    return dict(psnr_y=psnr(s_ab[3] / n_ab / 1e8, s_ba[3] / n_ba / 1e8),
+                psnr_rgb=psnr(sum(s_ab[:3]) / 3 / n_ab, sum(s_ba[:3]) / 3 / n_ba), sse_ab=s_ab, sse_ba=s_ba, n_ab=n_ab, n_ba=n_ba)

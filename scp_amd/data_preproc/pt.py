@@ -17,8 +17,11 @@ def loadbin(file):
 
 
 def loadply(filedir, color_format="geometry"):
-    """ascii PLY: every line whose first three tokens parse as floats is a point (header lines fail the parse)."""
-    coords = []
+    """ascii PLY: every line whose first three tokens parse as floats is a point (header lines fail the parse).  color_format "rgb": tokens
+    3 .. 5 of those lines as well (pt.py:224-246) -> (xyz float32 [P,3], rgb float32 [P,3]); a point line with fewer than six tokens
+    means the file has no colour columns, and the whole file falls back to (xyz, None).  Any other format returns (xyz, None)."""
+    coords, colors = [], []
+    want = color_format == "rgb"
     with open(filedir) as f:
         for line in f:
             w = line.split(" ")
@@ -26,7 +29,13 @@ def loadply(filedir, color_format="geometry"):
                 coords.append((float(w[0]), float(w[1]), float(w[2])))
             except (ValueError, IndexError):
                 continue
-    return np.array(coords).astype("float32").reshape(-1, 3), None
+            if want:
+                try:
+                    colors.append((float(w[3]), float(w[4]), float(w[5])))
+                except (ValueError, IndexError):
+                    want = False
+    xyz = np.array(coords).astype("float32").reshape(-1, 3)
+    return xyz, (np.array(colors).astype("float32").reshape(-1, 3) if want and color_format == "rgb" else None)
 
 
 def pcread(path, color_format="geometry"):
@@ -51,6 +60,18 @@ def write_ply_data(filename, points):
                 % len(points))
         for p in points:
             f.write("%s %s %s\n" % (repr(float(p[0])), repr(float(p[1])), repr(float(p[2]))))
+
+
+def write_ply_colors(filename, points, rgb):
+    """ascii PLY with x y z as `write_ply_data` prints them, followed by uchar red green blue."""
+    points, rgb = np.asarray(points), np.asarray(rgb)
+    if rgb.shape != (len(points), 3) or points.ndim != 2 or points.shape[1] < 3:
+        raise ValueError(f"points {points.shape} [n,3] and rgb {rgb.shape} [n,3] expected")
+    with open(filename, "w") as f:
+        f.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(points))
+        for p, c in zip(points, rgb):
+            f.write("%s %s %s %d %d %d\n" % (repr(float(p[0])), repr(float(p[1])), repr(float(p[2])), int(c[0]), int(c[1]), int(c[2])))
 
 
 def write_ply_normals(filename, points, normals):

@@ -661,7 +661,31 @@ def decode_attr(binfile, out, mullevel=False):
     return out
 
 
-def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False, device=None, profile=None, lod=0, attr=False):
+def decode_color(binfile, out, mullevel=False):
+    """--color: the colour layer of a decoded stream ("Colour").  Reads `<stream>.color`, checks every shell's depth and leaf
+    count against the decoded geometry and adds to `out` (decode_file's dict): colors (device uint8 [U,3], in the order of `points`) and
+    color_Q.  Runs per file, after the geometry."""
+    import os
+    from . import color
+    if out.get("lod"):
+        raise native.ScpError(f"--color with --lod {out['lod']}: a preview has cells, not leaves, and the weights of a cut tree are unknown to the decoder")
+    if out.get("ring_lod") is not None:
+        raise native.ScpError(f"--color: {binfile} is a ring-LOD stream, whose cells have mixed sizes - such streams carry no colour layer")
+    path = binfile + ".color"
+    if not os.path.exists(path):
+        raise native.ScpError(f"--color: {path} is missing - encode with encode.py --type obj --color to write it next to the stream")
+    with open(path, "rb") as f:
+        data = f.read()
+    info = {}
+    try:
+        values = color.decode_shells(data, out["leaves"], shell_depths(out["n_levels"], mullevel), info)
+    except native.ScpError as e:
+        raise native.ScpError(f"--color: {path}: {e}") from None
+    out.update(colors=torch.cat(values), color_Q=info["Q"])
+    return out
+
+
+def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False, device=None, profile=None, lod=0, attr=False, color=False):
     """A stream file written by the encode CLIs -> dict(codes per shell, leaves per shell, points [U,3] float64 Cartesian).
     Side information exactly as the reference's decoders take it (`extract_info`); the `.scp.json` written next to the stream
     supplies what that cannot carry.  Without it the reference's own rules apply: lidar level = the level count (decode_ehem.py:218),
@@ -671,15 +695,21 @@ def decode_file(binfile, model, lidar_level=None, data_type=None, mullevel=False
     full, since the range decoder has to pass them, and stops the last one early.  The dict gains lod, cells (int64 origins per shell)
     and levels_decoded (over all shells: D - K for one tree); `leaves` holds None for the shell that stopped.  lod = 0 is the path without the option.
     attr: also decode `<stream>.attr` (`decode_attr`): the dict gains reflectance (float32 [U], in the order of `points`) and attr_values
-    (uint8 per shell); not with lod >= 1.  Without it nothing of the attribute layer is read, launched or allocated."""
+    (uint8 per shell); not with lod >= 1.  Without it nothing of the attribute layer is read, launched or allocated.
+    color: also decode `<stream>.color` (`decode_color`): the dict gains colors (uint8 [U,3], in the order of `points`) and color_Q; not
+    with lod >= 1.  Without it nothing of the colour layer is read, launched or allocated."""
     if attr and lod:
         raise native.ScpError(f"--attr with --lod {lod}: a preview has cells, not leaves, and the attribute layer codes one value per leaf")
+    if color and lod:
+        raise native.ScpError(f"--color with --lod {lod}: a preview has cells, not leaves, and the weights of a cut tree are unknown to the decoder")
     job = _ehem_job(binfile, lidar_level, data_type, mullevel, profile)
     if lod:
         _refuse_ringlod_mode(job, f"--lod {lod}")
     dec = FrameDecoder(model, job["lidar_level"], mullevel=mullevel, polar=job["polar"], device=device, profile=profile)
     out = _ehem_result(job, dec.decode(job["stream"], job["n_levels"], job["pos_mm"], lod, temper=job["temper"], ring_lod=job["ring_lod"]), lod)
-    return decode_attr(binfile, out, mullevel) if attr else out
+    if attr:
+        out = decode_attr(binfile, out, mullevel)
+    return decode_color(binfile, out, mullevel) if color else out
 
 
 def shell_depths(n_levels, mullevel):

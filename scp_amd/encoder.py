@@ -841,6 +841,29 @@ class FrameEncoder(_FrontEnd):
                    bits_per_leaf=rep["bits"] / max(n_leaves, 1))
         return data, rep
 
+    # ------------------------------------------------------------------------------------------ colour
+    def encode_color(self, q_dev, rgb_dev, Q=1):
+        """The colour of the object cloud just encoded ("Colour"): codes one RGB triple per leaf of the octree of the last
+        synchronous `encode_ints` call.  q_dev device int32 [P,3]: the integers that tree was built from; rgb_dev device uint8 [P,3]: the
+        points' 8-bit colours (color.point_colors); Q = 1 .. 255 the step of the three planes (1: lossless on the leaf means).
+        -> (the bytes of `<stream>.color`, report): color.encode_shells' report plus n_points, bits_per_point, bits_per_leaf."""
+        from . import color
+        if self.ring_lod is not None:
+            raise native.ScpError("encode_color with ring_lod: the leaves of such a tree are snapped cells of mixed sizes, and a colour "
+                                  "layer for them is not part of this library")
+        if not self.geom.info:
+            raise native.ScpError("encode_color: no frame to code - call it after a synchronous encode_ints")
+        if len(self.geom.info) != 1:
+            raise native.ScpError(f"encode_color: the colour layer codes the one tree of an object cloud, this frame has {len(self.geom.info)} shells")
+        if q_dev.dim() != 2 or q_dev.shape[1] != 3 or rgb_dev.shape != q_dev.shape or rgb_dev.dtype != torch.uint8:
+            raise native.ScpError(f"encode_color: q int32 [P,3] and rgb uint8 [P,3] expected, got {tuple(q_dev.shape)} and {tuple(rgb_dev.shape)} "
+                                  f"{rgb_dev.dtype}")
+        leaves = self.attr_leaves()
+        data, rep = color.encode_shells(leaves, [int(i.depth) for i in self.geom.info], [q_dev.to(torch.int32).contiguous()], rgb_dev.contiguous(), Q)
+        n_leaves = sum(int(lv.shape[0]) for lv in leaves)
+        rep.update(n_points=int(q_dev.shape[0]), bits_per_point=rep["bits"] / max(int(q_dev.shape[0]), 1), bits_per_leaf=rep["bits"] / max(n_leaves, 1))
+        return data, rep
+
     def preprocess(self, xyz_dev, ints=None):
         # (ring_lod snaps the integers between the quantiser and the build: the route of the integer inputs)
         if ints is None and not self.host_transform and self.ring_lod is None:

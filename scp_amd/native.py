@@ -181,6 +181,13 @@ def lib():
         "scp_attr_inverse": (C.c_int, [_vp, i64, i32, i32, i32, _vp, _vp, _vp, i64, _vp]),
         "scp_attr_level_counts": (C.c_int, [_vp, i64, i32, _vp, _vp, i64, _vp]),
         "scp_attr_pairs": (C.c_int, [_vp, _vp, i64, _vp, i32, _vp, _vp]),
+        "scp_color_leaf_values_workspace_bytes": (C.c_int64, [i64]),
+        "scp_color_forward_workspace_bytes": (C.c_int64, [i64, i32]),
+        "scp_color_inverse_workspace_bytes": (C.c_int64, [i64, i32]),
+        "scp_color_leaf_values": (C.c_int, [_vp, _vp, i64, _vp, i64, i32, _vp, _vp, _vp, _vp, i64, _vp]),
+        "scp_color_forward": (C.c_int, [_vp, _vp, i64, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp]),
+        "scp_color_inverse": (C.c_int, [_vp, i64, i32, i32, _vp, _vp, _vp, _vp, i64, _vp]),
+        "scp_color_pairs": (C.c_int, [_vp, _vp, i64, _vp, i32, _vp, _vp]),
     }
     for name, (res, args) in sig.items():
         if hasattr(L, name):
@@ -2218,6 +2225,74 @@ def attr_inverse(leaves, depth, Q, root, k):
     _check(lib().scp_attr_inverse(leaves.data_ptr(), U, depth, int(Q), int(root), _dev(k, torch.int16), a.data_ptr(), ws.data_ptr(), nb, _stream()),
            "scp_attr_inverse")
     return a
+
+
+# ------------------------------------------------------------------------------------------------- colour layer (csrc/color.hip)
+COLOR_ALPHABET = 1021                                                      # z = 2 |k| - (k > 0), |k| <= 510 (Co / Cg differences)
+
+
+def color_leaf_values(q, rgb, leaves, depth):
+    """scp_color_leaf_values: q device int32 [P,3], rgb device uint8 [P,3], leaves device int32 [U,3] in the order of Geom.leaves ->
+    (rgb_mean uint8 [U,3], ycc int16 [3,U] - the YCoCg-R image of the means, planar -, cnt int32 [U])."""
+    leaves = _attr_leaves(leaves, "color_leaf_values")
+    if q.dim() != 2 or q.shape[1] != 3 or rgb.shape != q.shape:
+        raise ScpError(f"color_leaf_values: q [P,3] and rgb [P,3] expected, got {tuple(q.shape)} and {tuple(rgb.shape)}")
+    U, dev = leaves.shape[0], leaves.device
+    mean = torch.empty((U, 3), dtype=torch.uint8, device=dev)
+    ycc = torch.empty((3, U), dtype=torch.int16, device=dev)
+    cnt = torch.empty(U, dtype=torch.int32, device=dev)
+    ws, nb = _attr_workspace("scp_color_leaf_values_workspace_bytes", dev, U)
+    _check(lib().scp_color_leaf_values(_dev(q, torch.int32), _dev(rgb, torch.uint8), q.shape[0], leaves.data_ptr(), U, int(depth), mean.data_ptr(),
+                                       ycc.data_ptr(), cnt.data_ptr(), ws.data_ptr(), nb, _stream()), "scp_color_leaf_values")
+    return mean, ycc, cnt
+
+
+def color_forward(leaves, ycc, depth, Q):
+    """scp_color_forward: leaves device int32 [U,3], ycc device int16 [3,U] -> dict of device tensors: k int16 [3, U - 1] (every plane in
+    coding order), ctx uint8 [U - 1] (level - 1, shared by the planes), root int32 [3], hist int32 [3 depth, 1021] (row channel * depth +
+    level - 1), level_counts int64 [depth + 1]."""
+    leaves = _attr_leaves(leaves, "color_forward")
+    U, dev, depth = leaves.shape[0], leaves.device, int(depth)
+    if ycc.shape != (3, U):
+        raise ScpError(f"color_forward: ycc [3,{U}] expected for {U} leaves, got {tuple(ycc.shape)}")
+    if not 1 <= depth <= MAX_DEPTH:
+        raise ScpError(f"color_forward: depth {depth} outside 1 .. {MAX_DEPTH}")
+    k = torch.empty((3, max(U - 1, 0)), dtype=torch.int16, device=dev)
+    ctx = torch.empty(max(U - 1, 0), dtype=torch.uint8, device=dev)
+    root = torch.empty(3, dtype=torch.int32, device=dev)
+    hist = torch.empty((3 * depth, COLOR_ALPHABET), dtype=torch.int32, device=dev)
+    counts = torch.empty(depth + 1, dtype=torch.int64, device=dev)
+    ws, nb = _attr_workspace("scp_color_forward_workspace_bytes", dev, U, depth)
+    _check(lib().scp_color_forward(leaves.data_ptr(), _dev(ycc, torch.int16), U, depth, int(Q), k.data_ptr(), ctx.data_ptr(), root.data_ptr(),
+                                   hist.data_ptr(), counts.data_ptr(), ws.data_ptr(), nb, _stream()), "scp_color_forward")
+    return dict(k=k, ctx=ctx, root=root, hist=hist, level_counts=counts)
+
+
+def color_pairs(k, ctx, tables):
+    """scp_color_pairs: k int16 [3,n], ctx uint8 [n], tables uint16 [3 depth, 1022] (all device; torch has the rows as int16) -> lohi int32
+    [3 n] in payload order (Y, Co, Cg), the (c_low, c_high) pairs ac_encode_lohi takes."""
+    if tables.dim() != 2 or tables.shape[1] != COLOR_ALPHABET + 1 or tables.shape[0] % 3 or not 1 <= tables.shape[0] // 3 <= MAX_DEPTH:
+        raise ScpError(f"color_pairs: tables of shape [3 depth, {COLOR_ALPHABET + 1}] expected, got {tuple(tables.shape)}")
+    if k.dim() != 2 or ctx.dim() != 1 or k.shape != (3, ctx.shape[0]):
+        raise ScpError("color_pairs: k [3,n] and one context per coefficient of a plane expected")
+    lohi = torch.empty(3 * ctx.shape[0], dtype=torch.int32, device=k.device)
+    _check(lib().scp_color_pairs(_dev(k, torch.int16), _dev(ctx, torch.uint8), ctx.shape[0], _dev(tables, torch.int16), tables.shape[0] // 3,
+                                 lohi.data_ptr(), _stream()), "scp_color_pairs")
+    return lohi
+
+
+def color_inverse(leaves, depth, Q, root, k):
+    """scp_color_inverse: leaves device int32 [U,3], the roots (three host ints: Y, Co, Cg) and k device int16 [3, U - 1] -> rgb uint8 [U,3]."""
+    leaves = _attr_leaves(leaves, "color_inverse")
+    U, dev, depth = leaves.shape[0], leaves.device, int(depth)
+    if k.shape != (3, max(U - 1, 0)):
+        raise ScpError(f"color_inverse: coefficients [3,{max(U - 1, 0)}] expected for {U} leaves, got {tuple(k.shape)}")
+    r = (C.c_int32 * 3)(*[int(v) for v in root])
+    rgb = torch.empty((U, 3), dtype=torch.uint8, device=dev)
+    ws, nb = _attr_workspace("scp_color_inverse_workspace_bytes", dev, U, depth)
+    _check(lib().scp_color_inverse(leaves.data_ptr(), U, depth, int(Q), C.cast(r, _vp), _dev(k, torch.int16), rgb.data_ptr(), ws.data_ptr(), nb, _stream()),
+           "scp_color_inverse")
+    return rgb
 
 
 # ------------------------------------------------------------------------------------------------- range coder (host)

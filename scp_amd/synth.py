@@ -48,3 +48,29 @@ def write_kitti_bin4(path, xyz, refl):
     """KITTI .bin layout with the reflectance kept: float32 [P,4] (x, y, z, r)."""
     p = np.concatenate([np.asarray(xyz, np.float32)[:, :3], np.asarray(refl, np.float32).reshape(-1, 1)], 1).astype(np.float32)
     p.tofile(path)
+
+
+def synth_object(seed=0, n=4096):
+    """An object cloud as `--type obj` files hold them: int64 [n,3] distinct integer points on the surface of a bumpy sphere inside a 2^10
+    cube (centre 512, radius 380 +- 60 in smooth bumps), in no particular order."""
+    rng = np.random.default_rng(seed)
+    out = np.zeros((0, 3), np.int64)
+    while len(out) < n:
+        d = rng.normal(size=(2 * n, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        r = 380.0 + 40.0 * np.sin(5.0 * d[:, 0] + 1.0) * np.cos(4.0 * d[:, 1]) + 20.0 * np.sin(9.0 * d[:, 2] + 0.3)
+        p = np.clip(np.round(512.0 + d * r[:, None]), 0, 1023).astype(np.int64)
+        out = np.concatenate([out, p])
+        out = out[np.sort(np.unique(out, axis=0, return_index=True)[1])]
+    return np.ascontiguousarray(out[:n])
+
+
+def synth_colors(xyz, seed=0):
+    """Colours for the points of an object cloud, uint8 [P,3]: a smooth gradient along the axes, a texture term (stripes of period ~ 40
+    cells) and noise of sigma 4.  It says nothing about the statistics of a captured 8i / MVUB cloud."""
+    rng = np.random.default_rng(seed)
+    p = np.asarray(xyz, np.float64)[:, :3]
+    u = (p - p.min(0)) / np.maximum(p.max(0) - p.min(0), 1.0)
+    tex = 30.0 * np.sin(2.0 * np.pi * (p[:, 0] + 0.5 * p[:, 1]) / 40.0)
+    c = np.stack([40.0 + 170.0 * u[:, 0] + tex, 60.0 + 120.0 * u[:, 1] - 0.5 * tex, 200.0 - 150.0 * u[:, 2] + 0.25 * tex], 1)
+    return np.clip(np.round(c + rng.normal(0.0, 4.0, size=c.shape)), 0, 255).astype(np.uint8)
