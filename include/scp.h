@@ -567,7 +567,9 @@ SCP_API int scp_attr_pairs(const int16_t *k, const uint8_t *ctx, int64_t n, cons
  *   c[z] | c[z + 1] << 16 of row c * D + ctx[i] of tables uint16 [3 D][1022] (DEVICE; entry 1021 holds 65536 as 0).  |k| is clamped to
  *   510 and ctx to D - 1, so every table read is in range.
  * scp_attr_level_counts serves the decoder unchanged.  Workspaces, SCP_EINVAL and streams as for the reflectance layer; on unsorted or
- * repeated leaves the values are unspecified, but no access leaves the buffers (every level's count is clamped to its host bound). */
+ * repeated leaves the values are unspecified, but no access leaves the buffers: in both layers the workspace holds U entries for level 0
+ * and min(U, 8^(D-j)) for level j, and every level's count is clamped to that where it is produced; level_counts returns the counts as
+ * scanned, before the clamp (equal on Morton-ordered leaves). */
 SCP_API int64_t scp_color_leaf_values_workspace_bytes(int64_t U);             /* bytes, or SCP_EINVAL */
 SCP_API int64_t scp_color_forward_workspace_bytes(int64_t U, int32_t D);      /* bytes, or SCP_EINVAL */
 SCP_API int64_t scp_color_inverse_workspace_bytes(int64_t U, int32_t D);      /* bytes, or SCP_EINVAL */

@@ -80,18 +80,27 @@ def pack(Q, scale, shells):
     return b"".join(head + body)
 
 
+class Reader:
+    """Bounds-checked reads from the bytes of a layer's file; noun ("attribute file", "colour file") opens its refusals."""
+
+    def __init__(self, data, noun):
+        self.data, self.noun, self.pos = bytes(data), noun, 0
+
+    def take(self, n, what):
+        if self.pos + n > len(self.data):
+            raise native.ScpError(f"{self.noun}: truncated in {what} ({len(self.data)} bytes)")
+        self.pos += n
+        return self.data[self.pos - n:self.pos]
+
+    def end(self):
+        if self.pos != len(self.data):
+            raise native.ScpError(f"{self.noun}: {len(self.data) - self.pos} bytes behind the last payload")
+
+
 def unpack(data):
     """The bytes of `<stream>.attr` -> (Q, scale, shells as `pack` takes them); anything else is refused with the reason."""
-    data = bytes(data)
-    pos = [0]
-
-    def take(n, what):
-        if pos[0] + n > len(data):
-            raise native.ScpError(f"attribute file: truncated in {what} ({len(data)} bytes)")
-        b = data[pos[0]:pos[0] + n]
-        pos[0] += n
-        return b
-
+    r = Reader(data, "attribute file")
+    take = r.take
     if take(4, "the magic") != MAGIC:
         raise native.ScpError("attribute file: no 'SCPA' magic - not written by encode*.py --attr")
     version, Q, scale, n = struct.unpack("<BBIB", take(7, "the header"))
@@ -115,8 +124,7 @@ def unpack(data):
         shells.append(s)
     for k, s in enumerate(shells):
         s["payload"] = take(s.pop("length"), f"shell {k}'s payload")
-    if pos[0] != len(data):
-        raise native.ScpError(f"attribute file: {len(data) - pos[0]} bytes behind the last payload")
+    r.end()
     return Q, scale, shells
 
 
@@ -138,6 +146,41 @@ def default_scale(data_type):
     return 1 if data_type == "ford" else 255
 
 
+def encode_payload(f, pairs, alphabet):
+    """f: what a forward entry returns (k, ctx, hist), pairs: the layer's pairs entry -> (choice int [contexts], ideal bits float64
+    [contexts], the payload bytes): one table per context, the device's (c_low, c_high) pairs, the host range coder."""
+    choice, bits = choose_tables(f["hist"].cpu().numpy(), alphabet)
+    dev_tabs = torch.from_numpy(tables(alphabet)[choice].view(np.int16).copy()).to(f["k"].device)
+    lohi = pairs(f["k"], f["ctx"], dev_tabs)
+    return choice, bits, native.ac_encode_lohi(lohi.cpu().numpy())
+
+
+def shells_on_geometry(noun, shells, leaves, depths):
+    """The shells of an unpacked file against the decoded geometry: per shell (k, shell, leaves as contiguous int32, U, D), after the
+    shell count and the shell's D and U were found to be the geometry's.  A generator: every check runs when the caller's loop reaches it,
+    the shell count's at the first step."""
+    if len(shells) != len(leaves):
+        raise native.ScpError(f"{noun}: {len(shells)} shells, the geometry stream has {len(leaves)}")
+    for k, (s, lv, D) in enumerate(zip(shells, leaves, depths)):
+        U, D = int(lv.shape[0]), int(D)
+        if s["D"] != D or s["U"] != U:
+            raise native.ScpError(f"{noun}: shell {k} was coded on {s['U']} leaves of depth {s['D']}, the geometry stream decodes to "
+                                  f"{U} leaves of depth {D} - it belongs to another stream")
+        yield k, s, lv.to(torch.int32).contiguous(), U, D
+
+
+def decode_payload(noun, k, payload, table_of, lv, D, channels, alphabet):
+    """The payload of shell k (U >= 2 leaves lv) -> its coefficients, device int16 [channels, U - 1].  table_of: per context channel * D +
+    (level - 1) the index of its table.  Every coefficient's context follows from the level counts of the tree alone."""
+    U = int(lv.shape[0])
+    level = level_contexts(native.attr_level_counts(lv, D).cpu().numpy())
+    if level.shape[0] != U - 1:
+        raise native.ScpError(f"{noun}: shell {k}'s leaves are not a Morton-ordered set ({level.shape[0]} coefficients for {U} leaves)")
+    ctx = np.concatenate([level + np.uint8(c * D) for c in range(channels)])
+    z = native.AcDecoder(payload, Lp=alphabet + 1).run_ctx(tables(alphabet)[table_of], ctx)
+    return torch.from_numpy(symbols_to_coefficients(z).reshape(channels, U - 1)).to(lv.device)
+
+
 def encode_shells(leaves, depths, qs, refl, Q=1, scale=255):
     """leaves: per shell device int32 [U_s,3] in Morton order (Geom.leaves, a multi-level shell's unknown leaves dropped); depths: per
     shell; qs: per shell the quantised points, device int32 [P,3]; refl device float32 [P].  -> (bytes of the attribute file, report):
@@ -149,7 +192,6 @@ def encode_shells(leaves, depths, qs, refl, Q=1, scale=255):
         raise native.ScpError(f"attribute step Q = {Q} outside 1 .. 255")
     if not 1 <= scale <= 1 << 20:
         raise native.ScpError(f"attribute scale {scale} outside 1 .. 2^20")
-    tabs = tables()
     packed, rep, values, counts, decoded = [], [], [], [], []
     for lv, D, q in zip(leaves, depths, qs):
         U, D = int(lv.shape[0]), int(D)
@@ -168,10 +210,7 @@ def encode_shells(leaves, depths, qs, refl, Q=1, scale=255):
             rep.append(dict(U=1, depth=D, bits=0, level_bits=[], tables=[], root=root))
             decoded.append(a)
             continue
-        choice, bits = choose_tables(f["hist"].cpu().numpy())
-        dev_tabs = torch.from_numpy(tabs[choice].view(np.int16).copy()).to(lv.device)
-        lohi = native.attr_pairs(f["k"], f["ctx"], dev_tabs)
-        payload = native.ac_encode_lohi(lohi.cpu().numpy())
+        choice, bits, payload = encode_payload(f, native.attr_pairs, ALPHABET)
         order = list(range(D - 1, -1, -1))                                       # the file lists j = D .. 1
         packed.append(dict(D=D, U=U, root=root, tables=[int(choice[c]) for c in order], payload=payload))
         rep.append(dict(U=U, depth=D, bits=8 * len(payload), level_bits=[float(bits[c]) for c in order],
@@ -188,28 +227,17 @@ def decode_shells(data, leaves, depths, info=None):
     Q, scale, shells = unpack(data)
     if info is not None:
         info.update(Q=Q, scale=scale)
-    if len(shells) != len(leaves):
-        raise native.ScpError(f"attribute file: {len(shells)} shells, the geometry stream has {len(leaves)}")
-    tabs, out = tables(), []
-    for k, (s, lv, D) in enumerate(zip(shells, leaves, depths)):
-        U = int(lv.shape[0])
-        if s["D"] != int(D) or s["U"] != U:
-            raise native.ScpError(f"attribute file: shell {k} was coded on {s['U']} leaves of depth {s['D']}, the geometry stream decodes to "
-                                  f"{U} leaves of depth {int(D)} - it belongs to another stream")
-        lv = lv.to(torch.int32).contiguous()
+    out = []
+    for k, s, lv, U, D in shells_on_geometry("attribute file", shells, leaves, depths):
         if U == 0:
             out.append(torch.empty(0, dtype=torch.uint8, device=lv.device))
             continue
         if U == 1:
             out.append(torch.full((1,), s["root"], dtype=torch.uint8, device=lv.device))
             continue
-        ctx = level_contexts(native.attr_level_counts(lv, D).cpu().numpy())
-        if ctx.shape[0] != U - 1:
-            raise native.ScpError(f"attribute file: shell {k}'s leaves are not a Morton-ordered set ({ctx.shape[0]} coefficients for {U} leaves)")
-        rows = tabs[[s["tables"][D - 1 - c] for c in range(D)]]                  # row c = the table of context c (level c + 1)
-        z = native.AcDecoder(s["payload"], Lp=ALPHABET + 1).run_ctx(rows, ctx)
-        coef = torch.from_numpy(symbols_to_coefficients(z)).to(lv.device)
-        out.append(native.attr_inverse(lv, D, Q, s["root"], coef))
+        table_of = [s["tables"][D - 1 - c] for c in range(D)]                    # context c is level c + 1; the file lists j = D .. 1
+        coef = decode_payload("attribute file", k, s["payload"], table_of, lv, D, 1, ALPHABET)
+        out.append(native.attr_inverse(lv, D, Q, s["root"], coef[0]))
     return out
 
 

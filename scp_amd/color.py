@@ -48,16 +48,8 @@ def pack(Q, shells):
 
 def unpack(data):
     """The bytes of `<stream>.color` -> (Q, shells as `pack` takes them); anything else is refused with the reason."""
-    data = bytes(data)
-    pos = [0]
-
-    def take(n, what):
-        if pos[0] + n > len(data):
-            raise native.ScpError(f"colour file: truncated in {what} ({len(data)} bytes)")
-        b = data[pos[0]:pos[0] + n]
-        pos[0] += n
-        return b
-
+    r = attr.Reader(data, "colour file")
+    take = r.take
     if take(4, "the magic") != MAGIC:
         raise native.ScpError("colour file: no 'SCPC' magic - not written by encode.py --color")
     version, Q, transform, n = struct.unpack("<BBBB", take(4, "the header"))
@@ -85,8 +77,7 @@ def unpack(data):
         shells.append(s)
     for k, s in enumerate(shells):
         s["payload"] = take(s.pop("length"), f"shell {k}'s payload")
-    if pos[0] != len(data):
-        raise native.ScpError(f"colour file: {len(data) - pos[0]} bytes behind the last payload")
+    r.end()
     return Q, shells
 
 
@@ -103,7 +94,6 @@ def encode_shells(leaves, depths, qs, rgb, Q=1):
     Q = int(Q)
     if not 1 <= Q <= 255:
         raise native.ScpError(f"colour step Q = {Q} outside 1 .. 255")
-    tabs = attr.tables(ALPHABET)
     packed, rep, values, counts, decoded = [], [], [], [], []
     for lv, D, q in zip(leaves, depths, qs):
         U, D = int(lv.shape[0]), int(D)
@@ -121,10 +111,7 @@ def encode_shells(leaves, depths, qs, rgb, Q=1):
             packed.append(dict(D=D, U=1, root=roots))
             rep.append(dict(U=1, depth=D, bits=0, level_bits=[], tables=[], roots=roots))
             continue
-        choice, bits = attr.choose_tables(f["hist"].cpu().numpy(), ALPHABET)          # [3 D], by context
-        dev_tabs = torch.from_numpy(tabs[choice].view(np.int16).copy()).to(lv.device)
-        lohi = native.color_pairs(f["k"], f["ctx"], dev_tabs)
-        payload = native.ac_encode_lohi(lohi.cpu().numpy())
+        choice, bits, payload = attr.encode_payload(f, native.color_pairs, ALPHABET)    # [3 D], by context
         order = _file_order(D)
         packed.append(dict(D=D, U=U, root=roots, tables=[int(choice[c]) for c in order], payload=payload))
         rep.append(dict(U=U, depth=D, bits=8 * len(payload), level_bits=[[float(bits[c]) for c in order[ch * D:(ch + 1) * D]] for ch in range(3)],
@@ -142,28 +129,15 @@ def decode_shells(data, leaves, depths, info=None):
     Q, shells = unpack(data)
     if info is not None:
         info.update(Q=Q)
-    if len(shells) != len(leaves):
-        raise native.ScpError(f"colour file: {len(shells)} shells, the geometry stream has {len(leaves)}")
-    tabs, out = attr.tables(ALPHABET), []
-    for k, (s, lv, D) in enumerate(zip(shells, leaves, depths)):
-        U, D = int(lv.shape[0]), int(D)
-        if s["D"] != D or s["U"] != U:
-            raise native.ScpError(f"colour file: shell {k} was coded on {s['U']} leaves of depth {s['D']}, the geometry stream decodes to "
-                                  f"{U} leaves of depth {D} - it belongs to another stream")
-        lv = lv.to(torch.int32).contiguous()
+    out = []
+    for k, s, lv, U, D in attr.shells_on_geometry("colour file", shells, leaves, depths):
         if U == 0:
             out.append(torch.empty((0, 3), dtype=torch.uint8, device=lv.device))
             continue
         coef = torch.empty((3, 0), dtype=torch.int16, device=lv.device)
         if U >= 2:
-            level = attr.level_contexts(native.attr_level_counts(lv, D).cpu().numpy())
-            if level.shape[0] != U - 1:
-                raise native.ScpError(f"colour file: shell {k}'s leaves are not a Morton-ordered set ({level.shape[0]} coefficients for {U} leaves)")
-            ctx = np.concatenate([level + np.uint8(c * D) for c in range(3)])
             by_ctx = dict(zip(_file_order(D), s["tables"]))
-            rows = tabs[[by_ctx[c] for c in range(3 * D)]]                        # row c = the table of context c
-            z = native.AcDecoder(s["payload"], Lp=ALPHABET + 1).run_ctx(rows, ctx)
-            coef = torch.from_numpy(attr.symbols_to_coefficients(z).reshape(3, U - 1)).to(lv.device)
+            coef = attr.decode_payload("colour file", k, s["payload"], [by_ctx[c] for c in range(3 * D)], lv, D, 3, ALPHABET)
         out.append(native.color_inverse(lv, D, Q, s["root"], coef))
     return out
 

@@ -2,6 +2,7 @@
 values and counts, coefficients, contexts, histograms, level counts, the coder's pairs and the inverse - on the hard trees of
 tests/attr_cases.py and on a multi-level frame, whose dropped last node's leaves must be absent on both sides.  Every comparison is
 exact.  The reference of a case is computed once per process."""
+import ctypes
 import functools
 
 import numpy as np
@@ -173,6 +174,68 @@ def test_multilevel_frame_drops_the_last_nodes_leaves_on_both_sides(tmp_path):
             if Q == 1:
                 assert torch.equal(values[s], rep["values"][s])
         assert [sh["U"] for sh in rep["shells"]] == [len(k) for k in m["kept"]] and all(len(sh["tables"]) == sh["depth"] for sh in rep["shells"])
+
+
+GUARD, PATTERN = 1 << 16, 0xA5
+
+
+def unordered_leaves(name):
+    """Leaf lists that are no Morton-ordered set -> (int32 [U,3], D)."""
+    if name == "two_parents":                                                # level 1 counts 600 heads where 8 entries fit
+        return np.array([[0, 0, 0], [2, 0, 0]] * 300, np.int32), 2
+    if name == "heavy_reversed":
+        c = cases()["heavy"]
+        return np.ascontiguousarray(c["leaves"][::-1], dtype=np.int32), c["D"]
+    return np.array([[3, 1, 6]] * 300, np.int32), 3                          # "one_leaf": 300 copies
+
+
+@pytest.mark.parametrize("name", ["two_parents", "heavy_reversed", "one_leaf"])
+def test_unordered_leaves_leave_every_buffer_intact(name):
+    """The values of both layers are unspecified on such leaves; what is pinned is that no entry writes outside an output or outside the
+    workspace of exactly the size its *_workspace_bytes function returns.  Every written buffer is followed, inside its own allocation, by
+    64 KiB of pattern bytes, so that an index that left a buffer would show in the guard and stay in the test's memory.  (Inputs are only
+    read and carry no guard.)  level_counts are the counts as scanned: the overflowing level stays visible to the host."""
+    from scp_amd import native
+    L = native.lib()
+    leaves, D = unordered_leaves(name)
+    U = len(leaves)
+    lv = up(leaves, np.int32)
+    a = up(np.arange(U) % 251, np.uint8)
+    ycc = up(np.stack([np.arange(U) % 251, np.arange(U) % 509 - 254, np.arange(U) % 499 - 249]), np.int16)
+    st = native._stream()
+    guarded = []
+
+    def buf(nbytes):
+        t = torch.full((nbytes + GUARD,), PATTERN, dtype=torch.uint8, device=dev())
+        guarded.append((t, nbytes))
+        return t.data_ptr()
+
+    def counts_of(entry):
+        t, nbytes = entry
+        return t[:nbytes].cpu().numpy().view(np.int64).tolist()
+
+    nb_a, nb_c = L.scp_attr_forward_workspace_bytes(U, D), L.scp_color_forward_workspace_bytes(U, D)
+    assert nb_a > 0 and nb_c > nb_a and L.scp_attr_inverse_workspace_bytes(U, D) == nb_a and L.scp_color_inverse_workspace_bytes(U, D) == nb_c
+    zeros = torch.zeros(3 * (U - 1), dtype=torch.int16, device=dev())
+    roots = (ctypes.c_int32 * 3)(5, -5, 5)
+    for Q in (1, 255):
+        level_counts = []
+        assert L.scp_attr_forward(lv.data_ptr(), a.data_ptr(), U, D, Q, buf(2 * (U - 1)), buf(U - 1), buf(4), buf(4 * D * 511), buf(8 * (D + 1)),
+                                  buf(nb_a), nb_a, st) == 0
+        level_counts.append(guarded[-2])
+        assert L.scp_attr_level_counts(lv.data_ptr(), U, D, buf(8 * (D + 1)), buf(nb_a), nb_a, st) == 0
+        level_counts.append(guarded[-2])
+        assert L.scp_attr_inverse(lv.data_ptr(), U, D, Q, 5, zeros.data_ptr(), buf(U), buf(nb_a), nb_a, st) == 0
+        assert L.scp_color_forward(lv.data_ptr(), ycc.data_ptr(), U, D, Q, buf(6 * (U - 1)), buf(U - 1), buf(12), buf(4 * 3 * D * 1021),
+                                   buf(8 * (D + 1)), buf(nb_c), nb_c, st) == 0
+        level_counts.append(guarded[-2])
+        assert L.scp_color_inverse(lv.data_ptr(), U, D, Q, ctypes.cast(roots, ctypes.c_void_p), zeros.data_ptr(), buf(3 * U), buf(nb_c), nb_c, st) == 0
+        torch.cuda.synchronize()
+        for t, nbytes in guarded:
+            assert bool((t[nbytes:] == PATTERN).all()), (name, Q, nbytes)
+        if name == "two_parents":
+            assert [counts_of(c)[:2] for c in level_counts] == [[600, 600]] * 3
+        guarded.clear()
 
 
 def test_argument_errors_return_einval_and_launch_nothing():
