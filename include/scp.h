@@ -598,6 +598,38 @@ SCP_API int scp_ac_dec_run_ctx(scp_ac_dec *d, const uint16_t *tables, int32_t nc
 SCP_API int scp_ac_dec_free(scp_ac_dec *d);
 
 /* ------------------------------------------------------------------------------------------------
+ * Chunk-parallel range coder (csrc/ac_chunks.hip, csrc/ac_chunk.h; DESIGN.md 6, "Chunked payloads").  Additive; nothing here knows what
+ * the symbols are.
+ * Chunked payload (normative): n symbols in payload order, a chunk size N of 64 .. 2^20 symbols, C = ceil(n / N) chunks cut by symbol
+ *   index only.  The payload is C chunk lengths (little-endian uint32) followed by the C chunk byte strings.  Chunk c is BY DEFINITION the
+ *   bytes scp_ac_encode_lohi returns for the pairs [c N, min(n, (c + 1) N)): a fresh coder state (low 0, high 2^32 - 1, nothing pending),
+ *   the same flush, the same zero padding of the last byte.  Inside a chunk, bits behind its end read as zero, as in scp_ac_dec; a
+ *   decoder reads no byte outside the chunk it decodes.
+ * Version 2 of `<stream>.attr` and `<stream>.color` (version 1: the layers' sections above and DESIGN.md 6): the version byte is 2, one
+ *   uint32 N follows the fixed header, the rest of the header and the per-shell records are unchanged, and a shell's payload (n = U - 1
+ *   symbols for the reflectance, 3 (U - 1) for the colour: Y, Co, Cg) is a chunked payload whose "payload length" field covers the length
+ *   table and the byte strings.  A reader refuses a version above 2, an N outside 64 .. 2^20, a payload too short for its ceil(n / N)
+ *   lengths and a length table whose sum is not the payload length minus 4 C.
+ * scp_ac_chunks_encode_lohi: lohi uint32 [n] (DEVICE, the pairs scp_ac_encode_lohi takes) -> lengths uint32 [C] (DEVICE), the C chunks
+ *   packed back to back into out (DEVICE, 4-byte aligned, cap bytes), status int32 [1] (DEVICE): 0, or SCP_ESMALL when the chunks do not
+ *   fit into cap - then nothing is written to out, the lengths are still complete - or when a chunk outgrew its workspace slot (pairs that
+ *   no valid table produces; every store is bounds-checked).  One lane codes one chunk, then the lengths are scanned and workgroups pack.
+ *   workspace: device memory, 8-byte aligned, scp_ac_chunks_workspace_bytes(n, N) bytes (C + 1 offsets and C slots of 4 ceil((18 N + 2) /
+ *   32) bytes: a symbol moves at most 18 bits, derived in ac_chunk.h).  The call enqueues and returns; read lengths and status after it.
+ * scp_ac_chunks_decode_ctx: bytes (DEVICE), offsets int64 [C + 1] (DEVICE, ascending, inside bytes: chunk c is bytes[offsets[c] ..
+ *   offsets[c + 1])), tables uint16 [ntab][Lp] and table_of uint8 [nctx] (DEVICE), ctx uint8 [n] (DEVICE) -> sym int16 [n] (DEVICE):
+ *   symbol i decoded against row table_of[ctx[i]], what scp_ac_dec_run_ctx returns on the chunk's bytes (its search, step for step, so
+ *   any table decodes as on the host).  The tables and the map are held in LDS: ntab Lp 2 + nctx <= 65536 bytes.  The caller checks
+ *   ctx[i] < nctx and table_of[c] < ntab; the kernel clamps both, so every table read is in range whatever they hold.
+ * SCP_EINVAL before any launch for: n outside 0 .. 2^31, N outside 64 .. 2^20, cap < 0, ntab or nctx outside 1 .. 256, Lp outside 2 ..
+ * 32768, tables that do not fit into LDS, a NULL or misaligned pointer that the sizes make necessary, a short workspace. */
+SCP_API int64_t scp_ac_chunks_workspace_bytes(int64_t n, int64_t N);             /* bytes, or SCP_EINVAL */
+SCP_API int scp_ac_chunks_encode_lohi(const uint32_t *lohi, int64_t n, int64_t N, uint32_t *lengths, uint8_t *out, int64_t cap, int32_t *status,
+                                      void *workspace, int64_t workspace_bytes, void *stream);
+SCP_API int scp_ac_chunks_decode_ctx(const uint8_t *bytes, const int64_t *offsets, int64_t n, int64_t N, const uint16_t *tables, int32_t ntab, int32_t Lp,
+                                     const uint8_t *table_of, int32_t nctx, const uint8_t *ctx, int16_t *sym, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Legacy octree ABI - the ten symbols data_preproc/OctreeCPP/Octreewarpper.py:17-39 binds, so the
  * reference's own wrapper can load libscp_hip.so in place of Octree_python_lib.so.
  * ---------------------------------------------------------------------------------------------- */

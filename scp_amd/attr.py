@@ -2,7 +2,9 @@
 `<stream>.attr` file, and the two drivers `encode_shells` / `decode_shells` that FrameEncoder.encode_attr and decode_file(attr=True) call.
 
 The transform itself (leaf values, lifting, inverse, the coder's pairs) runs on the device in exact integers; what happens here is the
-choice of one table per octree level (transmitted, so its float arithmetic need not be reproducible), the serial range coder, and bytes."""
+choice of one table per octree level (transmitted, so its float arithmetic need not be reproducible), the serial range coder, and bytes.
+With chunk = N (a version-2 file, DESIGN.md 6, "Chunked payloads") the coder runs on the device too, on all chunks of a payload at once
+(csrc/ac_chunks.hip); the readers take the version from the file."""
 import struct
 
 import numpy as np
@@ -10,7 +12,7 @@ import torch
 
 from . import native
 
-MAGIC, VERSION = b"SCPA", 1
+MAGIC, VERSION, VERSION_CHUNKED = b"SCPA", 1, 2                 # version 2: chunked payloads (include/scp.h, "Chunk-parallel range coder")
 ALPHABET = native.ATTR_ALPHABET
 RATIOS = (32, 64, 96, 128, 152, 176, 192, 208, 216, 224, 232, 238, 243, 247, 250, 253)
 _TABLES = {}
@@ -61,11 +63,52 @@ def choose_tables(hist, alphabet=ALPHABET):
     return choice.astype(np.int64), cost[np.arange(len(choice)), choice]
 
 
-def pack(Q, scale, shells):
-    """shells: per shell dict(D, U, root, tables (D indices for j = D .. 1), payload bytes) -> the bytes of `<stream>.attr`."""
+def chunk_count(n, N):
+    """The chunks of a payload of n symbols at N symbols per chunk."""
+    return -(-int(n) // int(N))
+
+
+def chunked_blob(who, n, N, s):
+    """pack's side of a version-2 payload: the shell's `lengths` (C integers) and `payload` (the C chunks back to back) -> the length
+    table followed by the chunks, after both were found to fit the n symbols of the shell."""
+    lengths, payload = [int(v) for v in s["lengths"]], bytes(s["payload"])
+    if len(lengths) != chunk_count(n, N):
+        raise native.ScpError(f"{who}: {len(lengths)} chunk lengths for {n} symbols in chunks of {N}, {chunk_count(n, N)} expected")
+    if any(not 0 <= v < 1 << 32 for v in lengths) or sum(lengths) != len(payload):
+        raise native.ScpError(f"{who}: the chunk lengths add up to {sum(lengths)}, the chunks hold {len(payload)} bytes")
+    return np.asarray(lengths, "<u4").tobytes() + payload
+
+
+def chunked_split(noun, k, n, N, blob):
+    """unpack's side: the payload of shell k (n symbols, chunks of N) -> (lengths uint32 [C], the chunks back to back); a payload too
+    short for its length table, or whose lengths do not add up to the rest, is refused."""
+    C = chunk_count(n, N)
+    if len(blob) < 4 * C:
+        raise native.ScpError(f"{noun}: shell {k}'s payload of {len(blob)} bytes cannot hold the {C} chunk lengths of {n} symbols in chunks of {N}")
+    lengths = np.frombuffer(blob[:4 * C], "<u4").astype(np.uint32)
+    if int(lengths.sum(dtype=np.int64)) != len(blob) - 4 * C:
+        raise native.ScpError(f"{noun}: shell {k}'s {C} chunk lengths add up to {int(lengths.sum(dtype=np.int64))}, its payload holds "
+                              f"{len(blob) - 4 * C} bytes behind them")
+    return lengths, blob[4 * C:]
+
+
+def read_chunk_size(r):
+    """The chunk size behind the fixed header of a version-2 file (r: its Reader)."""
+    N = struct.unpack("<I", r.take(4, "the chunk size"))[0]
+    if not native.CHUNK_MIN <= N <= native.CHUNK_MAX:
+        raise native.ScpError(f"{r.noun}: a version-{VERSION_CHUNKED} file with a chunk size of {N} symbols, outside {native.CHUNK_MIN} .. 2^20")
+    return N
+
+
+def pack(Q, scale, shells, chunk=None):
+    """shells: per shell dict(D, U, root, tables (D indices for j = D .. 1), payload bytes) -> the bytes of `<stream>.attr`.  chunk = N:
+    a version-2 file - the shells with U >= 2 hold `lengths` (one per chunk of N symbols) and, as `payload`, the chunks back to back;
+    None: version 1."""
     if not 1 <= int(Q) <= 255 or not 1 <= int(scale) <= 1 << 20 or len(shells) > 255:
         raise native.ScpError(f"attr.pack: Q {Q} outside 1 .. 255, scale {scale} outside 1 .. 2^20 or {len(shells)} shells")
-    head, body = [MAGIC + struct.pack("<BBIB", VERSION, int(Q), int(scale), len(shells))], []
+    head, body = [MAGIC + struct.pack("<BBIB", VERSION if chunk is None else VERSION_CHUNKED, int(Q), int(scale), len(shells))], []
+    if chunk is not None:
+        head.append(struct.pack("<I", native.check_chunk(chunk, "attr.pack: chunk size")))
     for s in shells:
         D, U = int(s["D"]), int(s["U"])
         head.append(struct.pack("<BI", D, U))
@@ -75,8 +118,9 @@ def pack(Q, scale, shells):
             idx = [int(t) for t in s["tables"]]
             if len(idx) != D or not all(0 <= t < len(RATIOS) for t in idx):
                 raise native.ScpError(f"attr.pack: {D} table indices below {len(RATIOS)} expected, got {idx}")
-            head.append(bytes(idx) + struct.pack("<I", len(s["payload"])))
-            body.append(bytes(s["payload"]))
+            blob = bytes(s["payload"]) if chunk is None else chunked_blob("attr.pack", U - 1, chunk, s)
+            head.append(bytes(idx) + struct.pack("<I", len(blob)))
+            body.append(blob)
     return b"".join(head + body)
 
 
@@ -97,15 +141,19 @@ class Reader:
             raise native.ScpError(f"{self.noun}: {len(self.data) - self.pos} bytes behind the last payload")
 
 
-def unpack(data):
-    """The bytes of `<stream>.attr` -> (Q, scale, shells as `pack` takes them); anything else is refused with the reason."""
+def unpack(data, info=None):
+    """The bytes of `<stream>.attr` -> (Q, scale, shells as `pack` takes them); anything else is refused with the reason.  info: a dict
+    that receives the file's `version` and `chunk` (N of a version-2 file, whose shells with U >= 2 carry `lengths`; None for version 1)."""
     r = Reader(data, "attribute file")
     take = r.take
     if take(4, "the magic") != MAGIC:
         raise native.ScpError("attribute file: no 'SCPA' magic - not written by encode*.py --attr")
     version, Q, scale, n = struct.unpack("<BBIB", take(7, "the header"))
-    if version != VERSION:
-        raise native.ScpError(f"attribute file: version {version}, this library reads version {VERSION}")
+    if version not in (VERSION, VERSION_CHUNKED):
+        raise native.ScpError(f"attribute file: version {version}, this library reads versions {VERSION} and {VERSION_CHUNKED}")
+    chunk = read_chunk_size(r) if version == VERSION_CHUNKED else None
+    if info is not None:
+        info.update(version=version, chunk=chunk)
     if not 1 <= Q <= 255 or not 1 <= scale <= 1 << 20:
         raise native.ScpError(f"attribute file: Q {Q} outside 1 .. 255 or scale {scale} outside 1 .. 2^20")
     shells = []
@@ -124,6 +172,8 @@ def unpack(data):
         shells.append(s)
     for k, s in enumerate(shells):
         s["payload"] = take(s.pop("length"), f"shell {k}'s payload")
+        if chunk is not None and s["U"] >= 2:
+            s["lengths"], s["payload"] = chunked_split("attribute file", k, s["U"] - 1, chunk, s["payload"])
     r.end()
     return Q, scale, shells
 
@@ -146,13 +196,30 @@ def default_scale(data_type):
     return 1 if data_type == "ford" else 255
 
 
-def encode_payload(f, pairs, alphabet):
+def encode_payload(f, pairs, alphabet, chunk=None, want_overhead=False):
     """f: what a forward entry returns (k, ctx, hist), pairs: the layer's pairs entry -> (choice int [contexts], ideal bits float64
-    [contexts], the payload bytes): one table per context, the device's (c_low, c_high) pairs, the host range coder."""
+    [contexts], the payload): one table per context, the device's (c_low, c_high) pairs, then chunk = None (version 1): the host range
+    coder on the pairs, the payload bytes; chunk = N (version 2): the device coder on all chunks at once - the pairs stay on the device -
+    and the payload as dict(lengths uint32 [C], payload: the chunks back to back, serial_bytes: with want_overhead the size of the
+    version-1 payload of the same pairs, which costs a host coder run, else None)."""
     choice, bits = choose_tables(f["hist"].cpu().numpy(), alphabet)
     dev_tabs = torch.from_numpy(tables(alphabet)[choice].view(np.int16).copy()).to(f["k"].device)
     lohi = pairs(f["k"], f["ctx"], dev_tabs)
-    return choice, bits, native.ac_encode_lohi(lohi.cpu().numpy())
+    if chunk is None:
+        return choice, bits, native.ac_encode_lohi(lohi.cpu().numpy())
+    lengths, data = native.ac_chunks_encode(lohi, chunk)
+    serial = len(native.ac_encode_lohi(lohi.cpu().numpy())) if want_overhead else None
+    return choice, bits, dict(lengths=lengths, payload=data, serial_bytes=serial)
+
+
+def chunk_report(chunk, p):
+    """The chunked fields of a shell's report from encode_payload's version-2 payload p: chunk, chunks, and - where the serial size was
+    asked for - chunk_overhead_bits = the length table + the version-2 chunks - the version-1 payload of the same pairs."""
+    C = int(p["lengths"].shape[0])
+    rep = dict(chunk=int(chunk), chunks=C)
+    if p["serial_bytes"] is not None:
+        rep["chunk_overhead_bits"] = 8 * (4 * C + len(p["payload"]) - p["serial_bytes"])
+    return rep
 
 
 def shells_on_geometry(noun, shells, leaves, depths):
@@ -169,11 +236,22 @@ def shells_on_geometry(noun, shells, leaves, depths):
         yield k, s, lv.to(torch.int32).contiguous(), U, D
 
 
-def decode_payload(noun, k, payload, table_of, lv, D, channels, alphabet):
+def decode_payload(noun, k, payload, table_of, lv, D, channels, alphabet, chunk=None, lengths=None):
     """The payload of shell k (U >= 2 leaves lv) -> its coefficients, device int16 [channels, U - 1].  table_of: per context channel * D +
-    (level - 1) the index of its table.  Every coefficient's context follows from the level counts of the tree alone."""
+    (level - 1) the index of its table.  Every coefficient's context follows from the level counts of the tree alone - so with chunk = N
+    and the chunk lengths (a version-2 file) all chunks are decoded at once on the device, where contexts, symbols and the symbol ->
+    coefficient map stay."""
     U = int(lv.shape[0])
-    level = level_contexts(native.attr_level_counts(lv, D).cpu().numpy())
+    counts = native.attr_level_counts(lv, D)
+    if chunk is not None:
+        reps = (counts[:-1] - counts[1:]).flip(0).clamp(min=0)                  # levels D .. 1
+        level = torch.repeat_interleave(torch.arange(D - 1, -1, -1, dtype=torch.uint8, device=lv.device), reps)
+        if level.shape[0] != U - 1:
+            raise native.ScpError(f"{noun}: shell {k}'s leaves are not a Morton-ordered set ({level.shape[0]} coefficients for {U} leaves)")
+        ctx = torch.cat([level + c * D for c in range(channels)])
+        z = native.ac_chunks_decode(payload, lengths, chunk, tables(alphabet), table_of, ctx, alphabet + 1).to(torch.int32)
+        return torch.where((z & 1) != 0, (z + 1) >> 1, -(z >> 1)).to(torch.int16).reshape(channels, U - 1)
+    level = level_contexts(counts.cpu().numpy())
     if level.shape[0] != U - 1:
         raise native.ScpError(f"{noun}: shell {k}'s leaves are not a Morton-ordered set ({level.shape[0]} coefficients for {U} leaves)")
     ctx = np.concatenate([level + np.uint8(c * D) for c in range(channels)])
@@ -181,13 +259,17 @@ def decode_payload(noun, k, payload, table_of, lv, D, channels, alphabet):
     return torch.from_numpy(symbols_to_coefficients(z).reshape(channels, U - 1)).to(lv.device)
 
 
-def encode_shells(leaves, depths, qs, refl, Q=1, scale=255):
+def encode_shells(leaves, depths, qs, refl, Q=1, scale=255, chunk=None, want_overhead=False):
     """leaves: per shell device int32 [U_s,3] in Morton order (Geom.leaves, a multi-level shell's unknown leaves dropped); depths: per
     shell; qs: per shell the quantised points, device int32 [P,3]; refl device float32 [P].  -> (bytes of the attribute file, report):
     report = dict(Q, scale, shells = [dict(U, depth, bits, level_bits (ideal bits under the chosen table, levels D .. 1), tables, root)],
     bits, values (per shell device uint8 [U]: the leaf values that were coded), counts (int32 [U]: points per leaf), decoded (uint8 [U]:
-    what a decoder gets back - `values` itself at Q = 1))."""
+    what a decoder gets back - `values` itself at Q = 1)).  chunk = N: a version-2 file, every payload cut into chunks of N symbols
+    that the device codes at once (None: version 1, the host coder); the report gains `chunk` and every coded shell `chunk`, `chunks` and,
+    with want_overhead (a host coder run per shell), `chunk_overhead_bits`."""
     Q, scale = int(Q), int(scale)
+    if chunk is not None:
+        chunk = native.check_chunk(chunk, "attribute chunk size")
     if not 1 <= Q <= 255:
         raise native.ScpError(f"attribute step Q = {Q} outside 1 .. 255")
     if not 1 <= scale <= 1 << 20:
@@ -210,21 +292,31 @@ def encode_shells(leaves, depths, qs, refl, Q=1, scale=255):
             rep.append(dict(U=1, depth=D, bits=0, level_bits=[], tables=[], root=root))
             decoded.append(a)
             continue
-        choice, bits, payload = encode_payload(f, native.attr_pairs, ALPHABET)
+        choice, bits, payload = encode_payload(f, native.attr_pairs, ALPHABET, chunk, want_overhead)
         order = list(range(D - 1, -1, -1))                                       # the file lists j = D .. 1
-        packed.append(dict(D=D, U=U, root=root, tables=[int(choice[c]) for c in order], payload=payload))
-        rep.append(dict(U=U, depth=D, bits=8 * len(payload), level_bits=[float(bits[c]) for c in order],
-                        tables=[int(choice[c]) for c in order], root=root))
+        extra = {}
+        if chunk is not None:
+            extra, nbytes = chunk_report(chunk, payload), 4 * len(payload["lengths"]) + len(payload["payload"])
+            packed.append(dict(D=D, U=U, root=root, tables=[int(choice[c]) for c in order], lengths=payload["lengths"], payload=payload["payload"]))
+        else:
+            nbytes = len(payload)
+            packed.append(dict(D=D, U=U, root=root, tables=[int(choice[c]) for c in order], payload=payload))
+        rep.append(dict(U=U, depth=D, bits=8 * nbytes, level_bits=[float(bits[c]) for c in order],
+                        tables=[int(choice[c]) for c in order], root=root, **extra))
         decoded.append(a if Q == 1 else native.attr_inverse(lv, D, Q, root, f["k"]))
-    data = pack(Q, scale, packed)
-    return data, dict(Q=Q, scale=scale, shells=rep, bits=8 * len(data), values=values, counts=counts, decoded=decoded)
+    data = pack(Q, scale, packed, chunk)
+    report = dict(Q=Q, scale=scale, shells=rep, bits=8 * len(data), values=values, counts=counts, decoded=decoded)
+    if chunk is not None:
+        report["chunk"] = chunk
+    return data, report
 
 
 def decode_shells(data, leaves, depths, info=None):
     """The bytes of an attribute file + the decoded geometry (per shell device int32 / int64 [U,3] leaves in the decoder's order, and the
     depths) -> per shell the device uint8 [U] leaf values.  D and U of every shell must be the geometry's.  info: a dict that receives
-    the file's Q and scale."""
-    Q, scale, shells = unpack(data)
+    the file's Q and scale.  The file's version decides the coder: version 1 the host's, version 2 (chunked) the device's."""
+    meta = {}
+    Q, scale, shells = unpack(data, meta)
     if info is not None:
         info.update(Q=Q, scale=scale)
     out = []
@@ -236,7 +328,7 @@ def decode_shells(data, leaves, depths, info=None):
             out.append(torch.full((1,), s["root"], dtype=torch.uint8, device=lv.device))
             continue
         table_of = [s["tables"][D - 1 - c] for c in range(D)]                    # context c is level c + 1; the file lists j = D .. 1
-        coef = decode_payload("attribute file", k, s["payload"], table_of, lv, D, 1, ALPHABET)
+        coef = decode_payload("attribute file", k, s["payload"], table_of, lv, D, 1, ALPHABET, meta["chunk"], s.get("lengths"))
         out.append(native.attr_inverse(lv, D, Q, s["root"], coef[0]))
     return out
 

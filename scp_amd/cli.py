@@ -45,6 +45,10 @@ same stdout block per frame, same summary file.  Differences, all additive:
     (default 1: lossless on the leaf means) - into `<stream>.color` next to the stream, which `decode_ehem.py --color` turns into
     `<stem>.color.ply` (x y z red green blue).  One more line per frame (bits, bits per point, with `--metrics` the luma and RGB PSNR); the
     stream and every other file keep their bytes.
+  * `--chunk [N]` (with `--attr` or `--color`): the layer's file in its version 2 - every payload cut into chunks of N symbols (64 .. 2^20,
+    default 4096), each an independently terminated range-coder stream, which the device codes and `decode_ehem*.py --attr` / `--color`
+    decode all at once (csrc/ac_chunks.hip); costs the length table and a flush per chunk.  The decoders take the version from the file.
+    File names, the per-frame lines and every other file stay as they are.
   * `--normals estimate|DIR` (with `--metrics`, EHEM): the D2 (point-to-plane) PSNR as well, on normals estimated on the device or
     read from the `<DIR>/<sequence>/<frame>.ply` files `gene_normals.py` writes; one more line per frame, `PSNR_D2:` in the summary.
 """
@@ -187,6 +191,16 @@ def color_request(args):
     return None if q is None else int(q)
 
 
+def chunk_request(args):
+    """--chunk [N] -> N, or None without the flag; refused without --attr / --color and outside 64 .. 2^20."""
+    n = getattr(args, "chunk", None)
+    if n is None:
+        return None
+    if getattr(args, "attr", None) is None and getattr(args, "color", None) is None:
+        raise native.ScpError("--chunk cuts the payloads of an attribute layer into chunks: give --attr or --color as well")
+    return native.check_chunk(n, "--chunk")
+
+
 def ply_has_colors(path):
     """Whether the first point line of an ascii PLY holds six tokens that parse (x y z and three colour columns)."""
     if not str(path).endswith(".ply") or not os.path.exists(path):
@@ -281,6 +295,11 @@ def get_args(argv=None, mullevel=False):
                         "of --attr on the three planes with step Q (1 .. 255, default 1: lossless on the leaf means) - into <stream>.color next "
                         "to the stream, which decode_ehem.py --color reads; one more line per frame (bits, bits per point, with --metrics "
                         "the luma and RGB PSNR); the streams do not change")
+    # (absent from the namespace unless given: read it with chunk_request(args))
+    p.add_argument("--chunk", nargs="?", const=native.CHUNK_DEFAULT, type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="with --attr or --color: write the layer's file in its version 2 - every payload in chunks of N symbols (64 .. 2^20, "
+                        "default 4096), each an independently terminated range-coder stream, coded and decoded all at once on the device; "
+                        "decode_ehem*.py take the version from the file; file names and the per-frame lines do not change")
     p.add_argument("--host_transform", action="store_true",
                    help="strict identity with the reference from the frame on: the coordinate transform + quantiser run in numpy float32 on the "
                         "host exactly as data_preprocess.py:42-70 does (the device transform is more accurate, hence not bit-identical); "
@@ -342,6 +361,7 @@ def refuse_unsupported(args, name, mullevel):
         if args.preproc_path:
             raise native.ScpError("--ring_lod with --preproc_path: the record files hold a finished octree, and the option snaps the points "
                                   "before the tree is built")
+    chunk_request(args)
     if attr_request(args)[0] is not None:
         if name == "OctAttention":
             raise native.ScpError("--attr is available for the EHEM encoders only: the OctAttention readers keep no reflectance and their "
@@ -483,7 +503,7 @@ def gene_normals_main(argv=None):
     return written
 
 
-def frame_attr(enc, path, xyz, res, dev, Q, scale, want_psnr):
+def frame_attr(enc, path, xyz, res, dev, Q, scale, want_psnr, chunk=None):
     """--attr: the reflectance column of the frame file `path` through FrameEncoder.encode_attr, on the octree `enc` has just coded ->
     encode_attr's report with `bytes` (the attribute file) and, with want_psnr, `psnr` / `mse_ab` / `mse_ba` (attr.reflectance_psnr
     of the cloud decode_ehem*.py --attr will write: the kept leaves through the decoder's own de-quantiser, with the decoded values)."""
@@ -494,7 +514,7 @@ def frame_attr(enc, path, xyz, res, dev, Q, scale, want_psnr):
         raise native.ScpError(f"--attr: {path} has no reflectance column (KITTI / Ford .bin frames hold x y z r)")
     x_dev = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], np.float32)).to(dev)
     r_dev = torch.from_numpy(np.ascontiguousarray(refl, np.float32).reshape(-1)).to(dev)
-    data, rep = enc.encode_attr(x_dev, r_dev, Q, scale)
+    data, rep = enc.encode_attr(x_dev, r_dev, Q, scale, chunk=chunk)
     rep["bytes"] = data
     if want_psnr:
         qs = shell_qs(enc.data_type, enc.lidar_level, enc.mullevel)
@@ -504,7 +524,7 @@ def frame_attr(enc, path, xyz, res, dev, Q, scale, want_psnr):
     return rep
 
 
-def frame_color(enc, path, xyz, q, res, dev, Q, want_psnr):
+def frame_color(enc, path, xyz, q, res, dev, Q, want_psnr, chunk=None):
     """--color: the colour columns of the object file `path` through FrameEncoder.encode_color, on the octree `enc` has just coded from the
     integers q -> encode_color's report with `bytes` (the colour file) and, with want_psnr, color.color_psnr of the cloud
     decode_ehem.py --color will write (the leaves through the decoder's own de-quantiser, with the decoded colours) against the
@@ -514,7 +534,7 @@ def frame_color(enc, path, xyz, q, res, dev, Q, want_psnr):
     if rgb is None or len(rgb) != len(xyz):
         raise native.ScpError(f"--color: {path} has no colour columns (an ascii PLY with x y z red green blue per point is expected)")
     c_dev = color.point_colors(torch.from_numpy(np.ascontiguousarray(rgb, np.float32)).to(dev))
-    data, rep = enc.encode_color(q, c_dev, Q)
+    data, rep = enc.encode_color(q, c_dev, Q, chunk=chunk)
     rep["bytes"] = data
     if want_psnr:
         x = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], np.float32)).to(dev)
@@ -576,6 +596,7 @@ def main(argv=None, mullevel=False):
     want_depth, depth_drop, depth_edges = depth_request(args)
     attr_q, attr_scale = attr_request(args)
     color_q = color_request(args)
+    chunk = chunk_request(args)
     cls = OctAttention if name == "OctAttention" else EHEM
     if args.random_weights is not None or not args.ckpt_path:
         from .weights import fill_weights
@@ -735,7 +756,7 @@ def main(argv=None, mullevel=False):
             res = enc.encode_ints(q, 0, len(xyz), sequential=args.sequential) if name == "OctAttention" else enc.encode_ints([q], 0, 0.0, len(xyz))
             res["quant"] = [dict(qs=[1.0, 1.0, 1.0], offset=off)]     # the sidecar is the only carrier of the per-axis minimum
             if color_q is not None:
-                crep = frame_color(enc, cur, xyz, q, res, dev, color_q, args.metrics)
+                crep = frame_color(enc, cur, xyz, q, res, dev, color_q, args.metrics, chunk)
         elif name == "OctAttention":
             res = enc.encode(xyz, sequential=args.sequential)
         else:
@@ -751,7 +772,7 @@ def main(argv=None, mullevel=False):
             if want_depth:
                 lrep = enc.depth_report(x_dev, depth_drop, depth_edges)
             if attr_q is not None:
-                arep = frame_attr(enc, cur, xyz, res, dev, attr_q, attr_scale, args.metrics)
+                arep = frame_attr(enc, cur, xyz, res, dev, attr_q, attr_scale, args.metrics, chunk)
         report(cur, res, t0, dist, drep, rrep, lrep, arep, crep)
     for c0, h0, ts in pending:
         report(c0, enc.finish(h0), ts)

@@ -23,12 +23,15 @@ def point_colors(rgb):
     return torch.where(torch.isfinite(c), v, torch.zeros_like(v)).to(torch.uint8).contiguous()
 
 
-def pack(Q, shells):
+def pack(Q, shells, chunk=None):
     """shells: per shell dict(D, U, root (Y, Co, Cg), tables (3 D indices, channel-major, levels D .. 1), payload bytes) -> the bytes of
-    `<stream>.color`."""
+    `<stream>.color`.  chunk = N: a version-2 file - the shells with U >= 2 hold `lengths` (one per chunk of N symbols) and, as
+    `payload`, the chunks back to back; None: version 1."""
     if not 1 <= int(Q) <= 255 or len(shells) > 255:
         raise native.ScpError(f"color.pack: Q {Q} outside 1 .. 255 or {len(shells)} shells")
-    head, body = [MAGIC + struct.pack("<BBBB", VERSION, int(Q), TRANSFORM_YCOCG_R, len(shells))], []
+    head, body = [MAGIC + struct.pack("<BBBB", VERSION if chunk is None else attr.VERSION_CHUNKED, int(Q), TRANSFORM_YCOCG_R, len(shells))], []
+    if chunk is not None:
+        head.append(struct.pack("<I", native.check_chunk(chunk, "color.pack: chunk size")))
     for s in shells:
         D, U = int(s["D"]), int(s["U"])
         head.append(struct.pack("<BI", D, U))
@@ -41,24 +44,29 @@ def pack(Q, shells):
             idx = [int(t) for t in s["tables"]]
             if len(idx) != 3 * D or not all(0 <= t < len(attr.RATIOS) for t in idx):
                 raise native.ScpError(f"color.pack: {3 * D} table indices below {len(attr.RATIOS)} expected, got {idx}")
-            head.append(bytes(idx) + struct.pack("<I", len(s["payload"])))
-            body.append(bytes(s["payload"]))
+            blob = bytes(s["payload"]) if chunk is None else attr.chunked_blob("color.pack", 3 * (U - 1), chunk, s)
+            head.append(bytes(idx) + struct.pack("<I", len(blob)))
+            body.append(blob)
     return b"".join(head + body)
 
 
-def unpack(data):
-    """The bytes of `<stream>.color` -> (Q, shells as `pack` takes them); anything else is refused with the reason."""
+def unpack(data, info=None):
+    """The bytes of `<stream>.color` -> (Q, shells as `pack` takes them); anything else is refused with the reason.  info: a dict that
+    receives the file's `version` and `chunk` (N of a version-2 file, whose shells with U >= 2 carry `lengths`; None for version 1)."""
     r = attr.Reader(data, "colour file")
     take = r.take
     if take(4, "the magic") != MAGIC:
         raise native.ScpError("colour file: no 'SCPC' magic - not written by encode.py --color")
     version, Q, transform, n = struct.unpack("<BBBB", take(4, "the header"))
-    if version != VERSION:
-        raise native.ScpError(f"colour file: version {version}, this library reads version {VERSION}")
+    if version not in (VERSION, attr.VERSION_CHUNKED):
+        raise native.ScpError(f"colour file: version {version}, this library reads versions {VERSION} and {attr.VERSION_CHUNKED}")
     if transform != TRANSFORM_YCOCG_R:
         raise native.ScpError(f"colour file: unknown colour transform {transform}, this library knows {TRANSFORM_YCOCG_R} (YCoCg-R)")
     if not 1 <= Q <= 255:
         raise native.ScpError(f"colour file: Q {Q} outside 1 .. 255")
+    chunk = attr.read_chunk_size(r) if version == attr.VERSION_CHUNKED else None
+    if info is not None:
+        info.update(version=version, chunk=chunk)
     shells = []
     for k in range(n):
         D, U = struct.unpack("<BI", take(5, f"shell {k}"))
@@ -77,6 +85,8 @@ def unpack(data):
         shells.append(s)
     for k, s in enumerate(shells):
         s["payload"] = take(s.pop("length"), f"shell {k}'s payload")
+        if chunk is not None and s["U"] >= 2:
+            s["lengths"], s["payload"] = attr.chunked_split("colour file", k, 3 * (s["U"] - 1), chunk, s["payload"])
     r.end()
     return Q, shells
 
@@ -86,12 +96,15 @@ def _file_order(D):
     return [c * D + j for c in range(3) for j in range(D - 1, -1, -1)]
 
 
-def encode_shells(leaves, depths, qs, rgb, Q=1):
+def encode_shells(leaves, depths, qs, rgb, Q=1, chunk=None, want_overhead=False):
     """leaves: per shell device int32 [U_s,3] in Morton order; depths: per shell; qs: per shell the integer points, device int32 [P,3];
     rgb device uint8 [P,3].  -> (bytes of the colour file, report): report = dict(Q, shells = [dict(U, depth, bits, level_bits ([3][D]:
     ideal bits under the chosen table per channel, levels D .. 1), tables (likewise), roots)], bits, values (per shell device uint8 [U,3]:
-    the leaf means that were coded), counts (int32 [U]), decoded (uint8 [U,3]: what a decoder gets back - `values` itself at Q = 1))."""
+    the leaf means that were coded), counts (int32 [U]), decoded (uint8 [U,3]: what a decoder gets back - `values` itself at Q = 1)).
+    chunk = N / want_overhead: a version-2 file and its report fields, as in attr.encode_shells."""
     Q = int(Q)
+    if chunk is not None:
+        chunk = native.check_chunk(chunk, "colour chunk size")
     if not 1 <= Q <= 255:
         raise native.ScpError(f"colour step Q = {Q} outside 1 .. 255")
     packed, rep, values, counts, decoded = [], [], [], [], []
@@ -111,22 +124,32 @@ def encode_shells(leaves, depths, qs, rgb, Q=1):
             packed.append(dict(D=D, U=1, root=roots))
             rep.append(dict(U=1, depth=D, bits=0, level_bits=[], tables=[], roots=roots))
             continue
-        choice, bits, payload = attr.encode_payload(f, native.color_pairs, ALPHABET)    # [3 D], by context
+        choice, bits, payload = attr.encode_payload(f, native.color_pairs, ALPHABET, chunk, want_overhead)    # [3 D], by context
         order = _file_order(D)
-        packed.append(dict(D=D, U=U, root=roots, tables=[int(choice[c]) for c in order], payload=payload))
-        rep.append(dict(U=U, depth=D, bits=8 * len(payload), level_bits=[[float(bits[c]) for c in order[ch * D:(ch + 1) * D]] for ch in range(3)],
-                        tables=[[int(choice[c]) for c in order[ch * D:(ch + 1) * D]] for ch in range(3)], roots=roots))
+        extra = {}
+        if chunk is not None:
+            extra, nbytes = attr.chunk_report(chunk, payload), 4 * len(payload["lengths"]) + len(payload["payload"])
+            packed.append(dict(D=D, U=U, root=roots, tables=[int(choice[c]) for c in order], lengths=payload["lengths"], payload=payload["payload"]))
+        else:
+            nbytes = len(payload)
+            packed.append(dict(D=D, U=U, root=roots, tables=[int(choice[c]) for c in order], payload=payload))
+        rep.append(dict(U=U, depth=D, bits=8 * nbytes, level_bits=[[float(bits[c]) for c in order[ch * D:(ch + 1) * D]] for ch in range(3)],
+                        tables=[[int(choice[c]) for c in order[ch * D:(ch + 1) * D]] for ch in range(3)], roots=roots, **extra))
         if Q != 1:
             decoded[-1] = native.color_inverse(lv, D, Q, roots, f["k"])
-    data = pack(Q, packed)
-    return data, dict(Q=Q, shells=rep, bits=8 * len(data), values=values, counts=counts, decoded=decoded)
+    data = pack(Q, packed, chunk)
+    report = dict(Q=Q, shells=rep, bits=8 * len(data), values=values, counts=counts, decoded=decoded)
+    if chunk is not None:
+        report["chunk"] = chunk
+    return data, report
 
 
 def decode_shells(data, leaves, depths, info=None):
     """The bytes of a colour file + the decoded geometry (per shell device int32 / int64 [U,3] leaves in the decoder's order, and the
     depths) -> per shell the device uint8 [U,3] leaf colours.  D and U of every shell must be the geometry's.  info: a dict that
-    receives the file's Q."""
-    Q, shells = unpack(data)
+    receives the file's Q.  The file's version decides the coder: version 1 the host's, version 2 (chunked) the device's."""
+    meta = {}
+    Q, shells = unpack(data, meta)
     if info is not None:
         info.update(Q=Q)
     out = []
@@ -137,7 +160,8 @@ def decode_shells(data, leaves, depths, info=None):
         coef = torch.empty((3, 0), dtype=torch.int16, device=lv.device)
         if U >= 2:
             by_ctx = dict(zip(_file_order(D), s["tables"]))
-            coef = attr.decode_payload("colour file", k, s["payload"], [by_ctx[c] for c in range(3 * D)], lv, D, 3, ALPHABET)
+            coef = attr.decode_payload("colour file", k, s["payload"], [by_ctx[c] for c in range(3 * D)], lv, D, 3, ALPHABET, meta["chunk"],
+                                       s.get("lengths"))
         out.append(native.color_inverse(lv, D, Q, s["root"], coef))
     return out
 

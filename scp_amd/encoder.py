@@ -812,11 +812,13 @@ class FrameEncoder(_FrontEnd):
             out.append(lv)
         return out
 
-    def encode_attr(self, xyz_dev, refl_dev, Q=1, scale=None, ints=None):
+    def encode_attr(self, xyz_dev, refl_dev, Q=1, scale=None, ints=None, chunk=None, want_overhead=False):
         """The reflectance of the frame just encoded ("Reflectance"): codes one 8-bit value per leaf of the octree of the last
         `encode` / `preprocess` call, as `distortion` measures that octree - callable after a synchronous call.  xyz_dev device float32
         [P,>=3] and refl_dev device float32 [P] are the frame; Q = 1 .. 255 the step (1: lossless on the leaf values); scale: 8-bit units
-        per unit of reflectance (None: 255 for KITTI, 1 for Ford); ints: the host integers of the frame where the encoder was given them.
+        per unit of reflectance (None: 255 for KITTI, 1 for Ford); ints: the host integers of the frame where the encoder was given them;
+        chunk = N: a version-2 file whose payloads the device codes in chunks of N symbols (None: version 1, the host coder), want_overhead:
+        attr.encode_shells' `chunk_overhead_bits`.
         -> (the bytes of `<stream>.attr`, report): attr.encode_shells' report plus n_points, bits_per_point, bits_per_leaf."""
         from . import attr
         if self.ring_lod is not None:
@@ -835,17 +837,18 @@ class FrameEncoder(_FrontEnd):
             self._infos = infos
         leaves = self.attr_leaves()
         data, rep = attr.encode_shells(leaves, [int(i.depth) for i in self.geom.info], [q.contiguous() for q in qs], refl_dev, Q,
-                                       attr.default_scale(self.data_type) if scale is None else scale)
+                                       attr.default_scale(self.data_type) if scale is None else scale, chunk=chunk, want_overhead=want_overhead)
         n_leaves = sum(int(lv.shape[0]) for lv in leaves)
         rep.update(n_points=int(xyz_dev.shape[0]), bits_per_point=rep["bits"] / max(int(xyz_dev.shape[0]), 1),
                    bits_per_leaf=rep["bits"] / max(n_leaves, 1))
         return data, rep
 
     # ------------------------------------------------------------------------------------------ colour
-    def encode_color(self, q_dev, rgb_dev, Q=1):
+    def encode_color(self, q_dev, rgb_dev, Q=1, chunk=None, want_overhead=False):
         """The colour of the object cloud just encoded ("Colour"): codes one RGB triple per leaf of the octree of the last
         synchronous `encode_ints` call.  q_dev device int32 [P,3]: the integers that tree was built from; rgb_dev device uint8 [P,3]: the
-        points' 8-bit colours (color.point_colors); Q = 1 .. 255 the step of the three planes (1: lossless on the leaf means).
+        points' 8-bit colours (color.point_colors); Q = 1 .. 255 the step of the three planes (1: lossless on the leaf means); chunk = N /
+        want_overhead: a version-2 (chunked) file and its report fields, as for encode_attr.
         -> (the bytes of `<stream>.color`, report): color.encode_shells' report plus n_points, bits_per_point, bits_per_leaf."""
         from . import color
         if self.ring_lod is not None:
@@ -859,7 +862,8 @@ class FrameEncoder(_FrontEnd):
             raise native.ScpError(f"encode_color: q int32 [P,3] and rgb uint8 [P,3] expected, got {tuple(q_dev.shape)} and {tuple(rgb_dev.shape)} "
                                   f"{rgb_dev.dtype}")
         leaves = self.attr_leaves()
-        data, rep = color.encode_shells(leaves, [int(i.depth) for i in self.geom.info], [q_dev.to(torch.int32).contiguous()], rgb_dev.contiguous(), Q)
+        data, rep = color.encode_shells(leaves, [int(i.depth) for i in self.geom.info], [q_dev.to(torch.int32).contiguous()], rgb_dev.contiguous(), Q,
+                                        chunk=chunk, want_overhead=want_overhead)
         n_leaves = sum(int(lv.shape[0]) for lv in leaves)
         rep.update(n_points=int(q_dev.shape[0]), bits_per_point=rep["bits"] / max(int(q_dev.shape[0]), 1), bits_per_leaf=rep["bits"] / max(n_leaves, 1))
         return data, rep

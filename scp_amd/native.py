@@ -188,6 +188,9 @@ def lib():
         "scp_color_forward": (C.c_int, [_vp, _vp, i64, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp]),
         "scp_color_inverse": (C.c_int, [_vp, i64, i32, i32, _vp, _vp, _vp, _vp, i64, _vp]),
         "scp_color_pairs": (C.c_int, [_vp, _vp, i64, _vp, i32, _vp, _vp]),
+        "scp_ac_chunks_workspace_bytes": (C.c_int64, [i64, i64]),
+        "scp_ac_chunks_encode_lohi": (C.c_int, [_vp, i64, i64, _vp, _vp, i64, _vp, _vp, i64, _vp]),
+        "scp_ac_chunks_decode_ctx": (C.c_int, [_vp, _vp, i64, i64, _vp, i32, i32, _vp, i32, _vp, _vp, _vp]),
     }
     for name, (res, args) in sig.items():
         if hasattr(L, name):
@@ -2326,6 +2329,81 @@ def ac_encode_lohi(lohi):
             continue
         _check(rc, "scp_ac_encode_lohi")
         return out[: n.value].tobytes()
+
+
+# ------------------------------------------------------------------------------------------------- chunk-parallel range coder (csrc/ac_chunks.hip)
+CHUNK_MIN, CHUNK_MAX, CHUNK_DEFAULT = 64, 1 << 20, 4096
+
+
+def check_chunk(N, who="chunk size"):
+    """The chunk size of a chunked payload as an int; outside 64 .. 2^20 symbols it is refused."""
+    if isinstance(N, bool) or int(N) != N or not CHUNK_MIN <= int(N) <= CHUNK_MAX:
+        raise ScpError(f"{who} {N}: {CHUNK_MIN} .. 2^20 symbols per chunk expected")
+    return int(N)
+
+
+def ac_chunks_encode(lohi_dev, N, cap=None):
+    """scp_ac_chunks_encode_lohi: lohi device int32 [n] (the pairs ac_encode_lohi takes), N symbols per chunk -> (lengths numpy uint32 [C],
+    the C chunks back to back as bytes): chunk c is ac_encode_lohi(lohi[c N:(c + 1) N]), byte for byte, all chunks coded at once on the
+    device.  One wait (the lengths), then exactly the packed bytes cross; the pairs stay on the device.  cap: the size of the device
+    buffer the chunks are packed into (default: the slots' bound, which cannot be too small); SCP_ESMALL when they do not fit."""
+    N = check_chunk(N)
+    if lohi_dev.dim() != 1 or lohi_dev.dtype != torch.int32:
+        raise ScpError(f"ac_chunks_encode: pairs int32 [n] expected, got {lohi_dev.dtype} {tuple(lohi_dev.shape)}")
+    n, dev = lohi_dev.shape[0], lohi_dev.device
+    nchunks = -(-n // N)
+    nb = _check(lib().scp_ac_chunks_workspace_bytes(n, N), "scp_ac_chunks_workspace_bytes")
+    ws = torch.empty(nb // 8 + 1, dtype=torch.int64, device=dev)
+    cap = nb if cap is None else int(cap)
+    out = torch.empty(cap // 4 + 1, dtype=torch.int32, device=dev)
+    head = torch.empty(nchunks + 1, dtype=torch.int32, device=dev)          # the lengths, then the status word
+    _check(lib().scp_ac_chunks_encode_lohi(_dev(lohi_dev), n, N, head.data_ptr(), out.data_ptr(), cap, head.data_ptr() + 4 * nchunks, ws.data_ptr(), nb,
+                                           _stream()), "scp_ac_chunks_encode_lohi")
+    h = head.cpu().numpy()
+    _check(int(h[nchunks]), "scp_ac_chunks_encode_lohi")
+    lengths = h[:nchunks].view(np.uint32).copy()
+    total = int(lengths.sum(dtype=np.int64))
+    return lengths, out.view(torch.uint8)[:total].cpu().numpy().tobytes()
+
+
+def ac_chunks_decode(payload_bytes, lengths, N, tables, table_of, ctx_dev, Lp):
+    """scp_ac_chunks_decode_ctx: the chunk bytes back to back, their lengths (C integers), N symbols per chunk, tables uint16 / int16 numpy
+    [ntab, Lp], table_of (nctx table indices), ctx device uint8 [n] -> device int16 [n]: symbol i decoded against row table_of[ctx[i]],
+    chunk c being what AcDecoder(chunk c, Lp).run_ctx returns on its contexts; all chunks at once on the device.  A length table that
+    does not have ceil(n / N) entries or does not add up to the bytes, a context >= nctx and a table index >= ntab are refused."""
+    N = check_chunk(N)
+    tables = np.ascontiguousarray(tables).view(np.uint16)
+    table_of = np.ascontiguousarray(table_of, np.int64).reshape(-1)
+    if tables.ndim != 2 or tables.shape[1] != int(Lp) or tables.shape[0] < 1:
+        raise ScpError(f"ac_chunks_decode: tables of shape [ntab, {Lp}] expected, got {tables.shape}")
+    if ctx_dev.dim() != 1 or ctx_dev.dtype != torch.uint8:
+        raise ScpError(f"ac_chunks_decode: contexts uint8 [n] expected, got {ctx_dev.dtype} {tuple(ctx_dev.shape)}")
+    n, dev = ctx_dev.shape[0], ctx_dev.device
+    nchunks = -(-n // N)
+    lengths = np.asarray(lengths, np.int64).reshape(-1)
+    data = np.frombuffer(bytes(payload_bytes), np.uint8)
+    if lengths.shape[0] != nchunks:
+        raise ScpError(f"ac_chunks_decode: {lengths.shape[0]} chunk lengths for {n} symbols in chunks of {N}: {nchunks} expected")
+    if (lengths < 0).any() or int(lengths.sum()) != data.shape[0]:
+        raise ScpError(f"ac_chunks_decode: the chunk lengths add up to {int(lengths.sum())}, the chunks hold {data.shape[0]} bytes")
+    nctx, ntab = table_of.shape[0], tables.shape[0]
+    if not 1 <= nctx <= 256 or (table_of < 0).any() or (table_of >= ntab).any():
+        raise ScpError(f"ac_chunks_decode: 1 .. 256 contexts with a table index below {ntab} each expected, got {table_of.tolist()}")
+    sym = torch.empty(n, dtype=torch.int16, device=dev)
+    if n == 0:
+        return sym
+    top = int(ctx_dev.max().item())
+    if top >= nctx:
+        raise ScpError(f"ac_chunks_decode: context {top} of {nctx}")
+    offsets = np.zeros(nchunks + 1, np.int64)
+    np.cumsum(lengths, out=offsets[1:])
+    d_bytes = torch.from_numpy(data.copy()).to(dev)
+    d_off = torch.from_numpy(offsets).to(dev)
+    d_tab = torch.from_numpy(tables.view(np.int16).copy()).to(dev)
+    d_map = torch.from_numpy(table_of.astype(np.uint8)).to(dev)
+    _check(lib().scp_ac_chunks_decode_ctx(d_bytes.data_ptr(), d_off.data_ptr(), n, N, d_tab.data_ptr(), ntab, int(Lp), d_map.data_ptr(), nctx,
+                                          _dev(ctx_dev), sym.data_ptr(), _stream()), "scp_ac_chunks_decode_ctx")
+    return sym
 
 
 class AcDecoder:
