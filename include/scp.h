@@ -582,6 +582,35 @@ SCP_API int scp_color_inverse(const int32_t *leaves, int64_t U, int32_t D, int32
 SCP_API int scp_color_pairs(const int16_t *k, const uint8_t *ctx, int64_t n, const uint16_t *tables, int32_t D, uint32_t *lohi, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Step sweep of the attribute layers (csrc/lift.h through csrc/attr.hip and csrc/color.hip; DESIGN.md 6, "Step sweep").  Additive.
+ * The transform is open-loop: every mean m and every difference d of the two layers above is taken from exact values and does not
+ * depend on Q; Q enters through s = max(1, isqrt((Q Q W) // (w[lo] w[hi]))) and k = sign(d) ((|d| + (s >> 1)) // s) alone.  For a grid
+ * steps int32 [G] (HOST, 1 <= G <= SCP_SWEEP_MAX_STEPS, strictly ascending, every step in 1 .. 255) and every g (normative):
+ *   hist[g]   int32 [C D][ALPHABET] = the hist of scp_attr_forward (C = 1, 511 symbols) / scp_color_forward (C = 3, 1021 symbols) at
+ *             Q = steps[g], bit for bit: |k| clamped to 255 / 510, z = 2 |k| - (k > 0), row channel * D + (level - 1).
+ *   sse[g]    uint64 [C_out] (C_out = 1: the reflectance; 3: R, G, B) = the sum over the leaves of (x - x^)^2, x the value that was coded
+ *             (a uint8 [U]; rgb_mean uint8 [U][3]) and x^ what scp_attr_inverse / scp_color_inverse returns for the k and the root of the
+ *             forward entry at Q = steps[g] - after the layer's epilogue: the clamp to 0 .. 255, for the colour behind the inverse colour
+ *             transform.  Zero at Q = 1.
+ *   linf[g]   uint32 [C_out] = the largest |x - x^| of the same comparison.
+ * root int32 [C] and level_counts int64 [D + 1] as the forward entry writes them (neither depends on Q).  All outputs DEVICE, zeroed by
+ * the call; scp_color_sweep takes ycc int16 [3][U] and rgb_mean uint8 [U][3] as scp_color_leaf_values wrote them.  Integer arithmetic
+ * and integer atomics only: the outputs are functions of the inputs.  U == 0 writes zeros; U == 1 zeros, the root and the counts, and
+ * launches nothing that reads a coefficient.  workspace: device memory, 8-byte aligned, scp_*_sweep_workspace_bytes(U, D, G) bytes.
+ * SCP_EINVAL before any launch for the forward entries' reasons and for G outside 1 .. SCP_SWEEP_MAX_STEPS, steps NULL, a step outside
+ * 1 .. 255, steps that do not strictly ascend, a NULL output.  Both enqueue on `stream` and wait for nothing; on unsorted or repeated
+ * leaves the values are unspecified, but no access leaves the buffers. */
+#define SCP_SWEEP_MAX_STEPS 16
+SCP_API int64_t scp_attr_sweep_workspace_bytes(int64_t U, int32_t D, int32_t G);    /* bytes, or SCP_EINVAL */
+SCP_API int64_t scp_color_sweep_workspace_bytes(int64_t U, int32_t D, int32_t G);   /* bytes, or SCP_EINVAL */
+SCP_API int scp_attr_sweep(const int32_t *leaves, const uint8_t *a, int64_t U, int32_t D, const int32_t *steps, int32_t G, int32_t *hist,
+                           uint64_t *sse, uint32_t *linf, int32_t *root, int64_t *level_counts, void *workspace, int64_t workspace_bytes,
+                           void *stream);
+SCP_API int scp_color_sweep(const int32_t *leaves, const int16_t *ycc, const uint8_t *rgb_mean, int64_t U, int32_t D, const int32_t *steps,
+                            int32_t G, int32_t *hist, uint64_t *sse, uint32_t *linf, int32_t *root, int64_t *level_counts, void *workspace,
+                            int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Range coder (host, serial) - replaces numpyAc/backend/numpyAc_backend.cpp
  *   encode_cdf :327-334 / encode :245-323  ->  scp_ac_encode_cdf, scp_ac_encode_lohi
  *   class decode :134-217                  ->  scp_ac_dec_*

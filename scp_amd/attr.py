@@ -311,6 +311,109 @@ def encode_shells(leaves, depths, qs, refl, Q=1, scale=255, chunk=None, want_ove
     return data, report
 
 
+TARGET_KINDS = ("psnr", "bpp", "linf")
+
+
+def check_target(target, who="target"):
+    """(kind, value) of a rate or quality target -> (kind, float value): kind is one of TARGET_KINDS, value finite and >= 0."""
+    try:
+        kind, value = target
+        value = float(value)
+    except (TypeError, ValueError):
+        raise native.ScpError(f"{who}: a pair (kind, value) expected, got {target!r}") from None
+    if kind not in TARGET_KINDS:
+        raise native.ScpError(f"{who}: unknown kind {kind!r}, one of {', '.join(TARGET_KINDS)} expected")
+    if not np.isfinite(value) or value < 0:
+        raise native.ScpError(f"{who}: {kind}={value} - a finite value >= 0 expected")
+    return kind, value
+
+
+def leaf_psnr(sse, n):
+    """10 log10(255^2 n / sse) over n leaf values with the squared error sse; inf at zero error (and for no value at all)."""
+    return float("inf") if sse == 0 or n == 0 else 10.0 * float(np.log10(255.0 ** 2 * n / sse))
+
+
+def sweep_rows(steps, channels, frame_bytes, shells):
+    """The table of a frame's sweep: steps [G]; frame_bytes the header and shell records `pack` writes for the frame (no payload);
+    shells: per coded shell (U, hist [G, contexts, alphabet], sse [G, channels], linf [G, channels]) as host arrays, per uncoded shell
+    (U, None, None, None).  -> per step dict(Q, table_bits, est_bits, sse, linf, leaves, psnr) and, for more than one channel, sse_rgb /
+    linf_rgb / psnr_rgb per channel.  PSNR is over leaf values - what the layer codes against what it returns."""
+    U_all = sum(int(s[0]) for s in shells)
+    rows = []
+    for g, Q in enumerate(steps):
+        table_bits, nbytes = 0.0, int(frame_bytes)
+        sse, linf = [0] * channels, [0] * channels
+        for U, hist, s2, smax in shells:
+            if hist is None:
+                continue
+            bits = float(choose_tables(hist[g], hist.shape[-1])[1].sum())
+            table_bits += bits
+            nbytes += int(np.ceil(bits / 8.0))
+            sse = [a + int(b) for a, b in zip(sse, s2[g])]
+            linf = [max(a, int(b)) for a, b in zip(linf, smax[g])]
+        row = dict(Q=int(Q), table_bits=table_bits, est_bits=8 * nbytes, sse=sum(sse), linf=max(linf), leaves=U_all,
+                   psnr=leaf_psnr(sum(sse), channels * U_all))
+        if channels > 1:
+            row.update(sse_rgb=sse, linf_rgb=linf, psnr_rgb=[leaf_psnr(v, U_all) for v in sse])
+        rows.append(row)
+    return rows
+
+
+def record_bytes(D, U):
+    """The bytes of a shell's record in the header of `<stream>.attr`: D, U, the root (U >= 1), D table indices and the payload length
+    (U >= 2)."""
+    return 5 + (1 if U >= 1 else 0) + (D + 4 if U >= 2 else 0)
+
+
+def sweep_shells(leaves, depths, qs, refl, scale=255, steps=None):
+    """One pass per shell over a grid of steps (native.attr_sweep; DESIGN.md 6, "Step sweep"), summed over the shells of a frame since a
+    file has one Q.  Arguments as encode_shells'; steps: native.sweep_steps.  -> dict(steps, points, leaves, rows): per step Q, table_bits
+    (choose_tables on that step's histograms, summed over contexts and shells, float64), est_bits (8 x (the header and shell-record bytes
+    of a version-1 file + ceil(table_bits / 8) per coded shell)), sse, linf, leaves, psnr = 10 log10(255^2 leaves / sse) - the PSNR over
+    LEAF VALUES, what the layer codes against what it returns, not the point-wise nearest-neighbour PSNR of --metrics."""
+    scale = int(scale)
+    if not 1 <= scale <= 1 << 20:
+        raise native.ScpError(f"attribute scale {scale} outside 1 .. 2^20")
+    grid = native.sweep_steps(steps)
+    if len(leaves) > 255:
+        raise native.ScpError(f"attr.sweep_shells: {len(leaves)} shells, an attribute file holds at most 255")
+    frame_bytes, shells = 4 + 7, []
+    for lv, D, q in zip(leaves, depths, qs):
+        U, D = int(lv.shape[0]), int(D)
+        frame_bytes += record_bytes(D, U)
+        if U < 2:
+            shells.append((U, None, None, None))
+            continue
+        a, _ = native.attr_leaf_values(q, refl, lv, D, scale)
+        s = native.attr_sweep(lv, a, D, grid)
+        shells.append((U, s["hist"].cpu().numpy(), s["sse"].cpu().numpy(), s["linf"].cpu().numpy()))
+    return dict(steps=[int(v) for v in grid], points=int(refl.shape[0]), leaves=sum(s[0] for s in shells),
+                rows=sweep_rows(grid, 1, frame_bytes, shells))
+
+
+def choose_step(sweep, kind, value):
+    """The step of a sweep table (sweep_shells) for a target: psnr - the largest step whose leaf PSNR is >= value; linf - the largest step
+    whose largest error (over the channels) is <= value; bpp - the smallest step whose est_bits <= value x points.  Every row is looked
+    at: the error need not grow with the step.  No step qualifies: the smallest step for psnr / linf, the largest for bpp, met = False.
+    -> dict(kind, value, Q, index, met).  A pure host function."""
+    kind, value = check_target((kind, value), "choose_step")
+    rows = sweep["rows"]
+    if not rows:
+        raise native.ScpError("choose_step: an empty sweep table")
+    if kind == "psnr":
+        ok = [i for i, r in enumerate(rows) if r["psnr"] >= value]
+    elif kind == "linf":
+        ok = [i for i, r in enumerate(rows) if r["linf"] <= value]
+    else:
+        ok = [i for i, r in enumerate(rows) if r["est_bits"] <= value * sweep["points"]]
+    by_q = sorted(range(len(rows)), key=lambda i: rows[i]["Q"])
+    if ok:
+        i = (min if kind == "bpp" else max)(ok, key=lambda i: rows[i]["Q"])
+    else:
+        i = by_q[-1] if kind == "bpp" else by_q[0]
+    return dict(kind=kind, value=value, Q=int(rows[i]["Q"]), index=i, met=bool(ok))
+
+
 def decode_shells(data, leaves, depths, info=None):
     """The bytes of an attribute file + the decoded geometry (per shell device int32 / int64 [U,3] leaves in the decoder's order, and the
     depths) -> per shell the device uint8 [U] leaf values.  D and U of every shell must be the geometry's.  info: a dict that receives

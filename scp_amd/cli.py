@@ -49,6 +49,16 @@ same stdout block per frame, same summary file.  Differences, all additive:
     default 4096), each an independently terminated range-coder stream, which the device codes and `decode_ehem*.py --attr` / `--color`
     decode all at once (csrc/ac_chunks.hip); costs the length table and a flush per chunk.  The decoders take the version from the file.
     File names, the per-frame lines and every other file stay as they are.
+  * `--attr_sweep [STEPS]` / `--color_sweep [STEPS]` (with `--attr` / `--color`): what every step of a grid (comma-separated, strictly ascending,
+    1 .. 255, at most 16; default 1,2,3,4,6,8,12,16,24,32,48,64,96,128,192,255) costs and loses on the frame, from one pass over the octree
+    (csrc/lift.h: scp_attr_sweep / scp_color_sweep).  One more line per frame (per step Q: estimated bits per point, leaf PSNR) and
+    `<stream>.attr.sweep.json` / `<stream>.color.sweep.json`; every other file keeps its bytes.  The PSNR is over leaf values - what the layer
+    codes against what it returns - not the point-wise PSNR of `--metrics`.
+  * `--attr_target KIND=VALUE` / `--color_target KIND=VALUE` (with `--attr` / `--color` without a Q), KIND `psnr`, `bpp` or `linf`: the layer's
+    file is written at the step the sweep chooses per frame - the largest whose leaf PSNR is >= VALUE, the smallest whose estimated bits are
+    <= VALUE per point, the largest whose largest leaf error is <= VALUE; where no step qualifies, the smallest (the largest for `bpp`), reported
+    as not met.  One more line per frame (target, chosen Q, met, estimated / written bits); with `--attr_sweep` / `--color_sweep` alongside, the
+    target chooses on that grid and the table is written too.  The decoders read the chosen Q from the header as before.
   * `--normals estimate|DIR` (with `--metrics`, EHEM): the D2 (point-to-plane) PSNR as well, on normals estimated on the device or
     read from the `<DIR>/<sequence>/<frame>.ply` files `gene_normals.py` writes; one more line per frame, `PSNR_D2:` in the summary.
 """
@@ -191,6 +201,42 @@ def color_request(args):
     return None if q is None else int(q)
 
 
+def sweep_request(args, layer):
+    """--<layer>_sweep [STEPS] / --<layer>_target KIND=VALUE (layer: "attr" or "color") -> (steps: numpy int32 [G] or None without
+    --<layer>_sweep, target: (kind, value) or None without --<layer>_target).  Refused with the reason: either option without --<layer>, a
+    step Q other than 1 together with a target, an unknown kind, a value that is not finite or negative, a grid that is empty, longer
+    than 16, not strictly ascending or outside 1 .. 255."""
+    from . import attr
+    sw, tg, q = getattr(args, layer + "_sweep", None), getattr(args, layer + "_target", None), getattr(args, layer, None)
+    what = "the reflectance layer" if layer == "attr" else "the colour layer"
+    if q is None and (sw is not None or tg is not None):
+        opt = f"--{layer}_sweep" if sw is not None else f"--{layer}_target"
+        raise native.ScpError(f"{opt} measures or sets the step of {what}: give --{layer} as well")
+    steps = target = None
+    if sw is not None:
+        if isinstance(sw, str):
+            try:
+                sw = None if sw == "" else [int(t) for t in sw.split(",")]
+            except ValueError:
+                raise native.ScpError(f"--{layer}_sweep {sw}: comma-separated integer steps expected, e.g. 1,2,4,8") from None
+        try:
+            steps = native.sweep_steps(sw)
+        except native.ScpError as e:
+            raise native.ScpError(f"--{layer}_sweep: {e}") from None
+    if tg is not None:
+        kind, sep, val = str(tg).partition("=")
+        try:
+            value = float(val)
+        except ValueError:
+            raise native.ScpError(f"--{layer}_target {tg}: KIND=VALUE expected, KIND one of {', '.join(attr.TARGET_KINDS)}") from None
+        if not sep:
+            raise native.ScpError(f"--{layer}_target {tg}: KIND=VALUE expected, KIND one of {', '.join(attr.TARGET_KINDS)}")
+        target = attr.check_target((kind, value), f"--{layer}_target")
+        if int(q) != 1:
+            raise native.ScpError(f"--{layer} {q} with --{layer}_target: the target chooses the step - give --{layer} without a Q")
+    return steps, target
+
+
 def chunk_request(args):
     """--chunk [N] -> N, or None without the flag; refused without --attr / --color and outside 64 .. 2^20."""
     n = getattr(args, "chunk", None)
@@ -295,6 +341,17 @@ def get_args(argv=None, mullevel=False):
                         "of --attr on the three planes with step Q (1 .. 255, default 1: lossless on the leaf means) - into <stream>.color next "
                         "to the stream, which decode_ehem.py --color reads; one more line per frame (bits, bits per point, with --metrics "
                         "the luma and RGB PSNR); the streams do not change")
+    # (absent from the namespace unless given: read them with sweep_request(args, "attr") / sweep_request(args, "color"))
+    for layer, noun in (("attr", "reflectance"), ("color", "colour")):
+        p.add_argument(f"--{layer}_sweep", nargs="?", const="", default=argparse.SUPPRESS, metavar="STEPS",
+                       help=f"with --{layer}: what every step of a grid costs and loses on this frame's {noun}, from one pass over the octree - "
+                            "STEPS comma-separated, strictly ascending, 1 .. 255, at most 16 (default 1,2,3,4,6,8,12,16,24,32,48,64,96,128,192,255); "
+                            f"one more line per frame (per step: estimated bits per point, leaf PSNR) and <stream>.{layer}.sweep.json; the PSNR "
+                            "is over leaf values, not the point-wise PSNR of --metrics; every other file keeps its bytes")
+        p.add_argument(f"--{layer}_target", default=argparse.SUPPRESS, metavar="KIND=VALUE",
+                       help=f"with --{layer} (without a Q): choose the step per frame from the sweep - psnr=DB: the largest step whose leaf PSNR is "
+                            "at least DB; bpp=B: the smallest step whose estimated bits stay within B bits per point; linf=E: the largest step "
+                            "whose largest leaf error is at most E; one more line per frame (target, chosen Q, met, estimated against written bits)")
     # (absent from the namespace unless given: read it with chunk_request(args))
     p.add_argument("--chunk", nargs="?", const=native.CHUNK_DEFAULT, type=int, default=argparse.SUPPRESS, metavar="N",
                    help="with --attr or --color: write the layer's file in its version 2 - every payload in chunks of N symbols (64 .. 2^20, "
@@ -362,6 +419,8 @@ def refuse_unsupported(args, name, mullevel):
             raise native.ScpError("--ring_lod with --preproc_path: the record files hold a finished octree, and the option snaps the points "
                                   "before the tree is built")
     chunk_request(args)
+    sweep_request(args, "attr")
+    sweep_request(args, "color")
     if attr_request(args)[0] is not None:
         if name == "OctAttention":
             raise native.ScpError("--attr is available for the EHEM encoders only: the OctAttention readers keep no reflectance and their "
@@ -503,10 +562,11 @@ def gene_normals_main(argv=None):
     return written
 
 
-def frame_attr(enc, path, xyz, res, dev, Q, scale, want_psnr, chunk=None):
+def frame_attr(enc, path, xyz, res, dev, Q, scale, want_psnr, chunk=None, steps=None, target=None):
     """--attr: the reflectance column of the frame file `path` through FrameEncoder.encode_attr, on the octree `enc` has just coded ->
     encode_attr's report with `bytes` (the attribute file) and, with want_psnr, `psnr` / `mse_ab` / `mse_ba` (attr.reflectance_psnr
-    of the cloud decode_ehem*.py --attr will write: the kept leaves through the decoder's own de-quantiser, with the decoded values)."""
+    of the cloud decode_ehem*.py --attr will write: the kept leaves through the decoder's own de-quantiser, with the decoded values).
+    steps / target: sweep_request's - the step from the target, and with steps alone the table of FrameEncoder.attr_sweep as `sweep`."""
     from . import attr
     from .decoder import dequantise_leaves, shell_qs
     refl = pointCloud.pcread(path)[1]
@@ -514,7 +574,9 @@ def frame_attr(enc, path, xyz, res, dev, Q, scale, want_psnr, chunk=None):
         raise native.ScpError(f"--attr: {path} has no reflectance column (KITTI / Ford .bin frames hold x y z r)")
     x_dev = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], np.float32)).to(dev)
     r_dev = torch.from_numpy(np.ascontiguousarray(refl, np.float32).reshape(-1)).to(dev)
-    data, rep = enc.encode_attr(x_dev, r_dev, Q, scale, chunk=chunk)
+    data, rep = enc.encode_attr(x_dev, r_dev, Q, scale, chunk=chunk, target=target, steps=steps if target is not None else None)
+    if steps is not None and target is None:
+        rep["sweep"] = enc.attr_sweep(x_dev, r_dev, scale, steps)
     rep["bytes"] = data
     if want_psnr:
         qs = shell_qs(enc.data_type, enc.lidar_level, enc.mullevel)
@@ -524,17 +586,19 @@ def frame_attr(enc, path, xyz, res, dev, Q, scale, want_psnr, chunk=None):
     return rep
 
 
-def frame_color(enc, path, xyz, q, res, dev, Q, want_psnr, chunk=None):
+def frame_color(enc, path, xyz, q, res, dev, Q, want_psnr, chunk=None, steps=None, target=None):
     """--color: the colour columns of the object file `path` through FrameEncoder.encode_color, on the octree `enc` has just coded from the
     integers q -> encode_color's report with `bytes` (the colour file) and, with want_psnr, color.color_psnr of the cloud
     decode_ehem.py --color will write (the leaves through the decoder's own de-quantiser, with the decoded colours) against the
-    file's points (MVUB files: in the swapped axes the stream is coded in)."""
+    file's points (MVUB files: in the swapped axes the stream is coded in).  steps / target: as for frame_attr."""
     from . import color, metrics
     rgb = pointCloud.pcread(path, "rgb")[1]
     if rgb is None or len(rgb) != len(xyz):
         raise native.ScpError(f"--color: {path} has no colour columns (an ascii PLY with x y z red green blue per point is expected)")
     c_dev = color.point_colors(torch.from_numpy(np.ascontiguousarray(rgb, np.float32)).to(dev))
-    data, rep = enc.encode_color(q, c_dev, Q, chunk=chunk)
+    data, rep = enc.encode_color(q, c_dev, Q, chunk=chunk, target=target, steps=steps if target is not None else None)
+    if steps is not None and target is None:
+        rep["sweep"] = enc.color_sweep(q, c_dev, steps)
     rep["bytes"] = data
     if want_psnr:
         x = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], np.float32)).to(dev)
@@ -544,6 +608,26 @@ def frame_color(enc, path, xyz, q, res, dev, Q, want_psnr, chunk=None):
         pts = metrics.dequantize(enc.attr_leaves()[0].long(), qd["qs"], qd["offset"], spher=False, cylin=False)
         rep.update(color.color_psnr(x, c_dev, pts, rep["decoded"][0]))
     return rep
+
+
+def sweep_lines(layer, rep, path, want_table):
+    """The lines and the file of --<layer>_sweep / --<layer>_target for a frame whose layer file is `path`: with a target one line (the
+    target, the chosen Q, met, estimated against written bits); with want_table one line (per step Q: estimated bits per point, leaf
+    PSNR) and `<path>.sweep.json`.  The PSNR is over leaf values - what the layer codes against what it returns."""
+    table = rep.get("sweep")
+    if table is None:
+        return
+    if "target" in rep:
+        row = table["rows"][[r["Q"] for r in table["rows"]].index(rep["chosen_Q"])]
+        print(f"{layer} target, chosen Q, met, estimated / written bits :", "%s=%g" % rep["target"], rep["chosen_Q"], rep["met"], row["est_bits"],
+              rep["bits"])
+    if want_table:
+        n = max(table["points"], 1)
+        print(f"{layer} sweep Q:est bpp:leaf PSNR (over leaf values, not the point-wise PSNR of --metrics) :",
+              *["%d:%.4f:%.2f" % (r["Q"], r["est_bits"] / n, r["psnr"]) for r in table["rows"]])
+        extra = {k: rep[k] for k in ("target", "chosen_Q", "met") if k in rep}
+        with open(path + ".sweep.json", "w") as f:
+            json.dump(dict(table, layer=layer, psnr_over="leaf values", bits=rep["bits"], **extra), f, indent=1)
 
 
 class Prefetch:
@@ -597,6 +681,7 @@ def main(argv=None, mullevel=False):
     attr_q, attr_scale = attr_request(args)
     color_q = color_request(args)
     chunk = chunk_request(args)
+    (attr_steps, attr_target), (color_steps, color_target) = sweep_request(args, "attr"), sweep_request(args, "color")
     cls = OctAttention if name == "OctAttention" else EHEM
     if args.random_weights is not None or not args.ckpt_path:
         from .weights import fill_weights
@@ -693,11 +778,13 @@ def main(argv=None, mullevel=False):
                 f.write(arep["bytes"])
             print("attr bits, bits per point" + (", PSNR (refl) :" if "psnr" in arep else "  :"), arep["bits"], arep["bits_per_point"],
                   *([arep["psnr"]] if "psnr" in arep else []))
+            sweep_lines("attr", arep, outfile + ".attr", attr_steps is not None)
         if crep:
             with open(outfile + ".color", "wb") as f:
                 f.write(crep["bytes"])
             print("color bits, bits per point" + (", PSNR (Y), PSNR (RGB) :" if "psnr_y" in crep else "  :"), crep["bits"], crep["bits_per_point"],
                   *([crep["psnr_y"], crep["psnr_rgb"]] if "psnr_y" in crep else []))
+            sweep_lines("color", crep, outfile + ".color", color_steps is not None)
         if drep:
             worse = max((drep["a_to_b"]["total"], drep["b_to_a"]["total"]), key=lambda e: e["mse"])     # the direction D1's mseF takes
             share = [worse[k] / worse["mse"] if worse["mse"] > 0 else 0.0 for k in ("mse_r", "mse_phi", "mse_theta")]
@@ -756,7 +843,7 @@ def main(argv=None, mullevel=False):
             res = enc.encode_ints(q, 0, len(xyz), sequential=args.sequential) if name == "OctAttention" else enc.encode_ints([q], 0, 0.0, len(xyz))
             res["quant"] = [dict(qs=[1.0, 1.0, 1.0], offset=off)]     # the sidecar is the only carrier of the per-axis minimum
             if color_q is not None:
-                crep = frame_color(enc, cur, xyz, q, res, dev, color_q, args.metrics, chunk)
+                crep = frame_color(enc, cur, xyz, q, res, dev, color_q, args.metrics, chunk, color_steps, color_target)
         elif name == "OctAttention":
             res = enc.encode(xyz, sequential=args.sequential)
         else:
@@ -772,7 +859,7 @@ def main(argv=None, mullevel=False):
             if want_depth:
                 lrep = enc.depth_report(x_dev, depth_drop, depth_edges)
             if attr_q is not None:
-                arep = frame_attr(enc, cur, xyz, res, dev, attr_q, attr_scale, args.metrics, chunk)
+                arep = frame_attr(enc, cur, xyz, res, dev, attr_q, attr_scale, args.metrics, chunk, attr_steps, attr_target)
         report(cur, res, t0, dist, drep, rrep, lrep, arep, crep)
     for c0, h0, ts in pending:
         report(c0, enc.finish(h0), ts)

@@ -144,6 +144,37 @@ def encode_shells(leaves, depths, qs, rgb, Q=1, chunk=None, want_overhead=False)
     return data, report
 
 
+def record_bytes(D, U):
+    """The bytes of a shell's record in the header of `<stream>.color`: D, U, the roots (U >= 1), 3 D table indices and the payload length
+    (U >= 2)."""
+    return 5 + (5 if U >= 1 else 0) + (3 * D + 4 if U >= 2 else 0)
+
+
+def sweep_shells(leaves, depths, qs, rgb, steps=None):
+    """One pass per shell over a grid of steps (native.color_sweep; DESIGN.md 6, "Step sweep").  Arguments as encode_shells'; steps:
+    native.sweep_steps.  -> dict(steps, points, leaves, rows) as attr.sweep_shells, with sse / linf / psnr over the three channels
+    (psnr = 10 log10(255^2 3 leaves / sum(sse)), linf the largest error of any channel) and sse_rgb / linf_rgb / psnr_rgb per channel.
+    The PSNR is over LEAF COLOURS - the leaf means the layer codes against what it returns - not the point-wise PSNR of --metrics."""
+    grid = native.sweep_steps(steps)
+    if len(leaves) > 255:
+        raise native.ScpError(f"color.sweep_shells: {len(leaves)} shells, a colour file holds at most 255")
+    frame_bytes, shells = 4 + 4, []
+    for lv, D, q in zip(leaves, depths, qs):
+        U, D = int(lv.shape[0]), int(D)
+        frame_bytes += record_bytes(D, U)
+        if U < 2:
+            shells.append((U, None, None, None))
+            continue
+        mean, ycc, _ = native.color_leaf_values(q, rgb, lv, D)
+        s = native.color_sweep(lv, ycc, mean, D, grid)
+        shells.append((U, s["hist"].cpu().numpy(), s["sse"].cpu().numpy(), s["linf"].cpu().numpy()))
+    return dict(steps=[int(v) for v in grid], points=int(rgb.shape[0]), leaves=sum(s[0] for s in shells),
+                rows=attr.sweep_rows(grid, 3, frame_bytes, shells))
+
+
+choose_step = attr.choose_step
+
+
 def decode_shells(data, leaves, depths, info=None):
     """The bytes of a colour file + the decoded geometry (per shell device int32 / int64 [U,3] leaves in the decoder's order, and the
     depths) -> per shell the device uint8 [U,3] leaf colours.  D and U of every shell must be the geometry's.  info: a dict that

@@ -9,6 +9,7 @@
 //   scp_attr_inverse       lift_inverse; a leaf keeps its value clamped to 0 .. 255.
 //   scp_attr_level_counts  the tree alone: n_0 .. n_D, from which a decoder knows every coefficient's context before it has one.
 //   scp_attr_pairs         lift_pairs: (c_low | c_high << 16) of every coefficient from the chosen table of its context.
+//   scp_attr_sweep         lift_sweep: per step of a grid the histogram of scp_attr_forward and the error of scp_attr_inverse's values.
 //
 // Integer atomics only (leaf sums, histogram); no floating-point arithmetic except the one exact product r * scale of a point value.
 // Unsorted or repeated leaves give unspecified values, but no access leaves the buffers: every level's count is clamped to the level's
@@ -17,11 +18,18 @@
 
 #define AT_ALPHABET 511
 #define AT_KMAX 255
+#define AT_SWEEP_LDS 256        // symbols of a sweep row with LDS counters (|k| <= 128): 16 KB at 16 steps
 
 namespace {
 
 struct attr_store {
-    static __device__ __forceinline__ void leaf(uint8_t *a, int64_t i, const int32_t *x) { a[i] = (uint8_t)(x[0] < 0 ? 0 : (x[0] > 255 ? 255 : x[0])); }
+    static constexpr int OUT = 1;
+    static __device__ __forceinline__ void rule(const int32_t *x, int32_t *y) { y[0] = x[0] < 0 ? 0 : (x[0] > 255 ? 255 : x[0]); }
+    static __device__ __forceinline__ void leaf(uint8_t *a, int64_t i, const int32_t *x) {
+        int32_t y[OUT];
+        rule(x, y);
+        a[i] = (uint8_t)y[0];
+    }
 };
 
 __global__ __launch_bounds__(AT_THREADS) void attr_point_kernel(const int32_t *__restrict__ q, const float *__restrict__ r, int64_t P,
@@ -108,6 +116,15 @@ extern "C" int scp_attr_inverse(const int32_t *leaves, int64_t U, int32_t D, int
                                 int64_t workspace_bytes, void *stream) {
     if (root < 0 || root > 255) return SCP_EINVAL;
     return lift_inverse<1, attr_store>(leaves, U, D, Q, lift_vec<1>{{root}}, k, a, workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t scp_attr_sweep_workspace_bytes(int64_t U, int32_t D, int32_t G) { return lift_sweep_bytes<1, AT_ALPHABET>(U, D, G); }
+
+extern "C" int scp_attr_sweep(const int32_t *leaves, const uint8_t *a, int64_t U, int32_t D, const int32_t *steps, int32_t G, int32_t *hist,
+                              uint64_t *sse, uint32_t *linf, int32_t *root, int64_t *level_counts, void *workspace, int64_t workspace_bytes,
+                              void *stream) {
+    return lift_sweep<1, AT_ALPHABET, AT_KMAX, AT_SWEEP_LDS, attr_store>(leaves, a, a, U, D, steps, G, hist, sse, linf, root, level_counts, workspace,
+                                                                         workspace_bytes, stream);
 }
 
 extern "C" int scp_attr_pairs(const int16_t *k, const uint8_t *ctx, int64_t n, const uint16_t *tables, int32_t D, uint32_t *lohi, void *stream) {

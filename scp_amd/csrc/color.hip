@@ -9,6 +9,8 @@
 //   scp_color_inverse      lift_inverse; a leaf undoes the colour transform and clamps R, G, B to 0 .. 255 - the only clamp of the layer.
 //   scp_color_pairs        lift_pairs: the 3 (U - 1) coefficients in payload order (Y block, Co block, Cg block), table of context
 //                          channel * D + (level - 1).
+//   scp_color_sweep        lift_sweep: per step of a grid the histograms of scp_color_forward and the R, G, B error of scp_color_inverse's
+//                          colours against the leaf means.
 //
 // Integer arithmetic only.  Unsorted or repeated leaves give unspecified values, but no access leaves the buffers, for the reflectance
 // layer's reason: counts are clamped at the scan (attr_common.h).
@@ -16,16 +18,25 @@
 
 #define CL_ALPHABET 1021
 #define CL_KMAX 510
+#define CL_SWEEP_LDS 128        // symbols of a sweep row with LDS counters (|k| <= 64): 24 KB at 16 steps and three planes
 
 namespace {
 
 struct color_store {       // YCoCg-R back to R, G, B
-    static __device__ __forceinline__ void leaf(uint8_t *rgb, int64_t i, const int32_t *x) {
+    static constexpr int OUT = 3;
+    static __device__ __forceinline__ void rule(const int32_t *x, int32_t *y) {
         const int32_t t = x[0] - (x[2] >> 1), G = x[2] + t, B = t - (x[1] >> 1), R = B + x[1];
+        y[0] = R < 0 ? 0 : (R > 255 ? 255 : R);
+        y[1] = G < 0 ? 0 : (G > 255 ? 255 : G);
+        y[2] = B < 0 ? 0 : (B > 255 ? 255 : B);
+    }
+    static __device__ __forceinline__ void leaf(uint8_t *rgb, int64_t i, const int32_t *x) {
+        int32_t y[OUT];
+        rule(x, y);
         uint8_t *o = rgb + 3 * i;
-        o[0] = (uint8_t)(R < 0 ? 0 : (R > 255 ? 255 : R));
-        o[1] = (uint8_t)(G < 0 ? 0 : (G > 255 ? 255 : G));
-        o[2] = (uint8_t)(B < 0 ? 0 : (B > 255 ? 255 : B));
+        o[0] = (uint8_t)y[0];
+        o[1] = (uint8_t)y[1];
+        o[2] = (uint8_t)y[2];
     }
 };
 
@@ -102,6 +113,15 @@ extern "C" int scp_color_inverse(const int32_t *leaves, int64_t U, int32_t D, in
                                  void *workspace, int64_t workspace_bytes, void *stream) {
     if (!root || root[0] < 0 || root[0] > 255 || root[1] < -255 || root[1] > 255 || root[2] < -255 || root[2] > 255) return SCP_EINVAL;
     return lift_inverse<3, color_store>(leaves, U, D, Q, lift_vec<3>{{root[0], root[1], root[2]}}, k, rgb, workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t scp_color_sweep_workspace_bytes(int64_t U, int32_t D, int32_t G) { return lift_sweep_bytes<3, CL_ALPHABET>(U, D, G); }
+
+extern "C" int scp_color_sweep(const int32_t *leaves, const int16_t *ycc, const uint8_t *rgb_mean, int64_t U, int32_t D, const int32_t *steps,
+                               int32_t G, int32_t *hist, uint64_t *sse, uint32_t *linf, int32_t *root, int64_t *level_counts, void *workspace,
+                               int64_t workspace_bytes, void *stream) {
+    return lift_sweep<3, CL_ALPHABET, CL_KMAX, CL_SWEEP_LDS, color_store>(leaves, ycc, rgb_mean, U, D, steps, G, hist, sse, linf, root, level_counts,
+                                                                          workspace, workspace_bytes, stream);
 }
 
 extern "C" int scp_color_pairs(const int16_t *k, const uint8_t *ctx, int64_t n, const uint16_t *tables, int32_t D, uint32_t *lohi, void *stream) {

@@ -812,61 +812,110 @@ class FrameEncoder(_FrontEnd):
             out.append(lv)
         return out
 
-    def encode_attr(self, xyz_dev, refl_dev, Q=1, scale=None, ints=None, chunk=None, want_overhead=False):
-        """The reflectance of the frame just encoded (DESIGN.md 6, "Reflectance"): codes one 8-bit value per leaf of the octree of the last
-        `encode` / `preprocess` call, as `distortion` measures that octree - callable after a synchronous call.  xyz_dev device float32
-        [P,>=3] and refl_dev device float32 [P] are the frame; Q = 1 .. 255 the step (1: lossless on the leaf values); scale: 8-bit units
-        per unit of reflectance (None: 255 for KITTI, 1 for Ford); ints: the host integers of the frame where the encoder was given them;
-        chunk = N: a version-2 file whose payloads the device codes in chunks of N symbols (None: version 1, the host coder), want_overhead:
-        attr.encode_shells' `chunk_overhead_bits`.
-        -> (the bytes of `<stream>.attr`, report): attr.encode_shells' report plus n_points, bits_per_point, bits_per_leaf."""
-        from . import attr
+    def _attr_frame(self, who, xyz_dev, refl_dev, ints):
+        """The checks of the reflectance entries and what they code on: (leaves, depths, qs, refl, points)."""
         if self.ring_lod is not None:
-            raise native.ScpError("encode_attr with ring_lod: the leaves of such a tree are snapped cells of mixed sizes, and an attribute "
+            raise native.ScpError(f"{who} with ring_lod: the leaves of such a tree are snapped cells of mixed sizes, and an attribute "
                                   "layer for them is not part of this library")
         if not self.geom.info:
-            raise native.ScpError("encode_attr: no frame to code - call it after a synchronous encode / preprocess")
+            raise native.ScpError(f"{who}: no frame to code - call it after a synchronous encode / preprocess")
         xyz_dev = xyz_dev[:, :3].to(torch.float32).contiguous()
         refl_dev = refl_dev.reshape(-1).to(torch.float32).contiguous()
         if refl_dev.shape[0] != xyz_dev.shape[0]:
-            raise native.ScpError(f"encode_attr: {refl_dev.shape[0]} reflectances for {xyz_dev.shape[0]} points")
+            raise native.ScpError(f"{who}: {refl_dev.shape[0]} reflectances for {xyz_dev.shape[0]} points")
         infos = self._infos
         try:
             qs = self.quantize(xyz_dev, ints)[0]         # the integers the tree was built from (the same quantiser, the same input)
         finally:
             self._infos = infos
-        leaves = self.attr_leaves()
-        data, rep = attr.encode_shells(leaves, [int(i.depth) for i in self.geom.info], [q.contiguous() for q in qs], refl_dev, Q,
-                                       attr.default_scale(self.data_type) if scale is None else scale, chunk=chunk, want_overhead=want_overhead)
-        n_leaves = sum(int(lv.shape[0]) for lv in leaves)
-        rep.update(n_points=int(xyz_dev.shape[0]), bits_per_point=rep["bits"] / max(int(xyz_dev.shape[0]), 1),
-                   bits_per_leaf=rep["bits"] / max(n_leaves, 1))
+        return self.attr_leaves(), [int(i.depth) for i in self.geom.info], [q.contiguous() for q in qs], refl_dev, int(xyz_dev.shape[0])
+
+    @staticmethod
+    def _with_target(who, sweep, Q, target, steps, code):
+        """target = (kind, value): sweep() -> the table, the step that meets the target, code(Q) at that step, and the report with
+        `target`, `chosen_Q`, `met` and the table as `sweep`.  Without a target: code(Q), nothing else."""
+        from . import attr
+        if target is None:
+            if steps is not None:
+                raise native.ScpError(f"{who}: steps is the grid of a target's sweep - give target as well")
+            return code(Q)
+        kind, value = attr.check_target(target, f"{who}: target")
+        if int(Q) != 1:
+            raise native.ScpError(f"{who}: Q = {Q} together with a target - the target chooses the step, leave Q at 1")
+        table = sweep()
+        pick = attr.choose_step(table, kind, value)
+        data, rep = code(pick["Q"])
+        rep.update(target=(kind, value), chosen_Q=pick["Q"], met=pick["met"], sweep=table)
         return data, rep
 
+    def attr_sweep(self, xyz_dev, refl_dev, scale=None, steps=None, ints=None):
+        """What every step of a grid costs and loses on the reflectance of the frame just encoded ("Step sweep"), in one pass
+        per shell: attr.sweep_shells' table.  Preconditions and arguments as encode_attr's; steps: native.sweep_steps (None: the default
+        grid of 16).  The PSNR of the table is over leaf values, not the point-wise PSNR of `--metrics`."""
+        from . import attr
+        leaves, depths, qs, refl, _ = self._attr_frame("attr_sweep", xyz_dev, refl_dev, ints)
+        return attr.sweep_shells(leaves, depths, qs, refl, attr.default_scale(self.data_type) if scale is None else scale, steps)
+
+    def encode_attr(self, xyz_dev, refl_dev, Q=1, scale=None, ints=None, chunk=None, want_overhead=False, target=None, steps=None):
+        """The reflectance of the frame just encoded (DESIGN.md 6, "Reflectance"): codes one 8-bit value per leaf of the octree of the last
+        `encode` / `preprocess` call, as `distortion` measures that octree - callable after a synchronous call.  xyz_dev device float32
+        [P,>=3] and refl_dev device float32 [P] are the frame; Q = 1 .. 255 the step (1: lossless on the leaf values); scale: 8-bit units
+        per unit of reflectance (None: 255 for KITTI, 1 for Ford); ints: the host integers of the frame where the encoder was given them;
+        chunk = N: a version-2 file whose payloads the device codes in chunks of N symbols (None: version 1, the host coder), want_overhead:
+        attr.encode_shells' `chunk_overhead_bits`.  target = (kind, value), kind "psnr" / "bpp" / "linf": the step comes from a sweep over
+        `steps` (attr_sweep, attr.choose_step) and Q stays 1; the report gains target, chosen_Q, met and the table as `sweep`.
+        -> (the bytes of `<stream>.attr`, report): attr.encode_shells' report plus n_points, bits_per_point, bits_per_leaf."""
+        from . import attr
+        leaves, depths, qs, refl_dev, n_points = self._attr_frame("encode_attr", xyz_dev, refl_dev, ints)
+        scale = attr.default_scale(self.data_type) if scale is None else scale
+
+        def code(step):
+            data, rep = attr.encode_shells(leaves, depths, qs, refl_dev, step, scale, chunk=chunk, want_overhead=want_overhead)
+            n_leaves = sum(int(lv.shape[0]) for lv in leaves)
+            rep.update(n_points=n_points, bits_per_point=rep["bits"] / max(n_points, 1), bits_per_leaf=rep["bits"] / max(n_leaves, 1))
+            return data, rep
+
+        return self._with_target("encode_attr", lambda: attr.sweep_shells(leaves, depths, qs, refl_dev, scale, steps), Q, target, steps, code)
+
     # ------------------------------------------------------------------------------------------ colour
-    def encode_color(self, q_dev, rgb_dev, Q=1, chunk=None, want_overhead=False):
+    def _color_frame(self, who, q_dev, rgb_dev):
+        """The checks of the colour entries and what they code on: (leaves, depths, qs, rgb)."""
+        if self.ring_lod is not None:
+            raise native.ScpError(f"{who} with ring_lod: the leaves of such a tree are snapped cells of mixed sizes, and a colour "
+                                  "layer for them is not part of this library")
+        if not self.geom.info:
+            raise native.ScpError(f"{who}: no frame to code - call it after a synchronous encode_ints")
+        if len(self.geom.info) != 1:
+            raise native.ScpError(f"{who}: the colour layer codes the one tree of an object cloud, this frame has {len(self.geom.info)} shells")
+        if q_dev.dim() != 2 or q_dev.shape[1] != 3 or rgb_dev.shape != q_dev.shape or rgb_dev.dtype != torch.uint8:
+            raise native.ScpError(f"{who}: q int32 [P,3] and rgb uint8 [P,3] expected, got {tuple(q_dev.shape)} and {tuple(rgb_dev.shape)} "
+                                  f"{rgb_dev.dtype}")
+        return self.attr_leaves(), [int(i.depth) for i in self.geom.info], [q_dev.to(torch.int32).contiguous()], rgb_dev.contiguous()
+
+    def color_sweep(self, q_dev, rgb_dev, steps=None):
+        """What every step of a grid costs and loses on the colour of the object cloud just encoded ("Step sweep"), in one
+        pass: color.sweep_shells' table.  Preconditions and arguments as encode_color's; steps: native.sweep_steps.  The PSNR of the
+        table is over leaf colours, not the point-wise PSNR of `--metrics`."""
+        from . import color
+        return color.sweep_shells(*self._color_frame("color_sweep", q_dev, rgb_dev), steps)
+
+    def encode_color(self, q_dev, rgb_dev, Q=1, chunk=None, want_overhead=False, target=None, steps=None):
         """The colour of the object cloud just encoded ("Colour"): codes one RGB triple per leaf of the octree of the last
         synchronous `encode_ints` call.  q_dev device int32 [P,3]: the integers that tree was built from; rgb_dev device uint8 [P,3]: the
         points' 8-bit colours (color.point_colors); Q = 1 .. 255 the step of the three planes (1: lossless on the leaf means); chunk = N /
-        want_overhead: a version-2 (chunked) file and its report fields, as for encode_attr.
+        want_overhead: a version-2 (chunked) file and its report fields, as for encode_attr; target / steps: the step from a sweep
+        (color_sweep, color.choose_step), as for encode_attr.
         -> (the bytes of `<stream>.color`, report): color.encode_shells' report plus n_points, bits_per_point, bits_per_leaf."""
         from . import color
-        if self.ring_lod is not None:
-            raise native.ScpError("encode_color with ring_lod: the leaves of such a tree are snapped cells of mixed sizes, and a colour "
-                                  "layer for them is not part of this library")
-        if not self.geom.info:
-            raise native.ScpError("encode_color: no frame to code - call it after a synchronous encode_ints")
-        if len(self.geom.info) != 1:
-            raise native.ScpError(f"encode_color: the colour layer codes the one tree of an object cloud, this frame has {len(self.geom.info)} shells")
-        if q_dev.dim() != 2 or q_dev.shape[1] != 3 or rgb_dev.shape != q_dev.shape or rgb_dev.dtype != torch.uint8:
-            raise native.ScpError(f"encode_color: q int32 [P,3] and rgb uint8 [P,3] expected, got {tuple(q_dev.shape)} and {tuple(rgb_dev.shape)} "
-                                  f"{rgb_dev.dtype}")
-        leaves = self.attr_leaves()
-        data, rep = color.encode_shells(leaves, [int(i.depth) for i in self.geom.info], [q_dev.to(torch.int32).contiguous()], rgb_dev.contiguous(), Q,
-                                        chunk=chunk, want_overhead=want_overhead)
-        n_leaves = sum(int(lv.shape[0]) for lv in leaves)
-        rep.update(n_points=int(q_dev.shape[0]), bits_per_point=rep["bits"] / max(int(q_dev.shape[0]), 1), bits_per_leaf=rep["bits"] / max(n_leaves, 1))
-        return data, rep
+        leaves, depths, qs, rgb = self._color_frame("encode_color", q_dev, rgb_dev)
+
+        def code(step):
+            data, rep = color.encode_shells(leaves, depths, qs, rgb, step, chunk=chunk, want_overhead=want_overhead)
+            n_leaves = sum(int(lv.shape[0]) for lv in leaves)
+            rep.update(n_points=int(q_dev.shape[0]), bits_per_point=rep["bits"] / max(int(q_dev.shape[0]), 1), bits_per_leaf=rep["bits"] / max(n_leaves, 1))
+            return data, rep
+
+        return self._with_target("encode_color", lambda: color.sweep_shells(leaves, depths, qs, rgb, steps), Q, target, steps, code)
 
     def preprocess(self, xyz_dev, ints=None):
         # (ring_lod snaps the integers between the quantiser and the build: the route of the integer inputs)

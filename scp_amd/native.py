@@ -188,6 +188,10 @@ def lib():
         "scp_color_forward": (C.c_int, [_vp, _vp, i64, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp]),
         "scp_color_inverse": (C.c_int, [_vp, i64, i32, i32, _vp, _vp, _vp, _vp, i64, _vp]),
         "scp_color_pairs": (C.c_int, [_vp, _vp, i64, _vp, i32, _vp, _vp]),
+        "scp_attr_sweep_workspace_bytes": (C.c_int64, [i64, i32, i32]),
+        "scp_color_sweep_workspace_bytes": (C.c_int64, [i64, i32, i32]),
+        "scp_attr_sweep": (C.c_int, [_vp, _vp, i64, i32, _vp, i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp]),
+        "scp_color_sweep": (C.c_int, [_vp, _vp, _vp, i64, i32, _vp, i32, _vp, _vp, _vp, _vp, _vp, _vp, i64, _vp]),
         "scp_ac_chunks_workspace_bytes": (C.c_int64, [i64, i64]),
         "scp_ac_chunks_encode_lohi": (C.c_int, [_vp, i64, i64, _vp, _vp, i64, _vp, _vp, i64, _vp]),
         "scp_ac_chunks_decode_ctx": (C.c_int, [_vp, _vp, i64, i64, _vp, i32, i32, _vp, i32, _vp, _vp, _vp]),
@@ -2296,6 +2300,66 @@ def color_inverse(leaves, depth, Q, root, k):
     _check(lib().scp_color_inverse(leaves.data_ptr(), U, depth, int(Q), C.cast(r, _vp), _dev(k, torch.int16), rgb.data_ptr(), ws.data_ptr(), nb, _stream()),
            "scp_color_inverse")
     return rgb
+
+
+# ------------------------------------------------------------------------------------------------- step sweep (csrc/lift.h)
+SWEEP_MAX_STEPS = 16                                                       # include/scp.h: SCP_SWEEP_MAX_STEPS
+SWEEP_STEPS = (1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128, 192, 255)
+
+
+def sweep_steps(steps=None):
+    """The grid of steps of a sweep as numpy int32 [G].  None: SWEEP_STEPS.  A grid holds 1 .. SWEEP_MAX_STEPS integers in 1 .. 255,
+    strictly ascending."""
+    raw = list(SWEEP_STEPS if steps is None else steps)
+    if not 1 <= len(raw) <= SWEEP_MAX_STEPS:
+        raise ScpError(f"sweep steps: {len(raw)} steps, 1 .. {SWEEP_MAX_STEPS} expected")
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in raw):
+        raise ScpError(f"sweep steps: integers expected, got {raw}")
+    g = np.array([int(v) for v in raw], np.int64)
+    if (g < 1).any() or (g > 255).any():
+        raise ScpError(f"sweep steps: every step is 1 .. 255, got {g.tolist()}")
+    if (np.diff(g) <= 0).any():
+        raise ScpError(f"sweep steps: strictly ascending steps expected, got {g.tolist()}")
+    return np.ascontiguousarray(g.astype(np.int32))
+
+
+def _sweep(fn, channels, outs, alphabet, leaves, depth, steps, *values):
+    U, dev, depth = leaves.shape[0], leaves.device, int(depth)
+    if not 1 <= depth <= MAX_DEPTH:
+        raise ScpError(f"{fn}: depth {depth} outside 1 .. {MAX_DEPTH}")
+    g = sweep_steps(steps)
+    G = int(g.shape[0])
+    hist = torch.empty((G, channels * depth, alphabet), dtype=torch.int32, device=dev)
+    sse = torch.empty((G, outs), dtype=torch.int64, device=dev)             # uint64 on the device; a sum stays far below 2^63
+    linf = torch.empty((G, outs), dtype=torch.int32, device=dev)
+    root = torch.empty(channels, dtype=torch.int32, device=dev)
+    counts = torch.empty(depth + 1, dtype=torch.int64, device=dev)
+    ws, nb = _attr_workspace(f"scp_{fn}_workspace_bytes", dev, U, depth, G)
+    _check(getattr(lib(), f"scp_{fn}")(leaves.data_ptr(), *values, U, depth, g.ctypes.data, G, hist.data_ptr(), sse.data_ptr(), linf.data_ptr(),
+                                       root.data_ptr(), counts.data_ptr(), ws.data_ptr(), nb, _stream()), f"scp_{fn}")
+    return dict(steps=g, hist=hist, sse=sse, linf=linf, root=root, level_counts=counts)
+
+
+def attr_sweep(leaves, a, depth, steps=None):
+    """scp_attr_sweep: leaves device int32 [U,3], a device uint8 [U], steps (sweep_steps) -> dict: steps numpy int32 [G] and the device
+    tensors hist int32 [G, depth, 511] (row g: attr_forward's hist at Q = steps[g]), sse int64 [G, 1] and linf int32 [G, 1] (the squared
+    and the largest error of attr_inverse's leaf values at that step against a), root int32 [1], level_counts int64 [depth + 1]."""
+    leaves = _attr_leaves(leaves, "attr_sweep")
+    if a.shape != (leaves.shape[0],):
+        raise ScpError(f"attr_sweep: one value per leaf expected, got {tuple(a.shape)} for {leaves.shape[0]} leaves")
+    return _sweep("attr_sweep", 1, 1, ATTR_ALPHABET, leaves, depth, steps, _dev(a, torch.uint8))
+
+
+def color_sweep(leaves, ycc, rgb_mean, depth, steps=None):
+    """scp_color_sweep: leaves device int32 [U,3], ycc int16 [3,U] and rgb_mean uint8 [U,3] as color_leaf_values returns them, steps
+    (sweep_steps) -> dict: steps numpy int32 [G] and the device tensors hist int32 [G, 3 depth, 1021] (row g: color_forward's hist at
+    Q = steps[g]), sse int64 [G, 3] and linf int32 [G, 3] (R, G, B: color_inverse's leaf colours at that step against rgb_mean), root
+    int32 [3], level_counts int64 [depth + 1]."""
+    leaves = _attr_leaves(leaves, "color_sweep")
+    U = leaves.shape[0]
+    if ycc.shape != (3, U) or rgb_mean.shape != (U, 3):
+        raise ScpError(f"color_sweep: ycc [3,{U}] and rgb_mean [{U},3] expected, got {tuple(ycc.shape)} and {tuple(rgb_mean.shape)}")
+    return _sweep("color_sweep", 3, 3, COLOR_ALPHABET, leaves, depth, steps, _dev(ycc, torch.int16), _dev(rgb_mean, torch.uint8))
 
 
 # ------------------------------------------------------------------------------------------------- range coder (host)
