@@ -961,7 +961,17 @@ SCP_API int scp_mlp3_rows(const float *x, int64_t ldx, int64_t n_src, const int6
  *                                     writing the key / value heads as planes straight from the accumulators (M % 128 == 0, Tp >= M)
  *   scp_swin_attention_packed_planes: scp_swin_attention_packed(_split) on (q fp32, planes); out fp32 [rows][256] or ohi / olo planes
  * All three give the bits of the fp32 hand-over (scp_swin_ln_linear + scp_swin_attention_packed).  * valid (device fp32 [rows], may be NULL): 1 for real rows, 0 for window padding - a query tile (128 aligned rows) whose first row is
- * padding is skipped and its output rows are not written. */
+ * padding is skipped and its output rows are not written.
+ *
+ * The attention OUTPUT travels to scp_swin_post_attn the same way: with ldo (scp_swin_attention_packed_planes) / ldo_in (scp_swin_post_attn)
+ * = SCP_LDO_FRAG the o planes are the linear image of the post-attention kernels' B fragments instead of rows:
+ *   o   [128-row tile][32 chunks of 8 channels][128 rows][8 bf16] per plane (hi, lo): channel c of row r at element
+ *       (((r >> 7) * 32 + (c >> 3)) * 128 + (r & 127)) * 8 + (c & 7); 512 bytes per row as before, whole tiles: ceil(M / 128) * 128 * 256
+ *       elements per plane, 16-byte aligned.
+ * A lane of the consumer (row = lane & 31, half = lane >> 5) loads the fragment of k-step s - chunk 2 s + half - with one 16-byte load, a
+ * wave's load reads 2 x 512 contiguous bytes, and every store of the attention kernel writes whole lines.  Same values as the row-major
+ * planes [M][ldo], which stay available (a stride >= 256) for callers that feed other consumers. */
+#define SCP_LDO_FRAG 0
 SCP_API int scp_swin_kv_planes(const float *k, const float *v, int64_t ldkv, int64_t rows, void *khi, void *klo, void *vthi, void *vtlo, void *stream);
 SCP_API int scp_swin_ln_qkv(const float *x, int64_t ldx, const float *valid, const void *Whi, const void *Wlo, const float *bias, const float *wbeta,
                             float eps, float *q, int64_t ldq, void *planes, int64_t Tp, int32_t M, int32_t N, void *stream);

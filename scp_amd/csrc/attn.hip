@@ -335,6 +335,48 @@ __device__ __forceinline__ void attn_store_o(const f32x16 &o0, const f32x16 &o1,
     }
 }
 
+// The o planes in the FRAGMENT ORDER of the post-attention kernels (scp.h: SCP_LDO_FRAG; rowchain.hip reads a B fragment with one 16-byte load):
+// per 128-row tile and plane [32 chunks of 8 channels][128 rows][8 bf16].  A lane holds head dims 8 g + 4 h .. + 3 of its query in accumulator
+// registers 4 g .. 4 g + 3; the half-lanes of a query trade the split values of g odd (h = 0) for those of g even (h = 1) - one
+// v_permlane32_swap per packed pair - and lane h then owns the whole chunks 2 gp + h: every store instruction writes 2 x 512 contiguous bytes
+// (chunks c and c + 1 of the wave's 32 rows), whole lines, where the row-major form assembles every line from eight instructions.  The values
+// are those of store_split4 (rounded product first, then the split), so the planes hold the same bits in another place.
+// ohi / olo: the lane's row of chunk 8 head + h of its tile; the chunks of a tile lie 1024 elements apart.
+__device__ __forceinline__ void attn_store_o_frag(const f32x16 &o0, const f32x16 &o1, float inv, __bf16 *ohi, __bf16 *olo) {
+    typedef unsigned attn_u32x4 __attribute__((ext_vector_type(4)));
+    typedef unsigned attn_u32x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int half = 0; half < 2; ++half)
+#pragma unroll
+        for (int gp = 0; gp < 2; ++gp) {
+            attn_u32x2 ph[2], pl[2];                            // [g & 1]: the lane's four head dims of g = 2 gp, 2 gp + 1 as packed bf16
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                float f[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) f[u] = (half ? o1[8 * gp + 4 * e + u] : o0[8 * gp + 4 * e + u]) * inv;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) asm volatile("" : "+v"(f[u]));      // (see store_split4)
+                bf16x4s vh, vl;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const __bf16 hh = (__bf16)f[u];
+                    vh[u] = hh;
+                    vl[u] = (__bf16)(f[u] - (float)hh);
+                }
+                ph[e] = __builtin_bit_cast(attn_u32x2, vh);
+                pl[e] = __builtin_bit_cast(attn_u32x2, vl);
+            }
+            // swap(a, b): first result = a of the lower half-lane, second = b of the upper one - for h = 0 (own even g, partner's even g), for
+            // h = 1 (partner's odd g, own odd g): in both cases head dims 0 - 3 and 4 - 7 of chunk 2 gp + h
+            const auto h0 = __builtin_amdgcn_permlane32_swap(ph[0][0], ph[1][0], false, false), h1 = __builtin_amdgcn_permlane32_swap(ph[0][1], ph[1][1], false, false);
+            const auto l0 = __builtin_amdgcn_permlane32_swap(pl[0][0], pl[1][0], false, false), l1 = __builtin_amdgcn_permlane32_swap(pl[0][1], pl[1][1], false, false);
+            const int64_t c = (int64_t)(4 * half + 2 * gp) * 1024;
+            *(attn_u32x4 *)(ohi + c) = (attn_u32x4){h0[0], h1[0], h0[1], h1[1]};
+            *(attn_u32x4 *)(olo + c) = (attn_u32x4){l0[0], l1[0], l0[1], l1[1]};
+        }
+}
+
 template <bool FASTFIRST>
 __global__ __launch_bounds__(256, 2) void swin_attn_bf16x3_kernel(const float *__restrict__ q, const float *__restrict__ k,
                                                                  const float *__restrict__ v, const float *__restrict__ table,
@@ -562,6 +604,12 @@ __global__ __launch_bounds__(256, 3) void swin_attn_planes_kernel(const float *_
         if (__syncthreads_or(!attn_fast_ok(l_run, o0, o1, h))) sweep(AttnStd{});      // (the barrier also frees the stages for the second sweep)
     } else sweep(AttnStd{});
     const float inv = 1.0f / l_run;
+    if (ohi && ldo == 0) {      // fragment order: the cyclic shift moves whole 128-row tiles, so the workgroup's queries are ONE tile of the planes
+        const size_t row = seq_row + (size_t)qtok;
+        const size_t e = (((row >> 7) * 32 + head * 8 + h) * 128 + (row & 127)) * 8;
+        attn_store_o_frag(o0, o1, inv, ohi + e, olo + e);
+        return;
+    }
     attn_store_o(o0, o1, inv, h, out ? out + base + (size_t)qtok * (NH * HD) : nullptr,
                  ohi ? ohi + (seq_row + (size_t)qtok) * (size_t)ldo + head * HD : nullptr, ohi ? olo + (seq_row + (size_t)qtok) * (size_t)ldo + head * HD : nullptr);
 }
@@ -613,13 +661,15 @@ static std::atomic<int> g_attn_variant{1};
 extern "C" SCP_API int scp_set_attention_variant(int32_t v) { g_attn_variant.store(v ? 1 : 0, std::memory_order_relaxed); return SCP_OK; }
 extern "C" SCP_API int scp_get_attention_variant(void) { return g_attn_variant.load(std::memory_order_relaxed); }
 
-// packed window attention on those planes (q fp32 [rows][ldq]); out fp32 [rows][256] or (ohi, olo) planes [rows][ldo]
+// packed window attention on those planes (q fp32 [rows][ldq]); out fp32 [rows][256] or (ohi, olo) planes [rows][ldo]; ldo = SCP_LDO_FRAG: the
+// planes in the fragment order of scp_swin_post_attn (16-byte aligned, total_windows * 512 * 256 elements each)
 extern "C" SCP_API int scp_swin_attention_packed_planes(const float *q, const void *khi, const void *klo, const void *vthi, const void *vtlo,
                                                         const float *bias_table, const int32_t *wtab, int32_t total_windows, int32_t shift, int32_t ldq,
                                                         float *out, void *ohi, void *olo, int64_t ldo, const float *valid, void *stream) {
     if (!q || !khi || !klo || !vthi || !vtlo || !bias_table || !wtab || (!out && !ohi) || total_windows <= 0 || (shift != 0 && shift != WIN / 2) ||
         ldq < NH * HD || (ldq & 3) || (((uintptr_t)q | (uintptr_t)out | (uintptr_t)khi | (uintptr_t)klo | (uintptr_t)vthi | (uintptr_t)vtlo) & 15) ||
-        (ohi && (!olo || ldo < NH * HD || (ldo & 3) || (((uintptr_t)ohi | (uintptr_t)olo) & 7))))
+        (ohi && ldo != SCP_LDO_FRAG && (!olo || ldo < NH * HD || (ldo & 3) || (((uintptr_t)ohi | (uintptr_t)olo) & 7))) ||
+        (ohi && ldo == SCP_LDO_FRAG && (!olo || (((uintptr_t)ohi | (uintptr_t)olo) & 15))))
         return SCP_EINVAL;
     SCP_PROF(SCP_PROF_ATTENTION, stream, (double)total_windows * WIN * 2.0 * 2.0 * WIN * NH * HD);
 #define ATTN_GO(V) hipLaunchKernelGGL(swin_attn_planes_kernel<V>, dim3(total_windows * NH * (WIN / QT)), dim3(256), PNS * PST, (hipStream_t)stream, q, (const __bf16 *)khi, \

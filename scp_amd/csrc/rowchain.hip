@@ -531,7 +531,7 @@ __global__ __launch_bounds__(256, 1) void rc_ln_linear_kernel(const RcLnLinArgs 
 // The next tile's attention rows are requested into the fragment registers when the last P1 is done (body 30), its residual rows at
 // the start of the tile; they are older than the LDS-DMA pieces requested after them, so the step barriers (vmcnt(0)) cover them.
 struct RcPostArgs {
-    const __bf16 *Ohi, *Olo; int64_t ldo_in;    // attention output planes [M][ldo_in] (256 columns)
+    const __bf16 *Ohi, *Olo; int64_t ldo_in;    // attention output planes [M][ldo_in] (256 columns); OFRAG kernels: in fragment order (scp.h: SCP_LDO_FRAG)
     const float *x; int64_t ldx;                // residual stream in, fp32 [M][ldx]
     const void *W;                              // ONE buffer: tiled planes proj hi | fc1 hi | fc2 hi | proj lo | fc1 lo | fc2 lo (RC_W_*):
                                                 //   proj [256][256]; fc1 = s (W1 diag(gamma))[:, perm16] [1024][256]; fc2 = W2[:, perm16] / s [256][1024]
@@ -731,6 +731,24 @@ __device__ __forceinline__ void rc_body_step(const RcLane &L, char *smem, int ha
     else RC_DS_READ4_WAIT(A[0][1], fn.r0, 16384, A[0][3], fn.r0, RC_SLOT + 16384, A[0][0], fn.r0, 0, A[0][2], fn.r0, RC_SLOT);
 }
 
+// The attention rows of the tile that holds row r as B fragments, read from FRAGMENT-ORDERED planes (scp.h: SCP_LDO_FRAG): k-step s of lane
+// (row, h) is chunk 2 s + h = ONE 16-byte load, a wave's instruction reads 2 x 512 contiguous bytes - nothing to transpose.
+// Buffer loads: one resource per plane over the tile's 64 KiB (the tile is uniform over the wave), the lane's row and half in ONE offset
+// register, the k-step (4 KiB apart - beyond the immediate offset of a global load, which would cost a 64-bit address per fragment: 64
+// registers, spilled) in the scalar offset.  r: the lane's row (< M; rows behind M repeat row M - 1, which lies in the same tile).
+__device__ __forceinline__ void rc_load_o_frag(const __bf16 *Ohi, const __bf16 *Olo, int tile, int r, int h, rbf16x8 (&Bh)[16], rbf16x8 (&Bl)[16]) {
+    const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc((void *)(Ohi + (int64_t)tile * (RC_ROWS * 256)), 0, RC_ROWS * 512, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void *)(Olo + (int64_t)tile * (RC_ROWS * 256)), 0, RC_ROWS * 512, 0x00020000);
+    const int v = (r & (RC_ROWS - 1)) * 16 + h * 2048;
+    // (one plane after the other: with the two planes' loads alternating the register allocator spills 64 accumulator registers per tile
+    // around the first MLP step - 5 k cycles per tile, more than the transposition cost)
+#pragma unroll
+    for (int s = 0; s < 16; ++s) Bh[s] = __builtin_bit_cast(rbf16x8, __builtin_amdgcn_raw_buffer_load_b128(rh, v, 4096 * s, 0));
+#pragma unroll
+    for (int s = 0; s < 16; ++s) Bl[s] = __builtin_bit_cast(rbf16x8, __builtin_amdgcn_raw_buffer_load_b128(rl, v, 4096 * s, 0));
+}
+
+template <bool OFRAG>      // the attention planes in fragment order (the product's hand-over) / as rows [M][ldo_in]
 __global__ __launch_bounds__(256, 1) void rc_post_attn_kernel(const RcPostArgs a) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     const RcLane L = rc_lane();
@@ -775,7 +793,13 @@ __global__ __launch_bounds__(256, 1) void rc_post_attn_kernel(const RcPostArgs a
     // The attention rows of a tile are fetched COALESCED like the residual rows (see phase 0): raw chunk [4 p + it] = row 8 it + (lane >> 3),
     // 16-byte chunk lane & 7 of the row's 128-byte line p (k-steps 4 p .. 4 p + 3), and turned into B fragments (lane = row, k = 16 s + 8 h
     // + i: chunk 2 (s & 3) + h of line s >> 2) through the bounce buffer once the tile before is stored: eight passes of 4 writes + 4 reads.
+    // OFRAG: the planes arrive in that fragment order (rc_load_o_frag) - the same 32 loads, and transpose_o is empty.
     auto load_o = [&](int t) {
+        if (OFRAG) {
+            const int r = t * RC_ROWS + 32 * L.w + L.col;
+            rc_load_o_frag(a.Ohi, a.Olo, t, r < a.M ? r : a.M - 1, L.h, Bh, Bl);
+            return;
+        }
         const int r0 = t * RC_ROWS + 32 * L.w + (L.lane >> 3);
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
@@ -786,6 +810,11 @@ __global__ __launch_bounds__(256, 1) void rc_post_attn_kernel(const RcPostArgs a
         }
     };
     auto transpose_o = [&]() {
+        if (OFRAG) {      // nothing to do; the fragments (complete since body 30's barrier) are pinned where the row-major form defines them
+#pragma unroll
+            for (int s = 0; s < 16; ++s) asm volatile("" : "+v"(Bh[s]), "+v"(Bl[s]));
+            return;
+        }
 #pragma unroll
         for (int plane = 0; plane < 2; ++plane)
 #pragma unroll
@@ -1030,6 +1059,7 @@ __global__ __launch_bounds__(256, 1) void rc_post_attn_kernel(const RcPostArgs a
 #define RCW_D2 2
 #endif
 #define RCW_H_BYTES (32 * 4096)                     // H(c): [32 chunks][64 lanes][4 x 16 B: hi t = 0, 1, lo t = 0, 1]
+template <bool OFRAG>      // as rc_post_attn_kernel
 __global__ __launch_bounds__(256, 1) void rc_post_attn_wide_kernel(const RcPostArgs a) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     const RcLane L = rc_lane();
@@ -1056,7 +1086,10 @@ __global__ __launch_bounds__(256, 1) void rc_post_attn_wide_kernel(const RcPostA
         if (m0 >= a.M) continue;                                                           // (uniform over the workgroup)
         // ---- the tile's attention rows as B fragments (every wave all 32 rows): coalesced fetch + transposition as in the chain kernel ----
         rbf16x8 Bh[16], Bl[16];
-        {
+        if (OFRAG) {                                                                       // fragment-ordered planes: the fragments as they lie
+            const int r = m0 + L.col;
+            rc_load_o_frag(a.Ohi, a.Olo, t128, r < a.M ? r : a.M - 1, L.h, Bh, Bl);
+        } else {
             const int r0 = m0 + (L.lane >> 3);
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
@@ -1800,7 +1833,7 @@ extern "C" SCP_API int scp_swin_ln_qkv(const float *x, int64_t ldx, const float 
 }
 
 // x2 = x1 + fc2(GELU(fc1(LayerNorm(x1)))) with x1 = x + proj(o): the whole Swin block behind the attention (swin_transformer.py:503-571,
-// 662-706) for M rows.  o: attention output as bf16 hi/lo planes [M][ldo_in]; x: fp32 [M][ldx]; out: fp32 [M][ldc] (may be x).
+// 662-706) for M rows.  o: attention output as bf16 hi/lo planes [M][ldo_in], or in fragment order (ldo_in = SCP_LDO_FRAG, scp.h); x: fp32 [M][ldx]; out: fp32 [M][ldc] (may be x).
 // W: ONE device buffer of scp_swin_post_attn_weight_bytes() bytes holding the tiled planes (scp_split_weight_bf16 + scp_tile_weight_bf16)
 // proj hi | fc1 hi | fc2 hi | proj lo | fc1 lo | fc2 lo with proj [256][256]; fc1 = (W1 diag(gamma))[:, rc_perm16] [1024][256]; fc2 =
 // W2[:, rc_perm16] [256][1024]; rc_perm16: inside every group of 16 columns, columns 4 - 7 and 8 - 11 change places.  b1 = the fc1 bias
@@ -1808,14 +1841,16 @@ extern "C" SCP_API int scp_swin_ln_qkv(const float *x, int64_t ldx, const float 
 extern "C" SCP_API int scp_swin_post_attn(const void *Ohi, const void *Olo, int64_t ldo_in, const float *x, int64_t ldx, const void *W, const float *bp,
                                           const float *b1, const float *b2, float eps, float *out, int64_t ldc, int32_t M, const int32_t *tile_list,
                                           int32_t n_tiles, void *stream) {
-    if (!Ohi || !Olo || !x || !W || !bp || !b1 || !b2 || !out || M <= 0 || (tile_list && (n_tiles <= 0 || n_tiles > (M + RC_ROWS - 1) / RC_ROWS)) || ldo_in < 256 || (ldo_in & 7) || ldx < 256 || (ldx & 3) || ldc < 256 ||
+    if (!Ohi || !Olo || !x || !W || !bp || !b1 || !b2 || !out || M <= 0 || (tile_list && (n_tiles <= 0 || n_tiles > (M + RC_ROWS - 1) / RC_ROWS)) || (ldo_in != SCP_LDO_FRAG && (ldo_in < 256 || (ldo_in & 7))) || ldx < 256 || (ldx & 3) || ldc < 256 ||
         (ldc & 3) || (((uintptr_t)Ohi | (uintptr_t)Olo | (uintptr_t)x | (uintptr_t)out | (uintptr_t)W) & 15) ||
         (int64_t)RC_ROWS * ldc * 4 > 0x7fffffffLL)
         return SCP_EINVAL;
     static bool configured = false;
     if (!configured) {
-        HIP_TRY(hipFuncSetAttribute((const void *)rc_post_attn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RC_LDS));
-        HIP_TRY(hipFuncSetAttribute((const void *)rc_post_attn_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RC_LDS));
+        HIP_TRY(hipFuncSetAttribute((const void *)rc_post_attn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, RC_LDS));
+        HIP_TRY(hipFuncSetAttribute((const void *)rc_post_attn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, RC_LDS));
+        HIP_TRY(hipFuncSetAttribute((const void *)rc_post_attn_wide_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, RC_LDS));
+        HIP_TRY(hipFuncSetAttribute((const void *)rc_post_attn_wide_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, RC_LDS));
         configured = true;
     }
     RcPostArgs a;
@@ -1824,6 +1859,7 @@ extern "C" SCP_API int scp_swin_post_attn(const void *Ohi, const void *Olo, int6
     a.dbg = g_rc_dbg;
     { const char *e = getenv("SCP_RC_DUMP"); a.dbg_mode = e ? atoi(e) : 0; }
     a.tile_list = tile_list; a.n_list = tile_list ? n_tiles : 0;
+    const bool frag = ldo_in == SCP_LDO_FRAG;         // the planes in fragment order (whole 128-row tiles) instead of rows
     const int ntiles = tile_list ? n_tiles : (M + RC_ROWS - 1) / RC_ROWS;
     const int ncu = rc_num_cu();
     // algorithmic work: the rows of the tiles processed (a tile list leaves out tiles of nothing but window padding)
@@ -1833,11 +1869,13 @@ extern "C" SCP_API int scp_swin_post_attn(const void *Ohi, const void *Olo, int6
     // fill the CUs and stream every weight byte once per 128 rows instead of 32
     if (rc_wide_mode() == 1 || (rc_wide_mode() < 0 && !g_rc_dbg && !a.dbg_mode && 4 * (int64_t)ntiles <= (int64_t)ncu)) {
         const int items = 4 * ntiles;
-        hipLaunchKernelGGL(rc_post_attn_wide_kernel, dim3((unsigned)(items < 2 * ncu ? items : 2 * ncu)), dim3(256), RC_LDS, (hipStream_t)stream, a);
+        if (frag) hipLaunchKernelGGL(rc_post_attn_wide_kernel<true>, dim3((unsigned)(items < 2 * ncu ? items : 2 * ncu)), dim3(256), RC_LDS, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL(rc_post_attn_wide_kernel<false>, dim3((unsigned)(items < 2 * ncu ? items : 2 * ncu)), dim3(256), RC_LDS, (hipStream_t)stream, a);
         LAUNCH_CHECK();
         return SCP_OK;
     }
-    hipLaunchKernelGGL(rc_post_attn_kernel, dim3((unsigned)(ntiles < ncu ? ntiles : ncu)), dim3(256), RC_LDS, (hipStream_t)stream, a);
+    if (frag) hipLaunchKernelGGL(rc_post_attn_kernel<true>, dim3((unsigned)(ntiles < ncu ? ntiles : ncu)), dim3(256), RC_LDS, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(rc_post_attn_kernel<false>, dim3((unsigned)(ntiles < ncu ? ntiles : ncu)), dim3(256), RC_LDS, (hipStream_t)stream, a);
     LAUNCH_CHECK();
     return SCP_OK;
 }

@@ -188,7 +188,8 @@ def _swin_layer_rowchain(layer, x, valid, wtab, shift, query=None, tiles=None, q
             # q_pre: the block's query projection, computed ahead by ehem_phase2_prepare (the decoder: it does not depend on the decoded symbols)
             q = q_pre if q_pre is not None else native.swin_ln_linear(query, w["q"], qbias, eps_b, v1)
             _, kvp = native.swin_ln_qkv(x, w["kv"], w["b"], eps_b, v1)
-        o = native.swin_attention_packed_planes(q, kvp, table, wtab, shift, split=True, valid=v1 if tiles is not None else None)
+        # the output leaves in the fragment order of the post-attention kernels (native.FragAct; SCP_ATTN_O=rows: as rows - the same bits)
+        o = native.swin_attention_packed_planes(q, kvp, table, wtab, shift, split=native.attn_o_split(), valid=v1 if tiles is not None else None)
         if tiles is not None and tiles.shape[0] > 0:
             return native.swin_post_attn(o, x, w["post"], eps_a, out=x, tiles=tiles)
         return native.swin_post_attn(o, x, w["post"], eps_a)

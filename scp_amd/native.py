@@ -474,12 +474,73 @@ class KvPlanes:
         self.t = t
 
 
+# How the attention output travels to swin_post_attn: "frag" (default) = planes in the fragment order of the post-attention kernels
+# (include/scp.h: SCP_LDO_FRAG), "rows" = row-major planes (SCP_ATTN_O=rows; tests and A/B measurements - identical bits either way).
+_ATTN_O = "rows" if os.environ.get("SCP_ATTN_O", "")[:1] == "r" else "frag"
+LDO_FRAG = 0
+
+
+def set_attn_o(mode):
+    """Select the hand-over of the attention output ("frag" / "rows"); returns the previous mode (tests, A/B)."""
+    global _ATTN_O
+    if mode not in ("frag", "rows"):
+        raise ScpError("attention output hand-over: 'frag' or 'rows'")
+    prev, _ATTN_O = _ATTN_O, mode
+    return prev
+
+
+def attn_o_split():
+    """The `split` argument of swin_attention_packed_planes for the hand-over in force: "frag", or True (rows)."""
+    return "frag" if _ATTN_O == "frag" else True
+
+
+class FragAct:
+    """The attention output [M, 256] as bf16 hi / lo planes in the FRAGMENT ORDER of the post-attention kernels (csrc/rowchain.hip): per
+    128-row tile and plane [32 chunks of 8 channels][128 rows][8].  `t`: bfloat16 [2, ceil(M / 128), 32, 128, 8]."""
+
+    __slots__ = ("t", "M", "K")
+
+    def __init__(self, t, M):
+        self.t, self.M, self.K = t, M, 256
+
+    @staticmethod
+    def empty(M, device):
+        return FragAct(torch.empty((2, -(-M // 128), 32, 128, 8), dtype=torch.bfloat16, device=device), M)
+
+    @staticmethod
+    def from_rows(a):
+        """SplitAct [M, 256] -> the same values in fragment order (rows behind M in the last tile: zero)."""
+        M = a.M
+        nt = -(-M // 128)
+        r = torch.zeros((2, nt * 128, 256), dtype=torch.bfloat16, device=a.t.device)
+        r[:, :M] = a.t[:, :, :256]
+        return FragAct(r.view(2, nt, 128, 32, 8).permute(0, 1, 3, 2, 4).contiguous(), M)
+
+    def rows(self):
+        """-> SplitAct [M, 256]: the planes un-permuted (element for element)."""
+        nt = self.t.shape[1]
+        return SplitAct(self.t.permute(0, 1, 3, 2, 4).reshape(2, nt * 128, 256)[:, :self.M].contiguous(), 256)
+
+    def float(self):
+        return self.rows().float()
+
+
 def swin_attention_packed_planes(q, kv, bias_table, wtab, shift, split=False, valid=None):
     """swin_attention_packed with K / V as KvPlanes: operands staged by LDS-DMA, no conversion in the kernel; identical bits.
-    valid (fp32 [T] / [T, 1], optional): query tiles of nothing but window padding are skipped, their output rows stay unwritten."""
+    valid (fp32 [T] / [T, 1], optional): query tiles of nothing but window padding are skipped, their output rows stay unwritten.
+    split=True: the output as a SplitAct (row-major planes); split="frag": as a FragAct - the hand-over to swin_post_attn (the same values)."""
     T = q.shape[0]
     p = kv.t
     vp = None if valid is None else _dev(valid, torch.float32)
+    if isinstance(split, str):
+        if split != "frag":
+            raise ScpError("swin_attention_packed_planes: split is False, True or 'frag'")
+        o = FragAct.empty(T, q.device)
+        rc = lib().scp_swin_attention_packed_planes(q.data_ptr(), p[0].data_ptr(), p[1].data_ptr(), p[2].data_ptr(), p[3].data_ptr(),
+                                                    _dev(bias_table, torch.float32), _dev(wtab, torch.int32), T // 512, shift, q.stride(0), None,
+                                                    o.t[0].data_ptr(), o.t[1].data_ptr(), LDO_FRAG, vp, _stream())
+        _check(rc, "scp_swin_attention_packed_planes")
+        return o
     if split:
         o = SplitAct.empty(T, 256, q.device)
         rc = lib().scp_swin_attention_packed_planes(q.data_ptr(), p[0].data_ptr(), p[1].data_ptr(), p[2].data_ptr(), p[3].data_ptr(),
@@ -1407,8 +1468,8 @@ class PostAttnWeights:
 
 
 def swin_post_attn(o, x, pw, eps=1e-5, out=None, tiles=None):
-    """x + proj(o) -> LayerNorm -> fc1 -> GELU -> fc2 -> + residual, one launch (csrc/rowchain.hip).  o: SplitAct [M, 256] (the attention
-    output planes), x: fp32 [M, 256] residual stream, pw: PostAttnWeights.  -> fp32 [M, 256] (`out` may be x itself).
+    """x + proj(o) -> LayerNorm -> fc1 -> GELU -> fc2 -> + residual, one launch (csrc/rowchain.hip).  o: FragAct or SplitAct [M, 256] (the
+    attention output planes, in fragment order or as rows), x: fp32 [M, 256] residual stream, pw: PostAttnWeights.  -> fp32 [M, 256] (`out` may be x itself).
     tiles (int32 device tensor, optional): the 128-row tiles to process (ascending); the others keep what `out` held (use out=x)."""
     M = x.shape[0]
     if o.K != 256 or o.M != M or x.shape[1] != 256 or x.stride(1) != 1:
@@ -1416,7 +1477,8 @@ def swin_post_attn(o, x, pw, eps=1e-5, out=None, tiles=None):
     if out is None:
         out = torch.empty((M, 256), dtype=torch.float32, device=x.device)
     t = o.t
-    rc = lib().scp_swin_post_attn(t[0].data_ptr(), t[1].data_ptr(), t.stride(1), x.data_ptr(), x.stride(0), pw.packed.data_ptr(), _dev(pw.bp),
+    ldo = LDO_FRAG if isinstance(o, FragAct) else t.stride(1)       # planes in fragment order / as rows
+    rc = lib().scp_swin_post_attn(t[0].data_ptr(), t[1].data_ptr(), ldo, x.data_ptr(), x.stride(0), pw.packed.data_ptr(), _dev(pw.bp),
                                   _dev(pw.b1), _dev(pw.b2), float(eps), out.data_ptr(), out.stride(0), M,
                                   None if tiles is None else _dev(tiles, torch.int32), 0 if tiles is None else int(tiles.shape[0]), _stream())
     _check(rc, "scp_swin_post_attn")
